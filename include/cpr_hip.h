@@ -478,6 +478,28 @@ int cpr_spin(long long ticks, void* stream);
  * inv_sigma (optional) = 1/sqrt(var+eps) */
 int cpr_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale,
                 float* shift, float* inv_sigma, int C, void* stream);
+/* training-mode BatchNorm (ResNet norm_eval=False: T/mmdet/models/backbones/resnet.py:647-657, torch.nn.BatchNorm2d in training mode)
+ * on an NHWC fp32 map y (M, C), M = N*H*W > 1, C % 64 == 0.  ws: cpr_bn_train_ws(M, C) floats.
+ * cpr_bn_batch_stats: mean, rstd = 1/sqrt(biased var + eps), scale = gamma*rstd and shift = beta - mean*scale (each (C); scale /
+ *   shift may be NULL); running_mean / running_var (both or neither) updated in place with the unbiased variance,
+ *   num_batches_tracked (int64, may be NULL when momentum >= 0) incremented; momentum < 0 = torch's momentum None (1 / count).
+ *   Per-(row block, channel) Welford partials merged by Chan's formula in a fixed order: bit-repeatable, no float atomics.
+ *   center / cmean / cshift (all or none): the centred form for maps whose mean is far above their spread -- center = the map's
+ *   first row, cmean = mean - center, cshift = beta - cmean*scale, so that (y - center)*scale + cshift normalises with an exact
+ *   first difference.
+ * cpr_bn_apply: out = [ReLU]((y - center)*scale + shift [+ residual] [+ (y2 - center2)*scale2 + shift2]); center / center2 may be
+ *   NULL (= 0); residual and y2 are exclusive (y2: the projection shortcut of a bottleneck, never materialised).
+ * cpr_bn_train_bwd: g = dout * (z > 0) (z = the recorded post-ReLU output, or NULL: g = dout); xhat = ((y - center) - mean)*rstd
+ *   (center NULL = 0; with the centred statistics: center, cmean); dbeta = sum g, dgamma = sum g*xhat (either may be NULL),
+ *   dy = gamma*rstd*(g - dbeta/M - xhat*dgamma/M). */
+int cpr_bn_train_ws(long long M, int C);
+int cpr_bn_batch_stats(const float* y, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                       long long* num_batches_tracked, float momentum, float eps, float* mean, float* rstd, float* scale, float* shift,
+                       float* center, float* cmean, float* cshift, float* ws, long long M, int C, void* stream);
+int cpr_bn_apply(const float* y, const float* center, const float* scale, const float* shift, const float* residual, const float* y2,
+                 const float* center2, const float* scale2, const float* shift2, float* out, long long M, int C, int relu, void* stream);
+int cpr_bn_train_bwd(const float* dout, const float* z, const float* y, const float* center, const float* mean, const float* rstd,
+                     const float* gamma, float* dy, float* dgamma, float* dbeta, float* ws, long long M, int C, void* stream);
 /* Multi-tensor forms of cpr_bn_fold and cpr_pack_weights_bf16 (round 6; the per-step refresh of the mixed-precision / fp32 training
  * step, layers._PackCache.refresh_all): one launch over a DEVICE table of 64-byte jobs --
  *   fold job: { const float *gamma, *beta, *mean, *var; float *scale, *shift, *inv (each may be NULL); int C; float eps; }

@@ -100,6 +100,10 @@ SIGNATURES = {
     'cpr_pack_weights_bf16': [_p, _p, _p, _p] + [_i] * 5 + [_p],
     'cpr_spin': [ctypes.c_longlong, _p],
     'cpr_bn_fold': [_p, _p, _p, _p, _f, _p, _p, _p, _i, _p],
+    'cpr_bn_train_ws': [_l, _i],
+    'cpr_bn_batch_stats': [_p] * 6 + [_f, _f] + [_p] * 8 + [_l, _i, _p],
+    'cpr_bn_apply': [_p] * 10 + [_l, _i, _i, _p],
+    'cpr_bn_train_bwd': [_p] * 11 + [_l, _i, _p],
     'cpr_p2p_loss_bwd': [_p] * 9 + [_i] * 5 + [_f] * 9 + [_p, _i, _i, _p],
     'cpr_grad_sumsq': [_p, _l, _p, _p, _i, _p],
     'cpr_sgd_step': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p],

@@ -88,6 +88,8 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     bb, neck, head = model.backbone, model.neck, model.bbox_head
     if neck is None or type(neck).__name__ != 'FPN' or len(neck.fpn_convs) != 1:
         return 'needs an FPN neck with num_outs == 1 (every shipped CPR / P2P config)'
+    if bb.compute_dtype != torch.float32 and bb.batch_stats_active():
+        return 'BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only, not with the bf16 compute mode'
     if bb.compute_dtype != torch.float32 and type(head).__name__ != 'CPRHead':
         return 'the mixed-precision step (bf16 compute mode) covers the CPR locator; P2PNet trains in fp32'
     if any(p.requires_grad for m in (bb.conv1, bb.bn1) for p in m.parameters()):

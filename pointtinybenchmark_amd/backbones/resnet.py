@@ -2,8 +2,10 @@
 
 Interface of T/mmdet/models/backbones/resnet.py:305-657 (ctor kwargs, ``forward(x) -> tuple`` of the
 ``out_indices`` stage outputs, ``frozen_stages`` / ``norm_eval`` train() semantics, state-dict keys).
-BatchNorm is always evaluated with running statistics on this path (norm_eval=True in every CPR/P2P config)
-and is folded into the conv epilogue; the bottleneck shortcut add + ReLU are fused into conv3's epilogue.
+BatchNorm in eval mode (norm_eval=True, every CPR/P2P config; or model.eval()) uses running statistics and is folded into the
+conv epilogue; the bottleneck shortcut add + ReLU are fused into conv3's epilogue.  With norm_eval=False the BatchNorm modules of the
+non-frozen stages are in training mode (the reference's ``train()``) and normalise with batch statistics: raw conv, statistics pass,
+normalise / residual / ReLU pass (csrc/bn_train.hip), running statistics updated on the device.
 The backward of the trainable stages is driven by training.CprTrainer from the per-block records of ``forward(tape=)``."""
 import os
 
@@ -18,26 +20,45 @@ from ..registry import BACKBONES
 FUSE_SHORTCUT = [os.environ.get('CPR_FUSE_SHORTCUT', '1') == '1']   # A/B switch (tests, tools)
 
 
+def _bn_not_mixed():
+    return NotImplementedError('BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only: the bf16 compute '
+                               'mode (mixed precision) keeps norm_eval=True')
+
+
 class _Block(nn.Module):
-    def __init__(self, kind, inplanes, planes, stride, downsample):
+    def __init__(self, kind, inplanes, planes, stride, downsample, norm=nn.BatchNorm2d):
         super().__init__()
         self.kind = kind
         if kind == 'bottleneck':  # style='pytorch': the stride sits on the 3x3 (resnet.py:153-158)
             self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-            self.bn1 = nn.BatchNorm2d(planes)
+            self.bn1 = norm(planes)
             self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
-            self.bn2 = nn.BatchNorm2d(planes)
+            self.bn2 = norm(planes)
             self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
-            self.bn3 = nn.BatchNorm2d(planes * 4)
+            self.bn3 = norm(planes * 4)
         else:
             self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
-            self.bn1 = nn.BatchNorm2d(planes)
+            self.bn1 = norm(planes)
             self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
-            self.bn2 = nn.BatchNorm2d(planes)
+            self.bn2 = norm(planes)
         self.downsample = downsample
+
+    def _norms(self):
+        return [self.bn1, self.bn2] + ([self.bn3] if self.kind == 'bottleneck' else []) + \
+            ([self.downsample[1]] if self.downsample is not None else [])
+
+    def batch_stats(self):
+        """True when this block's BatchNorms normalise with batch statistics (training mode, norm_eval=False, stage not frozen)."""
+        modes = {self.training and bn.training for bn in self._norms()}
+        if len(modes) > 1:
+            raise NotImplementedError('a block whose BatchNorm modules are partly in training mode (set the modes through '
+                                      'ResNet.train / norm_eval)')
+        return modes.pop()
 
     def run(self, cache, x, save=None):
         """save (dict): training mode -- keeps the block's activations for the backward pass."""
+        if self.batch_stats():
+            return self._run_batch_stats(cache, x, save)
         identity = x
         dt = x.dtype
         # forward-only fp32 bottleneck with a projection shortcut: the shortcut GEMM rides in conv3's launch (bit-identical,
@@ -66,6 +87,41 @@ class _Block(nn.Module):
             save.update(block=self, x=x, o1=o1, o2=o2, identity=identity, out=out)
         return out
 
+    def _run_batch_stats(self, cache, x, save):
+        """Training-mode BatchNorm: raw conv (unscaled pack, no epilogue affine) -> batch statistics (running buffers updated) ->
+        normalise (+ shortcut) (+ ReLU).  The projection shortcut of a bottleneck joins in conv3's apply pass (two-input form);
+        nothing here takes the fused-shortcut conv2d_dual path.  save: the pre-BN maps y* and each BN's statistics (ops.BnStats) as well."""
+        if x.dtype != torch.float32:
+            raise _bn_not_mixed()
+        stats = {}
+
+        def conv_stats(name, conv, bn, inp):
+            y = ops.conv2d(inp, packed_conv(cache, conv, torch.float32))
+            stats[name] = ops.bn_batch_stats(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                             bn.momentum, bn.eps)
+            return y, stats[name]
+
+        y1, t1 = conv_stats('bn1', self.conv1, self.bn1, x)
+        o1 = ops.bn_apply(y1, t1.scale, t1.cshift, center=t1.center, relu=True)
+        y2, t2 = conv_stats('bn2', self.conv2, self.bn2, o1)
+        yd = o2 = y3 = None
+        if self.downsample is not None:
+            yd, td = conv_stats('bnd', self.downsample[0], self.downsample[1], x)
+        if self.kind == 'bottleneck':
+            o2 = ops.bn_apply(y2, t2.scale, t2.cshift, center=t2.center, relu=True)
+            y3, tl = conv_stats('bn3', self.conv3, self.bn3, o2)
+            yl = y3
+        else:
+            yl, tl = y2, t2
+        if self.downsample is not None:
+            out = ops.bn_apply(yl, tl.scale, tl.cshift, center=tl.center, y2=yd, scale2=td.scale, shift2=td.cshift, center2=td.center,
+                               relu=True)
+        else:
+            out = ops.bn_apply(yl, tl.scale, tl.cshift, center=tl.center, residual=x, relu=True)
+        if save is not None:
+            save.update(block=self, x=x, o1=o1, o2=o2, out=out, y1=y1, y2=y2, y3=y3, yd=yd, stats=stats, batch_stats=True)
+        return out
+
 
 F32_STEM = [os.environ.get('CPR_F32_STEM', '1') != '0']       # 0: stem conv on the implicit-GEMM kernel + separate max-pool (A/B, tests)
 BF16_STEM_POOL = [os.environ.get('CPR_BF16_STEM_POOL', '1') != '0']   # 0: stem conv and max-pool as two kernels
@@ -88,14 +144,17 @@ class ResNet(nn.Module):
         assert style == 'pytorch' and not deep_stem and not avg_down and dcn is None and plugins is None, \
             'only the options used by the CPR/P2P configs are built (SURVEY.md §2a row 5)'
         assert tuple(dilations[:num_stages]) == (1,) * num_stages and norm_cfg.get('type') == 'BN'
-        assert norm_eval, 'BatchNorm batch statistics are not on this path (every CPR/P2P config sets norm_eval=True)'
+        bn_kw = {'momentum': norm_cfg['momentum']} if 'momentum' in norm_cfg else {}     # (mmcv build_norm_layer)
+
+        def norm(c):
+            return nn.BatchNorm2d(c, **bn_kw)
         self.depth, self.num_stages, self.out_indices = depth, num_stages, tuple(out_indices)
         self.frozen_stages, self.norm_eval = frozen_stages, norm_eval
         kind, blocks = self.arch_settings[depth]
         exp = 4 if kind == 'bottleneck' else 1
         stem = stem_channels or base_channels
         self.conv1 = nn.Conv2d(in_channels, stem, 7, 2, 3, bias=False)
-        self.bn1 = nn.BatchNorm2d(stem)
+        self.bn1 = norm(stem)
         inplanes = stem
         self.res_layers = []
         for i in range(num_stages):
@@ -105,9 +164,8 @@ class ResNet(nn.Module):
                 stride = strides[i] if bi == 0 else 1
                 ds = None
                 if bi == 0 and (stride != 1 or inplanes != planes * exp):
-                    ds = nn.Sequential(nn.Conv2d(inplanes, planes * exp, 1, stride, bias=False),
-                                       nn.BatchNorm2d(planes * exp))
-                layer.append(_Block(kind, inplanes, planes, stride, ds))
+                    ds = nn.Sequential(nn.Conv2d(inplanes, planes * exp, 1, stride, bias=False), norm(planes * exp))
+                layer.append(_Block(kind, inplanes, planes, stride, ds, norm))
                 inplanes = planes * exp
             name = 'layer%d' % (i + 1)
             self.add_module(name, nn.Sequential(*layer))
@@ -121,17 +179,33 @@ class ResNet(nn.Module):
 
     def _freeze_stages(self):  # resnet.py:612-628
         if self.frozen_stages >= 0:
+            self.bn1.eval()
             for m in (self.conv1, self.bn1):
                 for p in m.parameters():
                     p.requires_grad = False
         for i in range(1, self.frozen_stages + 1):
-            for p in getattr(self, 'layer%d' % i).parameters():
+            m = getattr(self, 'layer%d' % i)
+            m.eval()
+            for p in m.parameters():
                 p.requires_grad = False
 
-    def train(self, mode=True):
+    def train(self, mode=True):  # resnet.py:647-657
         super().train(mode)
         self._freeze_stages()
+        if mode and self.norm_eval:
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    m.eval()
         return self
+
+    def batch_stats_active(self):
+        """True when some BatchNorm of this backbone normalises with batch statistics in the next forward."""
+        return (self.training and self.bn1.training) or any(blk.batch_stats() for name in self.res_layers
+                                                             for blk in getattr(self, name))
+
+    def _check_mode(self):
+        if self.compute_dtype != torch.float32 and self.batch_stats_active():
+            raise _bn_not_mixed()
 
     def init_weights(self):
         """The reference's default init_cfg when no checkpoint is given (resnet.py:404-424; the configs name
@@ -156,8 +230,17 @@ class ResNet(nn.Module):
     def stem(self, x):
         """(N,3,H,W) image -> the NHWC map after conv1 + bn1 + ReLU + max-pool (resnet.py:630-637)."""
         c = self._cache
-        s, b = folded_bn(c, self.bn1)
         c1 = self.conv1
+        if self.training and self.bn1.training:
+            # a stem BatchNorm in training mode (frozen_stages < 0, norm_eval=False; forward only: a trainable stem has no backward rule):
+            # the implicit-GEMM stem conv, batch statistics, normalise + ReLU, then the max-pool
+            self._check_mode()
+            x = ops.from_nchw(x) if (x.shape[1] > 4 or (x.shape[1] == 4 and x.stride(1) == 1)) else ops.nchw_to_nhwc(x)
+            y = ops.conv2d(x, packed_conv(c, c1))
+            bn = self.bn1
+            t = ops.bn_batch_stats(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps)
+            return ops.maxpool3x3s2(ops.bn_apply(y, t.scale, t.cshift, center=t.center, relu=True))
+        s, b = folded_bn(c, self.bn1)
         std7 = tuple(c1.weight.shape) == (64, 3, 7, 7) and c1.stride == (2, 2) and c1.padding == (3, 3)
         # the fused stem kernels read the three planes of a contiguous (N,3,H,W) fp32 image themselves (no nchw_to_nhwc4 pass)
         planar = std7 and x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] == 3 and x.is_contiguous() and \
@@ -185,6 +268,7 @@ class ResNet(nn.Module):
 
     def run_stage(self, i, x, tape=None):
         """Stage ``i`` (``layer{i+1}``) on an NHWC map.  tape (list): one record per block with trainable parameters."""
+        self._check_mode()
         for blk in getattr(self, self.res_layers[i]):
             rec = None
             if tape is not None and blk.conv1.weight.requires_grad:
@@ -196,6 +280,7 @@ class ResNet(nn.Module):
     def forward(self, x, tape=None):
         """x: (N,3,H,W) -> tuple of NCHW-shaped (channels_last) stage outputs.
         tape (list): training mode -- one record per block with trainable parameters, in forward order."""
+        self._check_mode()
         x = self.stem(x)
         outs = []
         for i in range(len(self.res_layers)):

@@ -103,7 +103,8 @@ class BasicLocator(nn.Module):
                                                      gt_true_bboxes)
             autograd_bridge.warn_once(why)
         k = int(os.environ.get('CPR_STREAMS', self.num_streams))
-        if k > 1 and img.is_cuda and hasattr(self.bbox_head, 'loss'):
+        # batch statistics are taken over the whole batch: a backbone with training-mode BatchNorm (norm_eval=False) runs single-stream
+        if k > 1 and img.is_cuda and hasattr(self.bbox_head, 'loss') and not self.backbone.batch_stats_active():
             outs = self._towers_multistream(img, k)
             return self.bbox_head.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore,
                                        **({'gt_true_bboxes': gt_true_bboxes} if 'CPR' in type(self.bbox_head).__name__

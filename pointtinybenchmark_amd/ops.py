@@ -5,6 +5,7 @@ hand-written HIP kernel from libcprhip.so on the current HIP stream.
 Activations are NHWC fp32 (see csrc/conv_mfma.hip for why).  ``as_nchw`` / ``from_nchw`` expose them as
 NCHW-shaped (channels_last-strided) tensors, which is what crosses the reference's module boundaries.
 """
+import collections
 import ctypes
 import math
 import os
@@ -495,6 +496,93 @@ def bn_fold(gamma, beta, mean, var, eps, want_inv_sigma=False):
     _lib.call('cpr_bn_fold', _ptr(_check(gamma.detach())), _ptr(_check(beta.detach())), _ptr(_check(mean)), _ptr(_check(var)),
               float(eps), _ptr(scale), _ptr(shift), _ptr(inv), C, _stream())
     return scale, shift, inv
+
+
+# ---- training-mode BatchNorm (batch statistics; ResNet norm_eval=False) -- csrc/bn_train.hip
+def _bn_rows(y):
+    C = y.shape[-1]
+    M = y.numel() // C
+    if M <= 1:
+        # torch.nn.functional.batch_norm's refusal (_verify_batch_size)
+        raise ValueError('Expected more than 1 value per channel when training, got input size %s' % (tuple(y.shape),))
+    assert C % 64 == 0, 'training-mode BatchNorm needs C % 64 == 0, got %d' % C
+    return M, C
+
+
+def _bn_vec(t, C):
+    """A per-channel (C,) operand of the bn_train.hip kernels (read with 16-byte loads): fp32, contiguous, exactly C long; None passes."""
+    if t is None:
+        return None
+    t = _check(t.detach())
+    assert t.numel() == C, 'per-channel vector of %d elements, want %d' % (t.numel(), C)
+    return t
+
+
+BnStats = collections.namedtuple('BnStats', 'mean rstd scale shift center cmean cshift')
+
+
+def bn_batch_stats(y, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1, eps=1e-5):
+    """Batch statistics of an NHWC fp32 map y (..., C) -> BnStats of (C,) vectors: mean, rstd = 1/sqrt(biased var + eps),
+    scale = gamma*rstd, shift = beta - mean*scale, and the centred form the product path applies and differentiates with --
+    center = the map's first row, cmean = mean - center, cshift = beta - cmean*scale: (y - center)*scale + cshift has an exact first
+    difference, so a map whose mean is far above its spread normalises to the precision of its spread.  running_mean / running_var are updated in place as torch's training-mode
+    BatchNorm does (unbiased variance; momentum None: 1 / num_batches_tracked), num_batches_tracked incremented -- on the device.
+    The kernel writes the buffers through raw pointers: their version counters are bumped here so that anything keyed on them
+    (layers._PackCache: the folded eval-mode BatchNorm) sees the change."""
+    M, C = _bn_rows(_check(y))
+    dev = y.device
+    st = torch.empty((7, C), device=dev, dtype=torch.float32)
+    ws = torch.empty((_lib.call('cpr_bn_train_ws', M, C, positive=True),), device=dev, dtype=torch.float32)
+    if momentum is None:
+        assert num_batches_tracked is not None, 'momentum None averages over num_batches_tracked'
+    assert (running_mean is None) == (running_var is None), 'running_mean and running_var go together'
+    bufs = [t for t in (running_mean, running_var) if t is not None]
+    for t in bufs:
+        _bn_vec(t, C)
+    if num_batches_tracked is not None:
+        assert _check(num_batches_tracked, torch.int64).numel() == 1
+    _lib.call('cpr_bn_batch_stats', _ptr(y), _ptr(_bn_vec(gamma, C)), _ptr(_bn_vec(beta, C)), _ptr(running_mean),
+              _ptr(running_var), _ptr(num_batches_tracked), -1.0 if momentum is None else float(momentum), float(eps),
+              _ptr(st[0]), _ptr(st[1]), _ptr(st[2]), _ptr(st[3]), _ptr(st[4]), _ptr(st[5]), _ptr(st[6]), _ptr(ws), M, C, _stream())
+    from torch.autograd.graph import increment_version
+    for t in bufs + ([num_batches_tracked] if num_batches_tracked is not None else []):
+        increment_version(t)
+    return BnStats(*st.unbind(0))
+
+
+def bn_apply(y, scale, shift, residual=None, relu=False, center=None, y2=None, scale2=None, shift2=None, center2=None, out=None):
+    """out = [ReLU]((y - center)*scale + shift [+ residual]) (center None = 0), or the two-input form of a bottleneck with a projection
+    shortcut: out = [ReLU]((y - center)*scale + shift + (y2 - center2)*scale2 + shift2) -- the shortcut is never materialised."""
+    M, C = y.numel() // _check(y).shape[-1], y.shape[-1]
+    for t in (residual, y2):
+        if t is not None:
+            assert _check(t).shape == y.shape, (t.shape, y.shape)
+    assert residual is None or y2 is None
+    assert y2 is not None or (scale2 is None and shift2 is None and center2 is None), 'scale2 / shift2 / center2 belong to y2'
+    assert y2 is None or (scale2 is not None and shift2 is not None), 'the two-input form needs scale2 and shift2'
+    if out is None:
+        out = torch.empty_like(y)
+    assert _check(out).shape == y.shape
+    _lib.call('cpr_bn_apply', _ptr(y), _ptr(_bn_vec(center, C)), _ptr(_bn_vec(scale, C)), _ptr(_bn_vec(shift, C)), _ptr(residual),
+              _ptr(y2), _ptr(_bn_vec(center2, C)), _ptr(_bn_vec(scale2, C)), _ptr(_bn_vec(shift2, C)), _ptr(out), M, C, int(relu),
+              _stream())
+    return out
+
+
+def bn_train_bwd(dout, y, mean, rstd, gamma, mask=None, out_dgamma=None, out_dbeta=None, center=None):
+    """Backward of training-mode BatchNorm (xhat = ((y - center) - mean)*rstd: pass BnStats' center and cmean for the centred form) (+ the ReLU whose output is ``mask``, when given: g = dout*(mask > 0), applied on the fly,
+    never written) -> (dy, dgamma, dbeta): dbeta = sum g, dgamma = sum g*xhat, dy = gamma*rstd*(g - dbeta/M - xhat*dgamma/M).
+    out_dgamma / out_dbeta: where the parameter gradients go (e.g. the trainer's gradient views); default fresh tensors."""
+    M, C = _bn_rows(_check(y))
+    assert _check(dout).shape == y.shape and (mask is None or _check(mask).shape == y.shape)
+    dev = y.device
+    dg = out_dgamma if out_dgamma is not None else torch.empty((C,), device=dev, dtype=torch.float32)
+    db = out_dbeta if out_dbeta is not None else torch.empty((C,), device=dev, dtype=torch.float32)
+    dy = torch.empty_like(y)
+    ws = torch.empty((_lib.call('cpr_bn_train_ws', M, C, positive=True),), device=dev, dtype=torch.float32)
+    _lib.call('cpr_bn_train_bwd', _ptr(dout), _ptr(mask), _ptr(y), _ptr(_bn_vec(center, C)), _ptr(_bn_vec(mean, C)), _ptr(_bn_vec(rstd, C)),
+              _ptr(_bn_vec(gamma, C)), _ptr(dy), _ptr(_bn_vec(dg, C)), _ptr(_bn_vec(db, C)), _ptr(ws), M, C, _stream())
+    return dy, dg, db
 
 
 def stem_weight_f32(weight):

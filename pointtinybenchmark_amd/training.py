@@ -793,6 +793,8 @@ class BackwardEngine:
         # the recorded maps are handed on as recorded (bf16 in the mixed-precision step): the ReLU masks are read as they are, the bf16
         # gradient kernels read x as it is, and only an fp32 fallback kernel widens what it reads (round 6: rounds 3-5 widened every
         # recorded map up front -- 5.6 % of the step's kernel time in torch copy kernels)
+        if rec.get('batch_stats'):
+            return self._block_backward_batch_stats(cache, blk, rec, dout, need_dx)
         mixed = self._mixed
         x = rec['x']
         if isinstance(dout, tuple):
@@ -825,6 +827,61 @@ class BackwardEngine:
             tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
         else:
             dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3, g16=g1h)
+            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
+        self._done(tail)
+        return dx
+
+    # ------------------------------------------------------------------ training-mode BatchNorm (ResNet norm_eval=False)
+    def _conv_bn_backward_batch_stats(self, cache, conv, bn, rec, key, g, mask, x, need_dx, add=None):
+        """conv -> batch-statistics BN given the gradient ``g`` of the BN output (``mask``: that output's ReLU, applied on the fly).
+        dgamma / dbeta are written by the BN backward itself (main stream), the weight gradient goes to the side stream; returns the
+        data gradient wrt x (+ ``add``), through the UNSCALED weights."""
+        st = rec['stats'][key]
+        aff = bn.weight.requires_grad
+        dy, _, _ = ops.bn_train_bwd(g, rec['y' + key[2:]], st.cmean, st.rstd, bn.weight, mask=mask, center=st.center,
+                                    out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
+        w = conv.weight
+        if w.requires_grad:
+            def param_grads():
+                ops.conv2d_wgrad(dy, x, w.shape, conv.stride[0], conv.padding[0], out=self._g(w))
+            self._param_side(param_grads, dy, x)
+        if not need_dx:
+            return None
+        pt = cache.get(('dgrad_raw', id(conv)), [w], lambda: ops.dgrad_pack(w, conv.stride[0], conv.padding[0]),
+                       refresh=lambda q: ('pack32', w, None, q, 1) if isinstance(q, ops.PackedConv) and
+                       w.dtype == torch.float32 and w.is_contiguous() else None)
+        return ops.conv2d_dgrad(dy, pt, (x.shape[1], x.shape[2]), conv.stride[0], add=add)
+
+    def _block_backward_batch_stats(self, cache, blk, rec, dout, need_dx):
+        """A block recorded with batch-statistics BatchNorm (resnet._Block._run_batch_stats): same parameter order and ``_done``
+        points as the folded rule; returns the plain gradient wrt the block input (its ReLU is the block below's mask)."""
+        x = rec['x']
+        if isinstance(dout, tuple):       # the block above already took it through this block's output ReLU
+            g3, m3 = dout[0], None
+        else:
+            g3, m3 = dout, rec['out']
+        ident = None
+        if blk.downsample is None and need_dx:
+            if m3 is not None:            # the identity shortcut's gradient is the masked map itself
+                g3 = ops.relu_bwd_colsum(g3, m3)[0]
+                m3 = None
+            ident = g3
+        o1 = rec['o1']
+        if blk.kind == 'bottleneck':
+            o2 = rec['o2']
+            d2 = self._conv_bn_backward_batch_stats(cache, blk.conv3, blk.bn3, rec, 'bn3', g3, m3, o2, True)
+            d1 = self._conv_bn_backward_batch_stats(cache, blk.conv2, blk.bn2, rec, 'bn2', d2, o2, o1, True)
+            last = blk.bn3
+        else:
+            d1 = self._conv_bn_backward_batch_stats(cache, blk.conv2, blk.bn2, rec, 'bn2', g3, m3, o1, True)
+            last = blk.bn2
+        self._done(last.bias if last.bias.requires_grad else blk.conv2.weight)
+        dx = self._conv_bn_backward_batch_stats(cache, blk.conv1, blk.bn1, rec, 'bn1', d1, o1, x, need_dx, add=ident)
+        if blk.downsample is not None:
+            dx = self._conv_bn_backward_batch_stats(cache, blk.downsample[0], blk.downsample[1], rec, 'bnd', g3, m3, x, need_dx,
+                                                    add=dx)
+            tail = blk.downsample[1].bias if blk.downsample[1].bias.requires_grad else blk.downsample[0].weight
+        else:
             tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
         self._done(tail)
         return dx
