@@ -500,6 +500,27 @@ int cpr_bn_apply(const float* y, const float* center, const float* scale, const 
                  const float* center2, const float* scale2, const float* shift2, float* out, long long M, int C, int relu, void* stream);
 int cpr_bn_train_bwd(const float* dout, const float* z, const float* y, const float* center, const float* mean, const float* rstd,
                      const float* gamma, float* dy, float* dgamma, float* dbeta, float* ws, long long M, int C, void* stream);
+/* P2PHead's output convolutions in the bf16 compute mode (csrc/p2p_out_bf16.hip): a 3x3 / pad 1 / stride 1 conv with bias from the
+ * RAW bf16 NHWC map x (N,H,W,Cin) of the last tower layer -- read as relu(a*x + b) with its per-(image, channel) GroupNorm affine
+ * a, b (N,Cin) fp32, the activation never written -- to J output channels.  w (J,Cin,3,3) and bias (J) fp32 (the nn.Conv2d
+ * parameters as they are).  Cin in {64, 128, 192, 256}, 1 <= J <= 8, any H, W; returns CPR_ERR_UNSUPPORTED outside that.
+ * Arithmetic: every bf16 element widened exactly, relu(fmaf(a, x, b)) in fp32, products and sums fp32 (no bf16 rounding of the
+ * activation).
+ * cpr_p2p_out_bf16_fwd: out (N,H,W,J) fp32.  taps (N,H,W,9J) fp32 workspace: the tap responses, summed by cpr_tap_sum3x3 (the
+ *   second of the two launches this entry enqueues).
+ * cpr_p2p_out_bf16_dgrad: dx (N,H,W,Cin) <- the gradient wrt the ACTIVATED input, sum over taps and j of dout * w (x, a, b not
+ *   needed); dout (N,H,W,J) fp32 with row stride ldd >= J (a channel-padded gradient map is read as it is); out_bf16: dx is bf16,
+ *   each element the round-to-nearest-even of the fp32 value, else fp32.
+ * cpr_p2p_out_bf16_wgrad: gw (J,Cin,3,3) and gb (J) WRITTEN (caller-given, e.g. a trainer's gradient views) from dout and the
+ *   activated map.  Per-wave partials over fixed pixel ranges into ws (cpr_p2p_out_bf16_wgrad_ws floats), summed in a fixed order
+ *   by a finalize launch: bit-repeatable, no float atomics. */
+int cpr_p2p_out_bf16_fwd(const void* x, const float* a, const float* b, const float* w, const float* bias, float* taps, float* out,
+                         int N, int H, int W, int Cin, int J, void* stream);
+int cpr_p2p_out_bf16_dgrad(const float* dout, int ldd, const float* w, void* dx, int out_bf16, int N, int H, int W, int Cin, int J,
+                           void* stream);
+int cpr_p2p_out_bf16_wgrad_ws(int N, int H, int W, int Cin, int J);
+int cpr_p2p_out_bf16_wgrad(const void* x, const float* a, const float* b, const float* dout, int ldd, float* gw, float* gb, float* ws,
+                           int N, int H, int W, int Cin, int J, void* stream);
 /* Multi-tensor forms of cpr_bn_fold and cpr_pack_weights_bf16 (round 6; the per-step refresh of the mixed-precision / fp32 training
  * step, layers._PackCache.refresh_all): one launch over a DEVICE table of 64-byte jobs --
  *   fold job: { const float *gamma, *beta, *mean, *var; float *scale, *shift, *inv (each may be NULL); int C; float eps; }

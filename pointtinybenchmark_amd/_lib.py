@@ -104,6 +104,10 @@ SIGNATURES = {
     'cpr_bn_batch_stats': [_p] * 6 + [_f, _f] + [_p] * 8 + [_l, _i, _p],
     'cpr_bn_apply': [_p] * 10 + [_l, _i, _i, _p],
     'cpr_bn_train_bwd': [_p] * 11 + [_l, _i, _p],
+    'cpr_p2p_out_bf16_fwd': [_p] * 7 + [_i] * 5 + [_p],
+    'cpr_p2p_out_bf16_dgrad': [_p, _i, _p, _p] + [_i] * 6 + [_p],
+    'cpr_p2p_out_bf16_wgrad_ws': [_i] * 5,
+    'cpr_p2p_out_bf16_wgrad': [_p] * 4 + [_i] + [_p] * 3 + [_i] * 5 + [_p],
     'cpr_p2p_loss_bwd': [_p] * 9 + [_i] * 5 + [_f] * 9 + [_p, _i, _i, _p],
     'cpr_grad_sumsq': [_p, _l, _p, _p, _i, _p],
     'cpr_sgd_step': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p],

@@ -90,8 +90,8 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
         return 'needs an FPN neck with num_outs == 1 (every shipped CPR / P2P config)'
     if bb.compute_dtype != torch.float32 and bb.batch_stats_active():
         return 'BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only, not with the bf16 compute mode'
-    if bb.compute_dtype != torch.float32 and type(head).__name__ != 'CPRHead':
-        return 'the mixed-precision step (bf16 compute mode) covers the CPR locator; P2PNet trains in fp32'
+    if bb.compute_dtype != torch.float32 and type(head).__name__ not in ('CPRHead', 'P2PHead'):
+        return 'the mixed-precision step (bf16 compute mode) covers the CPR and P2P locators'
     if any(p.requires_grad for m in (bb.conv1, bb.bn1) for p in m.parameters()):
         return 'a trainable stem (frozen_stages < 0) has no backward rule'
     if tuple(bb.out_indices) != tuple(range(len(bb.res_layers))):

@@ -97,6 +97,8 @@ class P2PHead(nn.Module):
             x, ab = conv_gn(self._cache, m, x, in_ab=ab, in_relu=True, materialize=False, save=rec)
         H, W = x.shape[1:3]
         J = out_conv.out_channels
+        if x.dtype == torch.bfloat16:
+            return self._out_conv_bf16(out_conv, x, ab, tape)
         if tape is None and TAP_PROJECTION[0] and x.dtype == torch.float32 and 9 * J <= 64 and out_conv.kernel_size == (3, 3) \
                 and out_conv.padding == (1, 1) and out_conv.stride == (1, 1):
             # forward only: a 3x3 conv with 1-2 output channels wastes 97 % of a 64-cout matrix-core tile; as a 1x1 projection to
@@ -114,6 +116,20 @@ class P2PHead(nn.Module):
         if (H * W) % 128 == 0:
             return ops.conv2d(x, pc, bias=out_conv.bias, in_ab=ab, in_relu=True)
         return ops.conv2d(ops.gn_apply(x, ab[0], ab[1], relu=True), pc, bias=out_conv.bias)
+
+    def _out_conv_bf16(self, out_conv, x, ab, tape=None):
+        """bf16 compute mode: the output conv over the raw bf16 last tower layer x with its GroupNorm affine ab (+ReLU) -> fp32
+        (N,H,W,J), so the loss, the assignment and the post-processing are those of the fp32 mode.  J <= 8: csrc/p2p_out_bf16.hip
+        (the activation is applied on load and kept in fp32); larger J (15 / 80-class heads): the activation is materialised in bf16
+        and the bf16 matrix-core conv writes fp32."""
+        assert out_conv.kernel_size == (3, 3) and out_conv.padding == (1, 1) and out_conv.stride == (1, 1)
+        J = out_conv.out_channels
+        if tape is not None:
+            tape.append(dict(kind='out', conv=out_conv, x=x, in_ab=ab))
+        if ops.p2p_out_bf16_supported(x.shape, J):
+            return ops.p2p_out_bf16(x, ab, out_conv.weight.detach(), out_conv.bias.detach())
+        pc = packed_conv(self._cache, out_conv, torch.bfloat16)
+        return ops.conv2d(ops.gn_apply(x, ab[0], ab[1], relu=True), pc, bias=out_conv.bias.detach(), out_dtype=torch.float32)
 
     def forward_single(self, feat):
         x = ops.from_nchw(feat)

@@ -722,6 +722,76 @@ def logit_project(x, w, bias, in_ab=None, in_relu=True):
     return out
 
 
+def p2p_out_bf16_supported(x_shape, J):
+    """Whether the bf16 output-conv kernels (csrc/p2p_out_bf16.hip) cover a map of this shape with J output channels."""
+    return len(x_shape) == 4 and 1 <= J <= 8 and x_shape[3] in (64, 128, 192, 256)
+
+
+def _p2p_out_args(x, ab, w):
+    _check(x, torch.bfloat16)
+    N, H, W, Cin = x.shape
+    J = w.shape[0]
+    assert tuple(w.shape) == (J, Cin, 3, 3), (tuple(w.shape), Cin)
+    a, b = ab
+    assert tuple(_check(a).shape) == (N, Cin) and tuple(_check(b).shape) == (N, Cin), (a.shape, b.shape)
+    return N, H, W, Cin, J
+
+
+def p2p_out_bf16(x, ab, w, bias):
+    """P2PHead output conv on the bf16 map: x (N,H,W,Cin) RAW bf16 last tower layer, ab = its GroupNorm affine (a, b) (N,Cin), read as
+    relu(a*x + b); w (J,Cin,3,3), bias (J) fp32 -> (N,H,W,J) fp32.  None when the shape is outside the kernel (p2p_out_bf16_supported)."""
+    if not p2p_out_bf16_supported(x.shape, w.shape[0]):
+        return None
+    N, H, W, Cin, J = _p2p_out_args(x, ab, w)
+    assert tuple(_check(bias).shape) == (J,)
+    taps = torch.empty((N, H, W, 9 * J), device=x.device, dtype=torch.float32)
+    out = torch.empty((N, H, W, J), device=x.device, dtype=torch.float32)
+    _lib.call('cpr_p2p_out_bf16_fwd', _ptr(x), _ptr(ab[0]), _ptr(ab[1]), _ptr(_check(w)), _ptr(bias), _ptr(taps), _ptr(out),
+              N, H, W, Cin, J, _stream())
+    return out
+
+
+def _dout_rows(dout, N, H, W, J):
+    """dout (N,H,W,Jd >= J) fp32: the first J channels are read (a channel-padded gradient map as it is)."""
+    assert dout.dtype == torch.float32 and dout.is_cuda and dout.is_contiguous() and tuple(dout.shape[:3]) == (N, H, W) \
+        and dout.shape[3] >= J, (tuple(dout.shape), (N, H, W, J))
+    return dout.shape[3]
+
+
+def p2p_out_bf16_dgrad(dout, w, x_shape, out_dtype=torch.float32):
+    """Data gradient of the output conv wrt its ACTIVATED input: dout (N,H,W,Jd) fp32 (first J = w.shape[0] channels live), w
+    (J,Cin,3,3) -> (N,H,W,Cin) fp32, or bf16 (each element the round-to-nearest-even of the fp32 result).  None when unsupported."""
+    J = w.shape[0]
+    if not p2p_out_bf16_supported(x_shape, J):
+        return None
+    N, H, W, Cin = x_shape
+    assert tuple(_check(w).shape) == (J, Cin, 3, 3) and out_dtype in ACT
+    ldd = _dout_rows(dout, N, H, W, J)
+    dx = torch.empty((N, H, W, Cin), device=dout.device, dtype=out_dtype)
+    _lib.call('cpr_p2p_out_bf16_dgrad', _ptr(dout), ldd, _ptr(w), _ptr(dx), int(out_dtype == torch.bfloat16), N, H, W, Cin, J,
+              _stream())
+    return dx
+
+
+def p2p_out_bf16_wgrad(dout, x, ab, weight_shape, out_w=None, out_b=None):
+    """Weight and bias gradients of the output conv: dout (N,H,W,Jd) fp32 (first J live), x / ab as in p2p_out_bf16 -> (gw (J,Cin,3,3),
+    gb (J)), written into out_w / out_b when given (e.g. a trainer's gradient views).  Fixed-order reduction: bit-repeatable.
+    None when unsupported."""
+    J = weight_shape[0]
+    if not p2p_out_bf16_supported(x.shape, J):
+        return None
+    N, H, W, Cin, _ = _p2p_out_args(x, ab, torch.empty(tuple(weight_shape), device='meta'))
+    ldd = _dout_rows(dout, N, H, W, J)
+    gw = out_w if out_w is not None else torch.empty(tuple(weight_shape), device=x.device, dtype=torch.float32)
+    gb = out_b if out_b is not None else torch.empty((J,), device=x.device, dtype=torch.float32)
+    assert tuple(_check(gw).shape) == (J, Cin, 3, 3) and tuple(_check(gb).shape) == (J,)
+    ws = torch.empty((_lib.call('cpr_p2p_out_bf16_wgrad_ws', N, H, W, Cin, J, positive=True),), device=x.device,
+                     dtype=torch.float32)
+    _lib.call('cpr_p2p_out_bf16_wgrad', _ptr(x), _ptr(ab[0]), _ptr(ab[1]), _ptr(dout), ldd, _ptr(gw), _ptr(gb), _ptr(ws), N, H, W,
+              Cin, J, _stream())
+    return gw, gb
+
+
 PROB_TYPES = {'sigmoid': 0, 'softmax': 1, 'normed_sigmoid': 2, 'identity': 3}
 
 

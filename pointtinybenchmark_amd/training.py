@@ -224,7 +224,8 @@ MIXED_BF16 = dict(wgrad=os.environ.get('CPR_MIXED_WGRAD', 'bf16') != 'fp32', dgr
                   dgrad1x1=os.environ.get('CPR_MIXED_DGRAD_1X1', 'bf16') != 'fp32',
                   dz16=os.environ.get('CPR_MIXED_DZ16', '1') != '0',
                   dgrad_s2=os.environ.get('CPR_MIXED_DGRAD_S2', 'bf16') != 'fp32',
-                  mask_mode=os.environ.get('CPR_MIXED_MASK_MODE', '1') != '0', force=False)
+                  mask_mode=os.environ.get('CPR_MIXED_MASK_MODE', '1') != '0',
+                  p2p_out=os.environ.get('CPR_MIXED_P2P_OUT', 'bf16') != 'fp32', force=False)
 
 
 class BackwardEngine:
@@ -1090,7 +1091,6 @@ class P2PHeadRules:
     @staticmethod
     def _forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes):
         assert len(lazy) == 1 and head.num_points == 1, 'single level, one point per cell (the shipped P2P configs)'
-        assert lazy[0][0].dtype == torch.float32, 'the mixed-precision step covers the CPR locator; P2PNet trains in fp32'
         raw, (a, b) = lazy[0]
         x = ops.gn_apply(raw, a, b, relu=False)                   # FPN output, materialised once for the two towers
         cls_tape, reg_tape, save = [], [], {}
@@ -1114,6 +1114,10 @@ class P2PHeadRules:
         dz = None
         for tape, dout, n_out, last in ((s['reg_tape'], dreg.view(B, H, W, 4), 2, head.reg_convs[0]),
                                         (s['cls_tape'], dcls.view(B, H, W, Cp), C, head.cls_convs[0])):
+            if tape[-1]['x'].dtype == torch.bfloat16:
+                d = self._p2p_tower_backward_mixed(tape, dout, n_out)
+                dz = d if dz is None else ops.axpby(dz, d, 1.0, 1.0)
+                continue
             d = self._out_conv_backward(tape[-1], dout, n_out)
             self._done(tape[-1]['conv'].bias)
             for rec in reversed(tape[:-1]):
@@ -1121,6 +1125,43 @@ class P2PHeadRules:
                 self._done(rec['module'].conv.weight)
             dz = d if dz is None else ops.axpby(dz, d, 1.0, 1.0)
         return dz
+
+    def _p2p_tower_backward_mixed(self, tape, dout, n_out):
+        """Mixed precision (the bf16 forward recorded bf16 tower maps): the output conv's gradients straight from the raw bf16 last layer
+        and its GroupNorm affine (csrc/p2p_out_bf16.hip: J <= 8; MIXED_BF16 p2p_out / wgrad / dgrad off, or larger J: the fp32 kernels
+        on the widened map), then the tower as in the CPR head -- bf16 gradient maps between its layers, fp32 at its input."""
+        rec = tape[-1]
+        conv = rec['conv']
+        w, x, ab = conv.weight, rec['x'], rec['in_ab']
+        ok = self._mixed and MIXED_BF16['p2p_out'] and ops.p2p_out_bf16_supported(x.shape, n_out)
+        wgrad16, dgrad16 = ok and MIXED_BF16['wgrad'], ok and MIXED_BF16['dgrad']
+        order = list(reversed(tape[:-1]))
+        to16 = bool(order) and self._mixed and MIXED_BF16['dz16'] and FUSED_CAST and order[0]['raw'].dtype == torch.bfloat16
+        if not (wgrad16 or dgrad16):
+            d = self._out_conv_backward(rec, dout, n_out)
+        else:
+            gw, gb = self._g(w), self._g(conv.bias)
+            if wgrad16:
+                self._param_side(lambda: ops.p2p_out_bf16_wgrad(dout, x, ab, tuple(w.shape), out_w=gw, out_b=gb), dout, x, ab[0], ab[1])
+            else:
+                xw = self._f32(x)
+                Cp = dout.shape[-1]
+                self._param_side(lambda: (gw.copy_(ops.conv2d_wgrad(dout, xw, (Cp,) + tuple(w.shape[1:]), 1, 1, in_ab=ab,
+                                                                    in_relu=True)[:n_out]),
+                                          gb.copy_(ops.relu_bwd_colsum(dout, None, want_g=False)[1][:n_out])), dout, xw)
+            if dgrad16:
+                d = ops.p2p_out_bf16_dgrad(dout, w.detach(), tuple(x.shape), torch.bfloat16 if to16 else torch.float32)
+            else:
+                wpad = torch.zeros((dout.shape[-1],) + tuple(w.shape[1:]), device=w.device, dtype=torch.float32)
+                wpad[:n_out] = w.detach()
+                d = ops.conv2d_dgrad(dout, ops.dgrad_pack(wpad, 1, 1), (x.shape[1], x.shape[2]), 1)
+        self._done(conv.bias)
+        for i, r in enumerate(order):
+            nxt = order[i + 1] if i + 1 < len(order) else None
+            to16 = nxt is not None and self._mixed and MIXED_BF16['dz16'] and FUSED_CAST and nxt['raw'].dtype == torch.bfloat16
+            d = self._gn_conv_backward(r, d, relu=True, need_dx=True, dx_bf16=to16)
+            self._done(r['module'].conv.weight)
+        return d
 
 
 class P2PTrainer(P2PHeadRules, CprTrainer):
