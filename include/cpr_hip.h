@@ -548,6 +548,16 @@ int cpr_grad_sumsq(const float* g, long long n, double* ws_partial, double* out,
  * g = min(1, max_norm/(sqrt(norm2)*grad_scale+1e-6)) * grad_scale * grad + wd*p; buf = first ? g : mu*buf+g; p -= lr*buf */
 int cpr_sgd_step(float* p, const float* grad, float* buf, const double* norm2, long long n, float lr, float mu, float wd,
                  float max_norm, float grad_scale, int first, void* stream);
+/* torch.optim.Adam / AdamW step (amsgrad=False) on one flat fp32 buffer with the clip coefficient of cpr_sgd_step; the P2P
+ * configs train with optimizer = dict(type='Adam', lr=1e-4) + grad_clip max_norm 35
+ * (configs2/TinyPersonV2/p2p/p2p_r50_fpns4_1x_fl_sl1_TinyPersonV2_640.py:86-93, configs2/COCO/p2p/p2p_r50_fpns4_1x_fl_sl1_coco.py:
+ * 141-143, both configs2/DOTA/p2p/ configs: 152-154).  torch's op order, each op rounded:
+ *   g = coef*grad (+ wd*p: Adam);  p *= 1 - lr*wd (AdamW, decoupled=1);  m = lerp(m, g, 1-beta1);  v = v*beta2 + (1-beta2)*g*g;
+ *   p += -step_size * (m / (sqrt(v)/bc2_sqrt + eps))
+ * step_size = lr/(1-beta1^t), bc2_sqrt = sqrt(1-beta2^t): computed by the caller in double, t = 1 at the first step. */
+int cpr_adam_step(float* p, const float* grad, float* exp_avg, float* exp_avg_sq, const double* norm2, long long n, double lr,
+                  double beta1, double beta2, double eps, double wd, float step_size, float bc2_sqrt, float max_norm,
+                  float grad_scale, int decoupled, void* stream);
 
 /* ---- data side feeding the path ----------------------------------------------------------
  * RandomFlip(horizontal) -> Normalize -> Pad(0 after normalisation) -> channels-last float of the mmdet pipeline

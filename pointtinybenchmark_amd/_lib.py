@@ -13,6 +13,7 @@ _p = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
 _l = ctypes.c_longlong
+_d = ctypes.c_double
 
 # name -> argtypes (restype is always int: 0 ok, <0 error).  Mirrors include/cpr_hip.h one to one.
 SIGNATURES = {
@@ -111,6 +112,7 @@ SIGNATURES = {
     'cpr_p2p_loss_bwd': [_p] * 9 + [_i] * 5 + [_f] * 9 + [_p, _i, _i, _p],
     'cpr_grad_sumsq': [_p, _l, _p, _p, _i, _p],
     'cpr_sgd_step': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p],
+    'cpr_adam_step': [_p, _p, _p, _p, _p, _l, _d, _d, _d, _d, _d, _f, _f, _f, _f, _i, _p],
 }
 
 # measurement build only (-DCPR_BENCH_HOOKS -> libcprhip_bench.so, tools/*.py): NOT part of the product library

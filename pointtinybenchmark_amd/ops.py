@@ -1511,3 +1511,22 @@ def grad_sumsq(g, out, ws, accumulate):
 def sgd_step(p, grad, buf, norm2, lr, momentum, weight_decay, max_norm, grad_scale, first):
     _lib.call('cpr_sgd_step', _ptr(p), _ptr(grad), _ptr(buf), _ptr(norm2), p.numel(), float(lr), float(momentum),
               float(weight_decay), float(max_norm), float(grad_scale), int(first), _stream())
+
+
+def adam_step(p, grad, exp_avg, exp_avg_sq, norm2, lr, betas, eps, weight_decay, step, max_norm, grad_scale,
+              decoupled=False):
+    """torch.optim.Adam (AdamW: decoupled=True) step number ``step`` (1 at the first) on flat fp32 buffers, clipped with
+    the coefficient of ``sgd_step`` (norm2: the device sum of squares of grad_sumsq; max_norm <= 0: no clip).  The bias
+    corrections are formed here in double, as torch forms them in Python."""
+    beta1, beta2 = float(betas[0]), float(betas[1])
+    if step < 1:
+        raise ValueError('adam_step: step counts from 1, got %r' % (step,))
+    for t in (p, grad, exp_avg, exp_avg_sq):
+        _check(t)
+        if t.numel() != p.numel():
+            raise _lib.CprHipError('adam_step: p, grad, exp_avg and exp_avg_sq must have one size')
+    step_size = float(lr) / (1 - beta1 ** step)
+    bc2_sqrt = (1 - beta2 ** step) ** 0.5
+    _lib.call('cpr_adam_step', _ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(norm2), p.numel(), float(lr),
+              beta1, beta2, float(eps), float(weight_decay), step_size, bc2_sqrt, float(max_norm), float(grad_scale),
+              int(bool(decoupled)), _stream())

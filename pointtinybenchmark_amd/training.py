@@ -1,5 +1,5 @@
 """The CPR training step beyond forward+loss: explicit backward over the recorded forward, a
-DDP-style bucketed gradient all-reduce and the SGD update -- all on HIP kernels, no torch autograd.
+DDP-style bucketed gradient all-reduce and the SGD / Adam update -- all on HIP kernels, no torch autograd.
 
 What it replaces in the reference: ``loss.backward()`` (torch autograd over mmcv ConvModule / nn.GroupNorm /
 F.grid_sample / the frozen-statistics BatchNorm of ResNet), MMDistributedDataParallel's gradient reducer
@@ -178,6 +178,52 @@ def layout_buckets(sizes, max_elems, min_elems, tail_elems):
     if n > bounds[-1]:
         bounds.append(n)
     return bounds
+
+
+# torch.optim's hyperparameters per optimizer type (torch's defaults), as the native step restates them
+_OPT_DEFAULTS = {
+    'SGD': dict(lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False),
+    'Adam': dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False),
+    'AdamW': dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False),
+}
+_OPT_HYPER = {k: [h for h in v if h != 'lr'] for k, v in _OPT_DEFAULTS.items()}
+_OPT_IGNORED = ('foreach', 'fused', 'capturable', 'differentiable')     # torch implementation choices: same update
+
+
+def parse_optimizer(cfg):
+    """An mmcv-style optimizer dict (``dict(type='Adam', lr=1e-4)``) -> the full set of torch.optim hyperparameters with
+    torch's defaults.  Refuses what the native step does not restate: other types, paramwise_cfg, amsgrad, SGD nesterov /
+    dampening, maximize."""
+    cfg = dict(cfg)
+    t = cfg.pop('type', None)
+    if t not in _OPT_DEFAULTS:
+        raise ValueError('optimizer type %r is not built (SGD, Adam, AdamW)' % (t,))
+    if 'paramwise_cfg' in cfg:
+        raise ValueError('optimizer paramwise_cfg is not built: the native trainer has one parameter group')
+    if cfg.pop('maximize', False):
+        raise ValueError('optimizer maximize=True is not built')
+    for k in _OPT_IGNORED:
+        cfg.pop(k, None)
+    unknown = sorted(set(cfg) - set(_OPT_DEFAULTS[t]))
+    if unknown:
+        raise ValueError('%s optimizer keys not built: %s' % (t, unknown))
+    o = dict(_OPT_DEFAULTS[t], **cfg)
+    for k in ('lr', 'momentum', 'dampening', 'weight_decay', 'eps'):
+        if k in o:
+            o[k] = float(o[k])
+    if t == 'SGD':
+        if o['nesterov']:
+            raise ValueError('SGD nesterov=True is not built')
+        if o['dampening'] != 0:
+            raise ValueError('SGD dampening != 0 is not built')
+    else:
+        if o['amsgrad']:
+            raise ValueError('%s amsgrad=True is not built' % t)
+        o['betas'] = tuple(float(b) for b in o['betas'])
+        if len(o['betas']) != 2 or not all(0.0 <= b < 1.0 for b in o['betas']) or o['eps'] <= 0:
+            raise ValueError('%s: betas in [0, 1) and eps > 0 expected, got %r, %r' % (t, o['betas'], o['eps']))
+    o['type'] = t
+    return o
 
 
 class StepLrSchedule:
@@ -891,14 +937,23 @@ class BackwardEngine:
 class CprTrainer(BackwardEngine):
     def __init__(self, model, lr=0.02, momentum=0.9, weight_decay=1e-4, max_norm=35.0, bucket_mb=25.0, group=None,
                  two_streams=True, force_collectives=False, schedule=None, reducer='all_reduce', reducer_timing=False,
-                 min_bucket_mb=4.0, tail_bucket_mb=1.0):
+                 min_bucket_mb=4.0, tail_bucket_mb=1.0, optimizer=None):
         """schedule: a StepLrSchedule (or any object with ``lr(iteration)``); ``lr`` is then only the fallback of
         ``step(lr=...)``.  Constructing the trainer re-homes every trainable parameter: ``p.data`` becomes a view of ONE
         flat buffer (``flat_p``) and ``p.grad`` a view of ``flat_g``; do not re-bind them afterwards (``model.to()``,
-        ``.float()``, ``p.data = ...``) -- ``step`` checks and refuses.  ``state_dict()`` below returns detached clones."""
+        ``.float()``, ``p.data = ...``) -- ``step`` checks and refuses.  ``state_dict()`` below returns detached clones.
+        optimizer: an mmcv-style dict (``type`` 'SGD', 'Adam' or 'AdamW' + torch.optim's keyword arguments, torch's
+        defaults) in place of the positional SGD arguments ``lr`` / ``momentum`` / ``weight_decay``; None: SGD with those."""
         BackwardEngine.__init__(self, model, two_streams)
         self.schedule = schedule
-        self.lr, self.momentum, self.weight_decay, self.max_norm = lr, momentum, weight_decay, max_norm
+        if optimizer is None:
+            optimizer = dict(type='SGD', lr=lr, momentum=momentum, weight_decay=weight_decay)
+        elif (lr, momentum, weight_decay) != (0.02, 0.9, 1e-4):
+            raise ValueError('CprTrainer: pass the optimizer either as optimizer=dict(...) or as lr / momentum / '
+                             'weight_decay, not both')
+        self.optimizer = parse_optimizer(optimizer)
+        o = self.optimizer
+        self.lr, self.momentum, self.weight_decay, self.max_norm = o['lr'], o.get('momentum'), o['weight_decay'], max_norm
         order = self._backward_order()
         seen = {id(p) for p in order}
         missing = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in seen]
@@ -908,7 +963,12 @@ class CprTrainer(BackwardEngine):
         n = sum(p.numel() for p in order)
         self.flat_p = torch.empty((n,), device=dev, dtype=torch.float32)
         self.flat_g = torch.zeros((n,), device=dev, dtype=torch.float32)
-        self.flat_m = torch.zeros((n,), device=dev, dtype=torch.float32)
+        # optimizer state in the flat layout: SGD's momentum buffer, or Adam's two moments
+        self.flat_m = torch.zeros((n,), device=dev, dtype=torch.float32) if o['type'] == 'SGD' else None
+        self.exp_avg = self.exp_avg_sq = None
+        if o['type'] != 'SGD':
+            self.exp_avg = torch.zeros((n,), device=dev, dtype=torch.float32)
+            self.exp_avg_sq = torch.zeros((n,), device=dev, dtype=torch.float32)
         self._launch = None      # stream the gradient collectives are issued from (two-stream backward on a device)
         self.offset, off = {}, 0
         for p in order:
@@ -939,7 +999,8 @@ class CprTrainer(BackwardEngine):
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(self.group) == 1:
             return
         dist.broadcast(self.flat_p, src=src, group=self.group)
-        dist.broadcast(self.flat_m, src=src, group=self.group)
+        for t in self._state_buffers():
+            dist.broadcast(t, src=src, group=self.group)
         flat_ids = set(self.offset)
         for t in list(self.model.parameters()) + list(self.model.buffers()):
             if id(t) not in flat_ids and t.numel() > 0:
@@ -957,6 +1018,138 @@ class CprTrainer(BackwardEngine):
     def state_dict(self):
         """Detached clones of the model's tensors (saving the views would serialise the whole flat storage per key)."""
         return {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+
+    def _state_buffers(self):
+        return [t for t in (self.flat_m, self.exp_avg, self.exp_avg_sq) if t is not None]
+
+    @classmethod
+    def from_config(cls, model, cfg, iters_per_epoch, **trainer_kw):
+        """The trainer an mmdet config asks for: ``cfg.optimizer`` (mmcv's DefaultOptimizerConstructor without
+        paramwise_cfg), ``cfg.optimizer_config`` (mmcv's OptimizerHook: grad_clip -> ``max_norm``, None = no clip) and
+        ``cfg.lr_config`` (``StepLrSchedule``).  cfg: the project's ``Config`` or a plain dict.  What the native step does
+        not restate is refused, not approximated."""
+        clash = sorted({'optimizer', 'max_norm', 'schedule', 'lr', 'momentum', 'weight_decay'} & set(trainer_kw))
+        if clash:
+            raise ValueError('from_config: %s come from the config' % clash)
+        optimizer = cfg.get('optimizer')
+        if optimizer is None:
+            raise ValueError('from_config: the config has no optimizer')
+        oc = cfg.get('optimizer_config')
+        if oc is None:
+            raise ValueError('from_config: the config has no optimizer_config (mmcv would register no OptimizerHook)')
+        oc = dict(oc)
+        hook = oc.pop('type', 'OptimizerHook')
+        if hook == 'Fp16OptimizerHook':
+            raise ValueError("from_config: Fp16OptimizerHook is not built; mixed precision here is "
+                             "model.set_compute_dtype('bf16') (weights, gradients and optimizer state stay fp32)")
+        if hook != 'OptimizerHook':
+            raise ValueError('from_config: optimizer_config type %r is not built (only the plain OptimizerHook)' % (hook,))
+        grad_clip = oc.pop('grad_clip', None)
+        if oc.pop('detect_anomalous_params', False) or oc:
+            raise ValueError('from_config: optimizer_config keys not built: %s' % sorted(oc))
+        max_norm = None
+        if grad_clip is not None:
+            grad_clip = dict(grad_clip)
+            max_norm = float(grad_clip.pop('max_norm'))
+            norm_type = grad_clip.pop('norm_type', 2)
+            if float(norm_type) != 2.0:
+                raise ValueError('from_config: grad_clip norm_type %r is not built (only the L2 norm)' % (norm_type,))
+            if grad_clip:
+                raise ValueError('from_config: grad_clip keys not built: %s' % sorted(grad_clip))
+        lr_config = cfg.get('lr_config')
+        schedule = None if lr_config is None else StepLrSchedule.from_config(parse_optimizer(optimizer), lr_config,
+                                                                              iters_per_epoch)
+        return cls(model, max_norm=max_norm, schedule=schedule, optimizer=optimizer, **trainer_kw)
+
+    # ------------------------------------------------------------------ optimizer state in torch.optim's format
+    def _torch_param_group(self):
+        """torch's own param_groups entry for this optimizer and these hyperparameters (every key torch writes)."""
+        o = self.optimizer
+        kw = {k: o[k] for k in _OPT_HYPER[o['type']]}
+        return getattr(torch.optim, o['type'])([torch.zeros(1, requires_grad=True)], lr=o['lr'], **kw) \
+            .state_dict()['param_groups'][0]
+
+    def _param_positions(self, params):
+        params = list(self.model.parameters()) if params is None else list(params)
+        pos = {id(p): i for i, p in enumerate(params)}
+        missing = [p for p in self.params if id(p) not in pos]
+        if missing:
+            raise ValueError('params misses %d trainable parameters of the trainer' % len(missing))
+        return params, {pos[id(p)]: p for p in self.params}
+
+    def optimizer_state_dict(self, params=None):
+        """The optimizer state as ``torch.optim.SGD / Adam / AdamW.state_dict()`` would hold it for an optimizer over
+        ``params`` (default ``list(model.parameters())``: mmcv's DefaultOptimizerConstructor order; frozen parameters
+        have no state).  One param group with torch's keys, ``lr`` the last lr used, plus ``iteration`` = ``steps``
+        (torch and mmcv keep and ignore an unknown group key)."""
+        params, trained = self._param_positions(params)
+        o = self.optimizer
+        state = {}
+        if self.steps > 0 and (o['type'] != 'SGD' or self.momentum):
+            for i in sorted(trained):
+                p = trained[i]
+                lo, hi = self.offset[id(p)]
+                if o['type'] == 'SGD':
+                    state[i] = {'momentum_buffer': self.flat_m[lo:hi].view(p.shape).clone()}
+                else:
+                    state[i] = {'step': torch.tensor(float(self.steps), dtype=torch.float32),
+                                'exp_avg': self.exp_avg[lo:hi].view(p.shape).clone(),
+                                'exp_avg_sq': self.exp_avg_sq[lo:hi].view(p.shape).clone()}
+        group = self._torch_param_group()
+        group.update(lr=getattr(self, 'last_lr', self.lr), params=list(range(len(params))), iteration=self.steps)
+        return {'state': state, 'param_groups': [group]}
+
+    def load_optimizer_state_dict(self, sd, params=None):
+        """Load a torch.optim state dict (``optimizer_state_dict``'s, torch's own, or mmcv's checkpoint ``optimizer``
+        entry) over ``params`` into the flat state buffers, in place, and restore ``steps`` (the schedule's iteration;
+        Adam's bias-correction step).  Refuses another optimizer type, other hyperparameters (lr excepted: the schedule
+        owns it) and mismatched parameters or shapes.  A torch SGD state dict carries no iteration count: ``steps``
+        becomes at least 1 when it holds momentum (set ``steps`` to the runner's iteration for the schedule)."""
+        params, trained = self._param_positions(params)
+        o = self.optimizer
+        groups = sd['param_groups']
+        if len(groups) != 1:
+            raise ValueError('%d parameter groups: one expected (paramwise_cfg is not built)' % len(groups))
+        g = groups[0]
+        if sorted(g['params']) != list(range(len(params))):
+            raise ValueError('the parameter group holds %d parameters, params has %d' % (len(g['params']), len(params)))
+        saved = 'SGD' if 'betas' not in g else ('AdamW' if g.get('decoupled_weight_decay', o['type'] == 'AdamW') else 'Adam')
+        if saved != o['type']:
+            raise ValueError('a %s state dict cannot be loaded into a %s trainer' % (saved, o['type']))
+        for k in _OPT_HYPER[o['type']]:
+            a, b = g.get(k), o[k]
+            if (tuple(map(float, a)) != tuple(b)) if k == 'betas' else a != b:
+                raise ValueError('hyperparameter %s differs: state dict %r, trainer %r' % (k, a, b))
+        if g.get('maximize', False):
+            raise ValueError('maximize=True is not built')
+        state = {int(k): v for k, v in sd['state'].items()}
+        names = ['momentum_buffer'] if o['type'] == 'SGD' else ['exp_avg', 'exp_avg_sq']
+        if state and set(state) != set(trained):
+            raise ValueError('state for parameters %s, the trainer trains %s' % (sorted(state)[:8], sorted(trained)[:8]))
+        steps = set()
+        for i, st in state.items():
+            for name in names:
+                if name not in st or st[name] is None or tuple(st[name].shape) != tuple(trained[i].shape):
+                    raise ValueError('parameter %d: %s missing or of another shape than %s' % (i, name, tuple(trained[i].shape)))
+            if 'step' in st:
+                steps.add(int(float(st['step'])))
+        if o['type'] != 'SGD':
+            if len(steps) > 1:
+                raise ValueError('parameters at different Adam steps %s: the flat state has one' % sorted(steps))
+            n = steps.pop() if steps else 0
+            if g.get('iteration', n) != n:
+                raise ValueError('iteration %r differs from the Adam step %d' % (g['iteration'], n))
+        else:
+            n = g.get('iteration', max(self.steps, 1) if state else 0)
+        bufs = self._state_buffers()
+        with torch.no_grad():
+            for b in bufs:
+                b.zero_()
+            for i, st in state.items():
+                lo, hi = self.offset[id(trained[i])]
+                for name, b in zip(names, bufs):
+                    b[lo:hi].copy_(st[name].reshape(-1))
+        self.steps = int(n)
 
     # ------------------------------------------------------------------ parameter order = gradient completion order
     def _backward_order(self):
@@ -1037,8 +1230,8 @@ class CprTrainer(BackwardEngine):
 
     # ------------------------------------------------------------------ optimizer
     def step(self, lr=None):
-        """Wait for the gradient buckets, clip by the global norm, SGD-momentum update of every trainable parameter.
-        lr: explicit override; else the schedule's value for this iteration; else the constructor's constant."""
+        """Wait for the gradient buckets, clip by the global norm, SGD-momentum / Adam / AdamW update of every trainable
+        parameter.  lr: explicit override; else the schedule's value for this iteration; else the constructor's constant."""
         self.check_bindings()
         if lr is None and self.schedule is not None:
             lr = self.schedule.lr(self.steps)
@@ -1046,8 +1239,14 @@ class CprTrainer(BackwardEngine):
         grad_scale = self.buckets.finish()
         if self.max_norm and self.max_norm > 0:
             ops.grad_sumsq(self.flat_g, self.norm2, self._ws, accumulate=False)
-        ops.sgd_step(self.flat_p, self.flat_g, self.flat_m, self.norm2, self.lr if lr is None else lr, self.momentum,
-                     self.weight_decay, self.max_norm or 0.0, grad_scale, first=self.steps == 0)
+        o = self.optimizer
+        if o['type'] == 'SGD':
+            ops.sgd_step(self.flat_p, self.flat_g, self.flat_m, self.norm2, self.last_lr, self.momentum,
+                         self.weight_decay, self.max_norm or 0.0, grad_scale, first=self.steps == 0)
+        else:
+            ops.adam_step(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm2, self.last_lr, o['betas'],
+                          o['eps'], o['weight_decay'], self.steps + 1, self.max_norm or 0.0, grad_scale,
+                          decoupled=o['type'] == 'AdamW')
         self.steps += 1
         bump_weight_epoch()
         # the folds / bf16 packs the last step registered are recomputed in place now, in two launches, instead of lapsing (round 6)
