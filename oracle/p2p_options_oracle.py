@@ -107,63 +107,93 @@ def get_pred_points(cls_outs, pts_outs, strides, point_anchor, pts_gamma, num_cl
     return torch.cat(preds, 1), torch.cat(clss, 1)
 
 
+P2P_REG_TYPES = ('SmoothL1Loss', 'MSELoss', 'L1Loss')                             # reg_mode 0 / 1 / 2 (ops.P2P_REG_MODES)
+
+
+def p2p_loss_from_assignment(cls, pred, gt_inds, gt_pts, gt_labels, gt_start, alpha, gamma, beta, pos_w, neg_w, reg_norm, w_cls,
+                             w_reg, cls_mode=0, reg_mode=0):
+    """The loss half of P2PHead.loss (:196-248) on a given assignment, with the inputs of ops.p2p_loss: cls (B, M, C) logits, pred (B, M, 3)
+    = (x, y, stride), gt_inds (B, M) (j + 1 = gt j of the image, 0 = background, < 0 = a cell outside the padded image), gt_pts (G, 2) and
+    gt_labels (G,) of all images, image b's gts starting at gt_start[b].  Targets as sample_result_to_target (:308-328) makes them, cells
+    gt_inds < 0 un-mapped with fill 0 (:300-305: label 0, label weight 0, no regression target).  Avg factors: the batch's positives for
+    FocalLoss and the regression, all B * M proposals (invalid cells included) for both CrossEntropyLoss modes (:199-200, 220-224).
+    Evaluated in the dtype of cls / pred; differentiable.  -> (loss_cls (B,), loss_pts (B,))."""
+    B, M, C = cls.shape
+    nfg = C - 1 if cls_mode == 2 else C                       # foreground classes; the background label
+    gt_inds = torch.as_tensor(gt_inds).long()
+    gt_pts, gt_labels = torch.as_tensor(gt_pts), torch.as_tensor(gt_labels).long()
+    start = [int(v) for v in torch.as_tensor(gt_start).reshape(-1)]
+    pos_all, valid_all = gt_inds > 0, gt_inds >= 0
+    num_pos = int(pos_all.sum())
+    num_total = B * M
+    pred_xy, stride = pred[..., :2], pred[..., 2:]
+    loss_c, loss_p = [], []
+    for b in range(B):
+        pos, valid = pos_all[b], valid_all[b]
+        g = start[b] + gt_inds[b][pos] - 1
+        lab = torch.full((M,), nfg, dtype=torch.long)
+        lab[pos] = gt_labels[g]
+        lab[~valid] = 0
+        lw = torch.full((M,), 1.0 if neg_w <= 0 else neg_w, dtype=cls.dtype)
+        lw[pos] = pos_w
+        lw[~valid] = 0.0
+        tgt = torch.zeros((M, 2), dtype=pred.dtype)
+        tgt[pos] = gt_pts[g].to(pred.dtype)
+        pw = torch.zeros((M, 2), dtype=pred.dtype)
+        pw[pos] = 1.0
+        if cls_mode == 0:
+            target = F.one_hot(lab, num_classes=nfg + 1)[:, :nfg].type_as(cls)
+            ps = cls[b].sigmoid()
+            pt = (1 - ps) * target + ps * (1 - target)
+            fw = (alpha * target + (1 - alpha) * (1 - target)) * pt.pow(gamma)
+            l = F.binary_cross_entropy_with_logits(cls[b], target, reduction='none') * fw * lw.view(-1, 1)
+            loss_c.append(w_cls * l.sum() / num_pos)
+        elif cls_mode == 1:
+            target = F.one_hot(lab, num_classes=nfg + 1)[:, :nfg].type_as(cls)          # _expand_onehot_labels :43-56
+            l = F.binary_cross_entropy_with_logits(cls[b], target, reduction='none') * lw.view(-1, 1)
+            loss_c.append(w_cls * l.sum() / num_total)
+        else:
+            l = F.cross_entropy(cls[b], lab, reduction='none') * lw
+            loss_c.append(w_cls * l.sum() / num_total)
+        e = pred_xy[b] / stride[b] / reg_norm - tgt / stride[b] / reg_norm
+        if reg_mode == 0:
+            d = e.abs()
+            r = torch.where(d < beta, 0.5 * d * d / beta, d - 0.5 * beta)
+        elif reg_mode == 1:
+            r = e * e
+        else:
+            r = e.abs()
+        loss_p.append(w_reg * (r * pw).sum() / num_pos)
+    return torch.stack(loss_c), torch.stack(loss_p)
+
+
 def p2p_loss(cls_outs, pts_outs, gt_bboxes, gt_labels, img_shape, strides, num_classes, loss_cls, loss_reg, assigner,
              pts_gamma=1.0, reg_norm=1.0, point_anchor=((0., 0.),), pos_weight=1.0, neg_weight=1.0):
     """P2PHead.loss (:172-248) for the loss / assigner options: loss_cls FocalLoss | CrossEntropyLoss(use_sigmoid) | CrossEntropyLoss
     (cross_entropy_loss.py:9-99; avg_factor = all proposals for CrossEntropyLoss, positives for FocalLoss: :220-224), loss_reg
-    SmoothL1Loss | MSELoss | L1Loss (avg_factor = positives).  Differentiable.  -> ({'loss_cls': [...], 'loss_pts': [...]}, gt_inds list)."""
+    SmoothL1Loss | MSELoss | L1Loss (avg_factor = positives): the assignment here, the losses in p2p_loss_from_assignment.
+    Differentiable.  -> ({'loss_cls': [...], 'loss_pts': [...]}, gt_inds list)."""
     use_sigmoid = loss_cls.get('use_sigmoid', False)
     nco = num_classes if use_sigmoid else num_classes + 1
     pred3, cls = get_pred_points(cls_outs, pts_outs, strides, point_anchor, pts_gamma, nco)
-    pred, stride = pred3[..., :2], pred3[..., 2:]
-    B, M = cls.shape[:2]
+    B = cls.shape[0]
     cc = assigner['cls_costs'] if isinstance(assigner['cls_costs'], (list, tuple)) else [assigner['cls_costs']]
     rc = assigner['reg_costs'] if isinstance(assigner['reg_costs'], (list, tuple)) else [assigner['reg_costs']]
-    labels, lw, tgt, pw, inds_all = [], [], [], [], []
+    ctrs, inds_all = [], []
     for b in range(B):
         ctr = (gt_bboxes[b][:, :2] + gt_bboxes[b][:, 2:]) / 2
-        inds, _, _ = hungarian_assign_v2(cc, rc, assigner.get('topk_k', 1), pred[b].detach(), cls[b].detach(), ctr, gt_labels[b], img_shape)
-        pos = inds > 0
-        lab = torch.full((M,), num_classes, dtype=torch.long)
-        lab[pos] = gt_labels[b][inds[pos] - 1]
-        w = torch.full((M,), 1.0 if neg_weight <= 0 else neg_weight)
-        w[pos] = pos_weight
-        t = torch.zeros((M, 2))
-        t[pos] = ctr[inds[pos] - 1]
-        ww = torch.zeros((M, 2))
-        ww[pos] = 1.0
-        labels.append(lab), lw.append(w), tgt.append(t), pw.append(ww), inds_all.append(inds)
-    num_pos = sum(int((w[:, 0] > 0).sum()) for w in pw)
-    num_total = B * M
-    w_cls, w_reg = loss_cls.get('loss_weight', 1.0), loss_reg.get('loss_weight', 1.0)
-    loss_c, loss_p = [], []
-    for b in range(B):
-        if loss_cls['type'] == 'FocalLoss':
-            alpha, gamma = loss_cls.get('alpha', 0.25), loss_cls.get('gamma', 2.0)
-            target = F.one_hot(labels[b], num_classes=num_classes + 1)[:, :num_classes].type_as(cls)
-            ps = cls[b].sigmoid()
-            pt = (1 - ps) * target + ps * (1 - target)
-            fw = (alpha * target + (1 - alpha) * (1 - target)) * pt.pow(gamma)
-            l = F.binary_cross_entropy_with_logits(cls[b], target, reduction='none') * fw * lw[b].view(-1, 1)
-            loss_c.append(w_cls * l.sum() / num_pos)
-        elif use_sigmoid:
-            target = F.one_hot(labels[b], num_classes=num_classes + 1)[:, :num_classes].type_as(cls)        # _expand_onehot_labels :43-56
-            l = F.binary_cross_entropy_with_logits(cls[b], target, reduction='none') * lw[b].view(-1, 1)
-            loss_c.append(w_cls * l.sum() / num_total)
-        else:
-            l = F.cross_entropy(cls[b], labels[b], reduction='none') * lw[b]
-            loss_c.append(w_cls * l.sum() / num_total)
-        e = pred[b] / stride[b] / reg_norm - tgt[b] / stride[b] / reg_norm
-        if loss_reg['type'] == 'SmoothL1Loss':
-            beta = loss_reg.get('beta', 1.0)
-            d = e.abs()
-            r = torch.where(d < beta, 0.5 * d * d / beta, d - 0.5 * beta)
-        elif loss_reg['type'] == 'MSELoss':
-            r = e * e
-        else:
-            r = e.abs()
-        loss_p.append(w_reg * (r * pw[b]).sum() / num_pos)
-    return {'loss_cls': loss_c, 'loss_pts': loss_p}, inds_all
+        inds, _, _ = hungarian_assign_v2(cc, rc, assigner.get('topk_k', 1), pred3[b, :, :2].detach(), cls[b].detach(), ctr, gt_labels[b],
+                                         img_shape)
+        ctrs.append(ctr), inds_all.append(inds)
+    counts = [len(c) for c in ctrs]
+    start = torch.tensor([sum(counts[:b]) for b in range(B)], dtype=torch.int32)
+    cls_mode = 0 if loss_cls['type'] == 'FocalLoss' else 1 if use_sigmoid else 2
+    reg_mode = P2P_REG_TYPES.index(loss_reg['type'])
+    lc, lp = p2p_loss_from_assignment(cls, pred3, torch.stack(inds_all), torch.cat(ctrs), torch.cat(list(gt_labels)), start,
+                                      loss_cls.get('alpha', 0.25), loss_cls.get('gamma', 2.0), loss_reg.get('beta', 1.0), pos_weight,
+                                      neg_weight, reg_norm, loss_cls.get('loss_weight', 1.0), loss_reg.get('loss_weight', 1.0),
+                                      cls_mode, reg_mode)
+    return {'loss_cls': list(lc.unbind(0)), 'loss_pts': list(lp.unbind(0))}, inds_all
 
 
 def p2p_get_bboxes_single(cls, pred_pts, img_shape, num_levels, use_sigmoid, num_cls_out, nms_pre=2000, score_thr=0.05, iou_thr=0.2,

@@ -1334,9 +1334,11 @@ __global__ void p2p_loss_bwd_kernel(const float* __restrict__ logits, const floa
                     const float pt = (1.f - p) * t + p * (1.f - t);
                     const float at = alpha * t + (1.f - alpha) * (1.f - t);
                     const float ptg = (gamma == 2.f) ? pt * pt : powf(pt, gamma);
-                    const float ptg1 = (gamma == 2.f) ? pt : powf(pt, gamma - 1.f);
                     const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-                    d = at * (ptg * (p - t) + bce * gamma * ptg1 * (1.f - 2.f * t) * p * (1.f - p)) * w * w_cls * inv_c;
+                    // d/dx at*pt^g*bce = at*(pt^g*(p-t) + g*bce*pt^(g-1)*(1-2t)*p(1-p)); p(1-p) == pt(1-pt) for a binary t, so
+                    // pt^g factors out and no negative power of pt is formed (powf(0, g-1) = inf for g < 1, and inf * 0 = NaN
+                    // where fp32 p saturates to 1)
+                    d = at * ptg * ((p - t) + gamma * bce * (1.f - pt) * (1.f - 2.f * t)) * w * w_cls * inv_c;
                 }
             }
         }

@@ -1494,10 +1494,13 @@ def p2p_loss_bwd(logits, pred, gt_inds, gt_pts, gt_labels, gt_start, alpha, gamm
     upstream (B,2): gradient of the caller's total wrt each image's (loss_cls, loss_pts); None = unit weights."""
     B, M, C = _check(logits).shape
     assert upstream is None or (tuple(upstream.shape) == (B, 2) and upstream.dtype == torch.float32 and upstream.is_contiguous())
+    _check(pred), _check(gt_inds, torch.int64), _check(gt_pts), _check(gt_labels, torch.int32), _check(gt_start, torch.int32)
+    assert tuple(pred.shape) == (B, M, 3) and tuple(gt_inds.shape) == (B, M) and gt_start.numel() >= B, \
+        (tuple(pred.shape), tuple(gt_inds.shape), gt_start.numel())
     npos = (gt_inds > 0).sum().to(torch.float32).reshape(1)          # device scalar, no host sync
     dcls = torch.empty((B, M, Cp), device=logits.device, dtype=torch.float32)
     dreg = torch.empty((B, M, Rp), device=logits.device, dtype=torch.float32)
-    _lib.call('cpr_p2p_loss_bwd', _ptr(logits), _ptr(_check(pred)), _ptr(gt_inds), _ptr(gt_pts), _ptr(gt_labels),
+    _lib.call('cpr_p2p_loss_bwd', _ptr(logits), _ptr(pred), _ptr(gt_inds), _ptr(gt_pts), _ptr(gt_labels),
               _ptr(gt_start), _ptr(npos), _ptr(dcls), _ptr(dreg), B, M, C, Cp, Rp, float(alpha), float(gamma), float(beta),
               float(pos_w), float(neg_w), float(reg_norm), float(w_cls), float(w_reg), float(gamma_p), _ptr(upstream),
               int(cls_mode), int(reg_mode), _stream())
