@@ -542,6 +542,18 @@ int cpr_p2p_loss_bwd(const float* logits, const float* pred, const long long* gt
                      const int* gt_labels, const int* gt_start, const float* npos, float* dcls, float* dreg, int B, int M,
                      int C, int Cp, int Rp, float alpha, float gamma, float beta, float pos_w, float neg_w, float reg_norm,
                      float w_cls, float w_reg, float gamma_p, const float* upstream, int cls_mode, int reg_mode, void* stream);
+/* the same gradient for L FPN levels and P points per cell (L <= 8, P >= 1), written straight into every level's output-conv
+ * gradient maps: the proposal rows m in [0, M) are the levels' concatenation, level l owning [level_off[l], level_off[l] +
+ * level_hw[l] * P) cell-major (the table must tile [0, M) exactly).  Class c of point p goes to channel p*C + c of level_dcls[l]
+ * (B, H_l, W_l, level_cp[l] >= P*C), coordinate k to channel p*2 + k of level_dreg[l] (B, H_l, W_l, level_rp[l] >= 2P); padding
+ * channels are written as zero.  The tables are HOST arrays of L entries.  The CrossEntropyLoss average runs over all B*M rows.
+ * L = 1, P = 1 gives cpr_p2p_loss_bwd's output bit for bit. */
+int cpr_p2p_loss_bwd_levels(const float* logits, const float* pred, const long long* gt_inds, const float* gt_pts,
+                            const int* gt_labels, const int* gt_start, const float* npos, int B, int M, int C, int P, int L,
+                            const int* level_hw, const int* level_off, const int* level_cp, const int* level_rp,
+                            float* const* level_dcls, float* const* level_dreg, float alpha, float gamma, float beta, float pos_w,
+                            float neg_w, float reg_norm, float w_cls, float w_reg, float gamma_p, const float* upstream,
+                            int cls_mode, int reg_mode, void* stream);
 /* sum of squares of a flat gradient buffer into out[0] (double; accumulate across buffers); ws_partial 1024 doubles */
 int cpr_grad_sumsq(const float* g, long long n, double* ws_partial, double* out, int accumulate, void* stream);
 /* torch.optim.SGD step (momentum, weight decay) with clip_grad_norm_'s coefficient taken from norm2 on the device:

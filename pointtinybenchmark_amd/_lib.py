@@ -110,6 +110,7 @@ SIGNATURES = {
     'cpr_p2p_out_bf16_wgrad_ws': [_i] * 5,
     'cpr_p2p_out_bf16_wgrad': [_p] * 4 + [_i] + [_p] * 3 + [_i] * 5 + [_p],
     'cpr_p2p_loss_bwd': [_p] * 9 + [_i] * 5 + [_f] * 9 + [_p, _i, _i, _p],
+    'cpr_p2p_loss_bwd_levels': [_p] * 7 + [_i] * 5 + [_p] * 6 + [_f] * 9 + [_p, _i, _i, _p],
     'cpr_grad_sumsq': [_p, _l, _p, _p, _i, _p],
     'cpr_sgd_step': [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p],
     'cpr_adam_step': [_p, _p, _p, _p, _p, _l, _d, _d, _d, _d, _d, _f, _f, _f, _f, _i, _p],

@@ -9,8 +9,8 @@ chain have none: a raw map travels with a pending affine):
 
     image -> stem + frozen stages (no graph)
           -> _StageFn (layer2) -> _StageFn (layer3) -> _StageFn (layer4)          d(stage output) between them
-          -> _LateralsFn: lateral 1x1 convs + GN + top-down adds -> finest lateral sum        d(lateral sum)
-          -> _HeadLossFn: FPN 3x3 output conv + head towers + projection + point stage + losses -> the loss vector
+          -> _LateralsFn: lateral 1x1 convs + GN + top-down adds -> the lateral sums the output convs read   d(lateral sums)
+          -> _HeadLossFn: FPN 3x3 output conv(s) + head towers + projection + point stage + losses -> the loss vector
 
 Every Function takes its trainable parameters as explicit inputs, so they sit in the autograd graph as leaves: gradient
 accumulators fire per Function -- the head's 9.4 MB of gradients (63 % of the backward's time) are final and on the wire while
@@ -20,7 +20,8 @@ pinned to ``loss.backward()`` through the reference's own modules by tests/golde
 
 Both compute modes (round 5: the bf16 mode = mixed precision, the reference analogue being mmcv's ``Fp16OptimizerHook`` around an
 unmodified ``loss.backward()``, T/mmdet/apis/train.py:116-119 -- see ``Bridge.carrier`` for how bf16 maps cross the Function
-boundaries), every CPRHead option set that runs forward (``CPRHead.train_step_supported``), one FPN output level, a frozen stem.  Anything else keeps the forward-only path and warns once."""
+boundaries), every CPRHead option set that runs forward (``CPRHead.train_step_supported``) with one FPN output level, P2PHead with any number of
+FPN output levels and points per cell, a frozen stem.  Anything else keeps the forward-only path and warns once."""
 import os
 import warnings
 
@@ -57,7 +58,8 @@ class Bridge:
         self._maps = {}         # bf16 compute mode: data_ptr of an fp32 carrier -> the bf16 map it stands for (see carrier())
         self.stage_params = [[p for p in getattr(bb, name).parameters() if p.requires_grad] for name in bb.res_layers]
         self.lateral_params = [p for cm in neck.lateral_convs for p in cm.parameters() if p.requires_grad]
-        self.head_params = [p for p in list(neck.fpn_convs[0].parameters()) + list(head.parameters()) if p.requires_grad]
+        self.head_params = [p for p in [q for cm in neck.fpn_convs for q in cm.parameters()] + list(head.parameters())
+                            if p.requires_grad]
         self.signature = signature(model)
 
 
@@ -86,8 +88,10 @@ def signature(model):
 def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     """None when ``forward_train`` can be differentiable, else why not."""
     bb, neck, head = model.backbone, model.neck, model.bbox_head
-    if neck is None or type(neck).__name__ != 'FPN' or len(neck.fpn_convs) != 1:
-        return 'needs an FPN neck with num_outs == 1 (every shipped CPR / P2P config)'
+    if neck is None or type(neck).__name__ != 'FPN' or len(neck.fpn_convs) < 1:
+        return 'needs an FPN neck'
+    if len(neck.fpn_convs) != 1 and type(head).__name__ != 'P2PHead':
+        return 'needs an FPN neck with num_outs == 1 (every shipped CPR config; CPRHead asserts one level, cpr_head.py:487)'
     if bb.compute_dtype != torch.float32 and bb.batch_stats_active():
         return 'BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only, not with the bf16 compute mode'
     if bb.compute_dtype != torch.float32 and type(head).__name__ not in ('CPRHead', 'P2PHead'):
@@ -109,8 +113,10 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
         if head.num_cls_fcs > 0 and bb.compute_dtype != torch.float32:
             return 'num_cls_fcs > 0 trains in the fp32 compute mode (the FC backward reads fp32 activations)'
     elif kind == 'P2PHead':
-        if head.num_points != 1 or not getattr(head, 'train_cfg', None):
-            return 'P2PHead trains with one point per cell and a train_cfg (the shipped P2P configs)'
+        if not getattr(head, 'train_cfg', None):
+            return 'P2PHead trains with a train_cfg (the shipped P2P configs)'
+        if len(head.strides) != len(neck.fpn_convs):
+            return 'P2PHead needs one FPN output per stride (%d strides, num_outs %d)' % (len(head.strides), len(neck.fpn_convs))
     else:
         return 'no backward rules for head %s' % kind
     return None
@@ -166,23 +172,25 @@ class _StageFn(torch.autograd.Function):
 
 
 class _LateralsFn(torch.autograd.Function):
-    """FPN lateral convs + GroupNorm + the top-down nearest-upsample adds (T/mmdet/models/necks/fpn.py:166-188) -> the finest
-    lateral sum (the only one an output conv reads when num_outs == 1)."""
+    """FPN lateral convs + GroupNorm + the top-down nearest-upsample adds (T/mmdet/models/necks/fpn.py:166-188) -> the lateral
+    sums the output convs read: the finest alone when num_outs == 1, else one output per FPN output level, finest first."""
 
     @staticmethod
     def forward(ctx, bridge, n_in, *args):
         xs, params = args[:n_in], args[n_in:]
-        lat0, recs = bridge.engine.forward_laterals([bridge.real(x) for x in xs])
+        lat, recs = bridge.engine.forward_laterals([bridge.real(x) for x in xs])
         ctx.bridge, ctx.recs, ctx.params, ctx.n_in = bridge, recs, params, n_in
-        return bridge.carrier(lat0)
+        ctx.multi = isinstance(lat, (tuple, list))
+        return tuple(bridge.carrier(t) for t in lat) if ctx.multi else bridge.carrier(lat)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, dlat):
+    def backward(ctx, *dlat):
         eng = ctx.bridge.engine
         assert ctx.recs is not None, _CONSUMED
         need = [ctx.needs_input_grad[2 + i] for i in range(ctx.n_in)]
-        dxs = eng.backward_laterals(ctx.recs, dlat.contiguous(), need)
+        d = [g.contiguous() for g in dlat] if ctx.multi else dlat[0].contiguous()
+        dxs = eng.backward_laterals(ctx.recs, d, need)
         grads = eng.collect(ctx.params)
         ctx.recs = None
         return (None, None) + tuple(dxs) + grads
@@ -195,14 +203,16 @@ class _HeadLossFn(torch.autograd.Function):
     affines from layer to layer, so this is the smallest unit with a true gradient on both sides."""
 
     @staticmethod
-    def forward(ctx, bridge, lat0, pack, *params):
+    def forward(ctx, bridge, pack, n_lat, *args):
         eng = bridge.engine
-        out, state = eng.forward_head_loss(bridge.real(lat0), pack.img_metas, pack.gt_bboxes, pack.gt_labels,
+        lats, params = args[:n_lat], args[n_lat:]
+        lat = bridge.real(lats[0]) if n_lat == 1 else tuple(bridge.real(t) for t in lats)
+        out, state = eng.forward_head_loss(lat, pack.img_metas, pack.gt_bboxes, pack.gt_labels,
                                            pack.gt_bboxes_ignore, pack.gt_true_bboxes)
         saved = state[1] if isinstance(state, tuple) and len(state) == 2 and isinstance(state[1], dict) else None
         if saved is not None and saved.get(eng.loss_vector_key) is out:
             saved[eng.loss_vector_key] = out.detach()
-        ctx.bridge, ctx.state, ctx.params = bridge, state, params
+        ctx.bridge, ctx.state, ctx.params, ctx.n_lat = bridge, state, params, n_lat
         return out
 
     @staticmethod
@@ -215,7 +225,7 @@ class _HeadLossFn(torch.autograd.Function):
         dlat = eng.backward_head_loss(ctx.state, gout.contiguous().float())
         grads = eng.collect(ctx.params)
         ctx.state = None
-        return (None, dlat, None) + grads
+        return (None, None, None) + (tuple(dlat) if ctx.n_lat > 1 else (dlat,)) + grads
 
 
 # ------------------------------------------------------------------------------------------------ entry point
@@ -245,8 +255,9 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
         feats.append(x)
     assert len(feats) == len(neck.in_channels)
     xs = feats[neck.start_level:neck.start_level + len(neck.lateral_convs)]
-    lat0 = _LateralsFn.apply(bridge, len(xs), *xs, *bridge.lateral_params)
+    lat = _LateralsFn.apply(bridge, len(xs), *xs, *bridge.lateral_params)
+    lats = tuple(lat) if isinstance(lat, (tuple, list)) else (lat,)
     pack = _GtPack(img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
-    out = _HeadLossFn.apply(bridge, lat0, pack, *bridge.head_params)
+    out = _HeadLossFn.apply(bridge, pack, len(lats), *lats, *bridge.head_params)
     bridge._maps.clear()          # every forward consumer has run; the backward reads the tapes
     return eng.loss_dict(out)

@@ -1291,18 +1291,38 @@ extern "C" int cpr_sgd_step(float* p, const float* grad, float* buf, const doubl
 //   d/dx [bce * at * pt^g] = at * [pt^g (p - t) + bce * g * pt^(g-1) * (1 - 2t) * p (1 - p)]
 // SmoothL1 on pred/stride/reg_norm with pred = anchor + (point_anchor + reg*gamma_p) * stride:
 //   d/dreg = (|e| < beta ? e/beta : sign(e)) * gamma_p / reg_norm,  e = (pred - gt)/stride/reg_norm
-// Both scaled by loss_weight / (number of positives in the batch, a device scalar).  Outputs use the padded channel counts
-// of the conv gradient kernels: dcls (B*M, Cp) with the first C columns live, dreg (B*M, Rp) with the first 2 live.
+// Both scaled by loss_weight / (number of positives in the batch, a device scalar).
+// Outputs: one thread per proposal row (b, m), m = the row in the levels' concatenation (every level's H_l*W_l cells times
+// P points, cell-major), written straight into level l's NHWC gradient map of the output conv: class c of point p at channel
+// p*C + c of dcls[l] (B, H_l, W_l, cp[l]), coordinate k at channel p*2 + k of dreg[l] (B, H_l, W_l, rp[l]) -- the reference's
+// permute(0,2,3,1).reshape(B,-1,C) order (p2p_head.py:143-148).  The padding channels [P*C, cp) / [2P, rp) of a cell are
+// written as zeros by the thread of its last point.  No atomics: every element has one writer.  L = 1, P = 1 is the flat
+// (B*M, Cp) / (B*M, Rp) layout with the same arithmetic (cpr_p2p_loss_bwd).
+#define P2P_LOSS_BWD_MAX_LEVELS 8
+struct P2PLossLevels {
+    int L, P;
+    int hw[P2P_LOSS_BWD_MAX_LEVELS], off[P2P_LOSS_BWD_MAX_LEVELS], cp[P2P_LOSS_BWD_MAX_LEVELS], rp[P2P_LOSS_BWD_MAX_LEVELS];
+    float* dcls[P2P_LOSS_BWD_MAX_LEVELS];
+    float* dreg[P2P_LOSS_BWD_MAX_LEVELS];
+};
 __global__ void p2p_loss_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ pred,
                                     const long long* __restrict__ gt_inds, const float* __restrict__ gt_pts,
                                     const int* __restrict__ gt_labels, const int* __restrict__ gt_start,
-                                    const float* __restrict__ npos, float* __restrict__ dcls, float* __restrict__ dreg,
-                                    int M, int C, int Cp, int Rp, float alpha, float gamma, float beta, float pos_w,
+                                    const float* __restrict__ npos, const P2PLossLevels lv,
+                                    int M, int C, float alpha, float gamma, float beta, float pos_w,
                                     float neg_w, float reg_norm, float w_cls, float w_reg, float gamma_p,
                                     const float* __restrict__ up, int cls_mode, int reg_mode, float cls_total) {
     const int b = blockIdx.y;
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
+    int l = 0;
+    while (l + 1 < lv.L && m >= lv.off[l + 1]) ++l;
+    const int P = lv.P;
+    const int local = m - lv.off[l];
+    const int cell = local / P, pt = local - cell * P;
+    const int Cp = lv.cp[l], Rp = lv.rp[l];
+    float* __restrict__ ocls = lv.dcls[l] + ((size_t)b * lv.hw[l] + cell) * Cp;     // this cell's row of the level's map
+    float* __restrict__ oreg = lv.dreg[l] + ((size_t)b * lv.hw[l] + cell) * Rp;
     if (up) { w_cls *= up[b * 2]; w_reg *= up[b * 2 + 1]; }     // upstream gradients of this image's (loss_cls, loss_pts)
     const size_t r = (size_t)b * M + m;
     const float inv_n = 1.f / fmaxf(npos[0], 1.f);
@@ -1318,43 +1338,58 @@ __global__ void p2p_loss_bwd_kernel(const float* __restrict__ logits, const floa
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, logits[r * C + c]);
         for (int c = 0; c < C; ++c) se += expf(logits[r * C + c] - mx);
     }
-    for (int c = 0; c < Cp; ++c) {
-        float d = 0.f;
-        if (c < C) {
-            const float x = logits[r * C + c];
-            if (cls_mode == 2) {
-                const int lab = gi < 0 ? 0 : label;
-                d = (expf(x - mx) / se - (c == lab ? 1.f : 0.f)) * w * w_cls * inv_c;
+    for (int c = 0; c < C; ++c) {
+        float d;
+        const float x = logits[r * C + c];
+        if (cls_mode == 2) {
+            const int lab = gi < 0 ? 0 : label;
+            d = (expf(x - mx) / se - (c == lab ? 1.f : 0.f)) * w * w_cls * inv_c;
+        } else {
+            const float p = 1.f / (1.f + expf(-x));
+            const float t = (c == label) ? 1.f : 0.f;
+            if (cls_mode == 1) {
+                d = (p - t) * w * w_cls * inv_c;
             } else {
-                const float p = 1.f / (1.f + expf(-x));
-                const float t = (c == label) ? 1.f : 0.f;
-                if (cls_mode == 1) {
-                    d = (p - t) * w * w_cls * inv_c;
-                } else {
-                    const float pt = (1.f - p) * t + p * (1.f - t);
-                    const float at = alpha * t + (1.f - alpha) * (1.f - t);
-                    const float ptg = (gamma == 2.f) ? pt * pt : powf(pt, gamma);
-                    const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-                    // d/dx at*pt^g*bce = at*(pt^g*(p-t) + g*bce*pt^(g-1)*(1-2t)*p(1-p)); p(1-p) == pt(1-pt) for a binary t, so
-                    // pt^g factors out and no negative power of pt is formed (powf(0, g-1) = inf for g < 1, and inf * 0 = NaN
-                    // where fp32 p saturates to 1)
-                    d = at * ptg * ((p - t) + gamma * bce * (1.f - pt) * (1.f - 2.f * t)) * w * w_cls * inv_c;
-                }
+                const float pt = (1.f - p) * t + p * (1.f - t);
+                const float at = alpha * t + (1.f - alpha) * (1.f - t);
+                const float ptg = (gamma == 2.f) ? pt * pt : powf(pt, gamma);
+                const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+                // d/dx at*pt^g*bce = at*(pt^g*(p-t) + g*bce*pt^(g-1)*(1-2t)*p(1-p)); p(1-p) == pt(1-pt) for a binary t, so
+                // pt^g factors out and no negative power of pt is formed (powf(0, g-1) = inf for g < 1, and inf * 0 = NaN
+                // where fp32 p saturates to 1)
+                d = at * ptg * ((p - t) + gamma * bce * (1.f - pt) * (1.f - 2.f * t)) * w * w_cls * inv_c;
             }
         }
-        dcls[r * Cp + c] = d;
+        ocls[pt * C + c] = d;
     }
     const float s = pred[r * 3 + 2];
-    for (int k = 0; k < Rp; ++k) {
+    for (int k = 0; k < 2; ++k) {
         float d = 0.f;
-        if (pos && k < 2) {
+        if (pos) {
             const float e = pred[r * 3 + k] / s / reg_norm - gt_pts[g * 2 + k] / s / reg_norm;
             const float sg = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
             const float de = reg_mode == 1 ? 2.f * e : reg_mode == 2 ? sg : (fabsf(e) < beta) ? e / beta : sg;
             d = de * gamma_p / reg_norm * w_reg * inv_n;
         }
-        dreg[r * Rp + k] = d;
+        oreg[pt * 2 + k] = d;
     }
+    if (pt == P - 1) {                 // the cell's padding channels
+        for (int c = P * C; c < Cp; ++c) ocls[c] = 0.f;
+        for (int k = P * 2; k < Rp; ++k) oreg[k] = 0.f;
+    }
+}
+static int p2p_loss_bwd_launch(const float* logits, const float* pred, const long long* gt_inds, const float* gt_pts,
+                               const int* gt_labels, const int* gt_start, const float* npos, const P2PLossLevels& lv, int B,
+                               int M, int C, float alpha, float gamma, float beta, float pos_w, float neg_w, float reg_norm,
+                               float w_cls, float w_reg, float gamma_p, const float* upstream, int cls_mode, int reg_mode,
+                               hipStream_t stream) {
+    CPR_CHECK_ARG(B > 0 && M > 0 && C > 0 && (beta > 0 || reg_mode != 0));
+    CPR_CHECK_ARG(cls_mode >= 0 && cls_mode <= 2 && reg_mode >= 0 && reg_mode <= 2 && (cls_mode != 2 || C >= 2));
+    CPR_CHECK_ARG(logits && pred && gt_inds && gt_pts && gt_labels && gt_start && npos);
+    hipLaunchKernelGGL(p2p_loss_bwd_kernel, dim3(cdiv(M, 256), B), dim3(256), 0, stream, logits, pred, gt_inds, gt_pts,
+                       gt_labels, gt_start, npos, lv, M, C, alpha, gamma, beta, pos_w, neg_w, reg_norm, w_cls, w_reg, gamma_p,
+                       upstream, cls_mode, reg_mode, (float)((double)B * (double)M));
+    CPR_LAUNCH_STATUS();
 }
 extern "C" int cpr_p2p_loss_bwd(const float* logits, const float* pred, const long long* gt_inds, const float* gt_pts,
                                 const int* gt_labels, const int* gt_start, const float* npos, float* dcls, float* dreg,
@@ -1362,10 +1397,32 @@ extern "C" int cpr_p2p_loss_bwd(const float* logits, const float* pred, const lo
                                 float neg_w, float reg_norm, float w_cls, float w_reg, float gamma_p, const float* upstream,
                                 int cls_mode, int reg_mode, hipStream_t stream) {
     CPR_CHECK_ARG(B > 0 && M > 0 && C > 0 && Cp >= C && Rp >= 2 && (beta > 0 || reg_mode != 0));
-    CPR_CHECK_ARG(cls_mode >= 0 && cls_mode <= 2 && reg_mode >= 0 && reg_mode <= 2 && (cls_mode != 2 || C >= 2));
-    CPR_CHECK_ARG(logits && pred && gt_inds && gt_pts && gt_labels && gt_start && npos && dcls && dreg);
-    hipLaunchKernelGGL(p2p_loss_bwd_kernel, dim3(cdiv(M, 256), B), dim3(256), 0, stream, logits, pred, gt_inds, gt_pts,
-                       gt_labels, gt_start, npos, dcls, dreg, M, C, Cp, Rp, alpha, gamma, beta, pos_w, neg_w, reg_norm,
-                       w_cls, w_reg, gamma_p, upstream, cls_mode, reg_mode, (float)((double)B * (double)M));
-    CPR_LAUNCH_STATUS();
+    CPR_CHECK_ARG(dcls && dreg);
+    P2PLossLevels lv{};
+    lv.L = 1, lv.P = 1, lv.hw[0] = M, lv.off[0] = 0, lv.cp[0] = Cp, lv.rp[0] = Rp, lv.dcls[0] = dcls, lv.dreg[0] = dreg;
+    return p2p_loss_bwd_launch(logits, pred, gt_inds, gt_pts, gt_labels, gt_start, npos, lv, B, M, C, alpha, gamma, beta,
+                               pos_w, neg_w, reg_norm, w_cls, w_reg, gamma_p, upstream, cls_mode, reg_mode, stream);
+}
+extern "C" int cpr_p2p_loss_bwd_levels(const float* logits, const float* pred, const long long* gt_inds, const float* gt_pts,
+                                       const int* gt_labels, const int* gt_start, const float* npos, int B, int M, int C, int P,
+                                       int L, const int* level_hw, const int* level_off, const int* level_cp,
+                                       const int* level_rp, float* const* level_dcls, float* const* level_dreg, float alpha,
+                                       float gamma, float beta, float pos_w, float neg_w, float reg_norm, float w_cls,
+                                       float w_reg, float gamma_p, const float* upstream, int cls_mode, int reg_mode,
+                                       hipStream_t stream) {
+    CPR_CHECK_ARG(L >= 1 && L <= P2P_LOSS_BWD_MAX_LEVELS && P >= 1 && C > 0 && M > 0);
+    CPR_CHECK_ARG(level_hw && level_off && level_cp && level_rp && level_dcls && level_dreg);
+    P2PLossLevels lv{};
+    lv.L = L, lv.P = P;
+    long long next = 0;        // the table's rows must tile [0, M): level l owns [off[l], off[l] + hw[l] * P)
+    for (int l = 0; l < L; ++l) {
+        CPR_CHECK_ARG(level_hw[l] > 0 && (long long)level_off[l] == next);
+        CPR_CHECK_ARG(level_cp[l] >= P * C && level_rp[l] >= 2 * P && level_dcls[l] && level_dreg[l]);
+        next += (long long)level_hw[l] * P;
+        lv.hw[l] = level_hw[l], lv.off[l] = level_off[l], lv.cp[l] = level_cp[l], lv.rp[l] = level_rp[l];
+        lv.dcls[l] = level_dcls[l], lv.dreg[l] = level_dreg[l];
+    }
+    CPR_CHECK_ARG(next == M);
+    return p2p_loss_bwd_launch(logits, pred, gt_inds, gt_pts, gt_labels, gt_start, npos, lv, B, M, C, alpha, gamma, beta,
+                               pos_w, neg_w, reg_norm, w_cls, w_reg, gamma_p, upstream, cls_mode, reg_mode, stream);
 }

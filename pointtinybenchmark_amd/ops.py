@@ -1507,6 +1507,52 @@ def p2p_loss_bwd(logits, pred, gt_inds, gt_pts, gt_labels, gt_start, alpha, gamm
     return dcls, dreg
 
 
+P2P_LOSS_BWD_MAX_LEVELS = 8       # csrc/backward.hip: the level table of p2p_loss_bwd_kernel
+
+
+def p2p_grad_pad(n):
+    """Channel count of an output-conv gradient map with n live channels, as the conv gradient kernels take it."""
+    return 4 if n <= 4 else (n + 31) // 32 * 32
+
+
+def p2p_loss_bwd_levels(logits, pred, gt_inds, gt_pts, gt_labels, gt_start, shapes, num_points, alpha, gamma, beta, pos_w, neg_w,
+                        reg_norm, w_cls, w_reg, gamma_p, upstream=None, cls_mode=0, reg_mode=0, cps=None, rps=None, offsets=None,
+                        out=None):
+    """``p2p_loss_bwd`` for several FPN levels and ``num_points`` points per cell.  logits (B, M, C) / pred (B, M, 3): the levels'
+    proposals concatenated (P2PHead.get_pred_points); shapes: [(H_l, W_l)] per level.  -> (dcls list of (B, H_l, W_l, cp_l),
+    dreg list of (B, H_l, W_l, rp_l)): the gradient maps of every level's cls_out / reg_out, point p's channels at p*C .. and
+    p*2 .., padding zero.  cps / rps / offsets default to p2p_grad_pad(P*C) / p2p_grad_pad(2P) / the running row offsets.
+    out: (dcls, dreg) lists of maps to write into instead of fresh ones."""
+    B, M, C = _check(logits).shape
+    P, L = int(num_points), len(shapes)
+    assert upstream is None or (tuple(upstream.shape) == (B, 2) and upstream.dtype == torch.float32 and upstream.is_contiguous())
+    _check(pred), _check(gt_inds, torch.int64), _check(gt_pts), _check(gt_labels, torch.int32), _check(gt_start, torch.int32)
+    assert tuple(pred.shape) == (B, M, 3) and tuple(gt_inds.shape) == (B, M) and gt_start.numel() >= B, \
+        (tuple(pred.shape), tuple(gt_inds.shape), gt_start.numel())
+    cps = [p2p_grad_pad(P * C)] * L if cps is None else [int(c) for c in cps]
+    rps = [p2p_grad_pad(2 * P)] * L if rps is None else [int(r) for r in rps]
+    if offsets is None:
+        offsets = [0]
+        for h, w in shapes[:-1]:
+            offsets.append(offsets[-1] + h * w * P)
+    npos = (gt_inds > 0).sum().to(torch.float32).reshape(1)          # device scalar, no host sync
+    if out is None:
+        dcls = [torch.empty((B, h, w, c), device=logits.device, dtype=torch.float32) for (h, w), c in zip(shapes, cps)]
+        dreg = [torch.empty((B, h, w, r), device=logits.device, dtype=torch.float32) for (h, w), r in zip(shapes, rps)]
+    else:
+        dcls, dreg = list(out[0]), list(out[1])
+        for t, (h, w), c in list(zip(dcls, shapes, cps)) + list(zip(dreg, shapes, rps)):
+            assert tuple(_check(t).shape) == (B, h, w, c), (tuple(t.shape), (B, h, w, c))
+    n = max(L, 1)
+    ints = lambda v: (ctypes.c_int * n)(*[int(x) for x in v])                          # noqa: E731  (host tables)
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])               # noqa: E731
+    _lib.call('cpr_p2p_loss_bwd_levels', _ptr(logits), _ptr(pred), _ptr(gt_inds), _ptr(gt_pts), _ptr(gt_labels), _ptr(gt_start),
+              _ptr(npos), B, M, C, P, L, ints([h * w for h, w in shapes]), ints(offsets), ints(cps), ints(rps), ptrs(dcls),
+              ptrs(dreg), float(alpha), float(gamma), float(beta), float(pos_w), float(neg_w), float(reg_norm), float(w_cls),
+              float(w_reg), float(gamma_p), _ptr(upstream), int(cls_mode), int(reg_mode), _stream())
+    return dcls, dreg
+
+
 def grad_sumsq(g, out, ws, accumulate):
     _lib.call('cpr_grad_sumsq', _ptr(_check(g)), g.numel(), _ptr(ws), _ptr(out), int(accumulate), _stream())
 

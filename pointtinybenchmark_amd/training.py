@@ -11,6 +11,7 @@ moment their gradient becomes final during the backward (head first, backbone st
 flat buffers of the same layout.  Buckets are contiguous ranges of the gradient buffer: each is all-reduced (RCCL) as
 soon as its last gradient has been enqueued, overlapping with the rest of the backward; the optimizer is one kernel over
 the flat buffers (the clip coefficient is read from the device, no host sync)."""
+import contextlib
 import os
 import warnings
 
@@ -280,6 +281,7 @@ class BackwardEngine:
     behind ``torch.autograd.Function``s, gradients handed to torch, so that ``loss.backward()`` / DDP / torch.optim drive the
     drop-in classes as they drive the reference's).  ``_g(p)`` is where the gradient of parameter ``p`` is written."""
     _sink, side, _mixed = None, None, False
+    _redirect = None      # id(p) -> scratch: where a later FPN level's contribution to p's gradient goes (_level_grads)
 
     def __init__(self, model, two_streams=True):
         self.model = model
@@ -301,6 +303,10 @@ class BackwardEngine:
 
     def _g(self, p):
         """Where the gradient of ``p`` is written."""
+        if self._redirect is not None:
+            t = self._redirect.get(id(p))
+            if t is not None:
+                return t
         if self._sink is None:
             return p.grad
         t = self._sink.get(id(p))
@@ -349,28 +355,37 @@ class BackwardEngine:
         return dx if need_in else None
 
     def forward_laterals(self, xs):
+        """-> (the lateral sums the FPN output convs read: the finest one alone when num_outs == 1, else a tuple finest first,
+        the backward state)."""
         tape = []
-        lat = self.model.neck.run_laterals(list(xs), tape)
-        return lat[0], {r['level']: r for r in tape}
+        neck = self.model.neck
+        lat = neck.run_laterals(list(xs), tape)
+        n = len(neck.fpn_convs)
+        return (lat[0] if n == 1 else tuple(lat[:n])), {r['level']: r for r in tape}
 
     def backward_laterals(self, recs, dlat, need):
-        """need[i]: whether the gradient wrt the i-th input (stage start_level + i) is wanted -> list of gradients / None."""
+        """dlat: gradient wrt the lateral sum(s) forward_laterals returned.  need[i]: whether the gradient wrt the i-th input (stage start_level + i) is wanted -> list of gradients / None."""
         neck = self.model.neck
         d_stage = self._backward_laterals(neck, recs, dlat, need_dx_of=lambda stage: need[stage - neck.start_level])
         return [d_stage.get(i + neck.start_level) for i in range(len(need))]
 
-    def forward_head_loss(self, lat0, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_true_bboxes=None):
-        """FPN output conv (lazy) -> head -> losses: returns the loss vector of the loss kernels and the backward state."""
+    def forward_head_loss(self, lat, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_true_bboxes=None):
+        """FPN output conv(s) (lazy) -> head -> losses: returns the loss vector of the loss kernels and the backward state.
+        lat: what forward_laterals returned (one lateral sum, or one per FPN output level)."""
         from .layers import conv_gn
         neck, head = self.model.neck, self.model.bbox_head
-        rec = dict(kind='out', level=0)
-        lazy = [conv_gn(neck._cache, neck.fpn_convs[0], lat0, materialize=False, save=rec)]
+        lats = list(lat) if isinstance(lat, (tuple, list)) else [lat]
+        recs = [dict(kind='out', level=i) for i in range(len(lats))]
+        lazy = [conv_gn(neck._cache, neck.fpn_convs[i], t, materialize=False, save=rec) for i, (t, rec) in enumerate(zip(lats, recs))]
         _, saved = self._forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
-        return saved[self.loss_vector_key], (rec, saved)
+        return saved[self.loss_vector_key], (recs if isinstance(lat, (tuple, list)) else recs[0], saved)
 
     def backward_head_loss(self, state, upstream):
+        """-> the gradient wrt the lateral sum(s) forward_head_loss read, in the same form."""
         rec, saved = state
         dz = self._backward_head(self.model.bbox_head, saved, upstream=upstream)
+        if isinstance(rec, list):
+            return [self._backward_out_conv(r, d) for r, d in zip(rec, dz)]
         return self._backward_out_conv(rec, dz)
 
     loss_vector_key = 'out5'       # CPRHead: (gt_loss, pos_loss, bag_acc, neg_loss, num_sample)
@@ -380,6 +395,23 @@ class BackwardEngine:
 
 
     # ------------------------------------------------------------------ helpers
+    @contextlib.contextmanager
+    def _level_grads(self, level, params):
+        """Backward of one layer of a tower shared by several FPN levels: level 0 writes the gradients of ``params`` where
+        ``_g`` points; a later level writes them into scratch, added on the side stream once the level's rule has been
+        enqueued -- so the sum over levels runs in level order, the same every step."""
+        if level == 0:
+            yield
+            return
+        scratch = {id(p): torch.empty(p.shape, device=p.device, dtype=torch.float32) for p in params}
+        self._redirect = scratch
+        try:
+            yield
+        finally:
+            self._redirect = None
+        dst = [self._g(p) for p in params]
+        self._param_side(lambda: [ops.axpby(d, scratch[id(p)], 1.0, 1.0) for d, p in zip(dst, params)], *scratch.values())
+
     def _param_side(self, fn, *tensors):
         """Run the parameter-gradient work ``fn`` on the side stream, ordered after everything enqueued so far on the
         main stream.  ``tensors``: its inputs that may be released by the main stream before the side stream ran."""
@@ -664,12 +696,15 @@ class BackwardEngine:
 
     # ------------------------------------------------------------------ FPN, backbone
     def _backward_neck(self, neck, neck_tape, dz):
-        """Output conv, then the top-down chain from the finest lateral to the coarsest -> {stage: d(stage output)}."""
+        """Output convs, then the top-down chain from the finest lateral to the coarsest -> {stage: d(stage output)}.
+        dz: gradient wrt the (normalised) FPN output -- one map (num_outs == 1), or a list with one per output level."""
         lat_recs = {r['level']: r for r in neck_tape if r['kind'] == 'lateral'}
         out_recs = {r['level']: r for r in neck_tape if r['kind'] == 'out'}
-        assert list(out_recs) == [0], 'num_outs == 1 (every shipped CPR config)'
-        dlat = self._backward_out_conv(out_recs[0], dz)
-        return self._backward_laterals(neck, lat_recs, dlat)
+        dzs = list(dz) if isinstance(dz, (list, tuple)) else [dz]
+        assert sorted(out_recs) == list(range(len(dzs))), 'one gradient per FPN output level (%d outputs, %d gradients)' \
+            % (len(out_recs), len(dzs))
+        dlats = [self._backward_out_conv(out_recs[i], d) for i, d in enumerate(dzs)]     # fpn_convs in the flat order
+        return self._backward_laterals(neck, lat_recs, dlats)
 
     def _backward_out_conv(self, rec, dz):
         """FPN output conv (3x3 + GN, no activation): dz wrt its normalised output -> gradient wrt the finest lateral sum."""
@@ -679,10 +714,17 @@ class BackwardEngine:
 
     def _backward_laterals(self, neck, lat_recs, dlat, need_dx_of=None):
         """The top-down chain from the finest lateral to the coarsest -> {stage: d(stage output) or None}.
+        dlat: gradient wrt the finest lateral sum, or a list: wrt the lateral sums 0, 1, .. that FPN output convs read (each
+        added to what flows up from the finer level before that level's step).
         need_dx_of(stage): whether the gradient wrt that backbone stage's output is wanted (default: the stage trains)."""
         d_stage = {}
         L = len(lat_recs)
+        douts = list(dlat) if isinstance(dlat, (list, tuple)) else [dlat]
+        assert 1 <= len(douts) <= L, (len(douts), L)
+        dlat = douts[0]
         for i in range(L):
+            if 0 < i < len(douts):
+                dlat = ops.axpby(dlat, douts[i], 1.0, 1.0)
             rec = lat_recs[i]
             stage = i + neck.start_level
             need_dx = bool((need_dx_of or self._stage_trainable)(stage))
@@ -1289,78 +1331,88 @@ class P2PHeadRules:
 
     @staticmethod
     def _forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes):
-        assert len(lazy) == 1 and head.num_points == 1, 'single level, one point per cell (the shipped P2P configs)'
-        raw, (a, b) = lazy[0]
-        x = ops.gn_apply(raw, a, b, relu=False)                   # FPN output, materialised once for the two towers
-        cls_tape, reg_tape, save = [], [], {}
-        cls = ops.as_nchw(head._tower(head.cls_convs, head.cls_out, x, tape=cls_tape))
-        reg = ops.as_nchw(head._tower(head.reg_convs, head.reg_out, x, tape=reg_tape))
-        losses = head.loss([cls], [reg], gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore, save=save)
-        save.update(cls_tape=cls_tape, reg_tape=reg_tape, hw=tuple(x.shape[1:3]))
+        """Per FPN level: the output materialised once, the two towers with their own tapes; then the loss over the levels'
+        concatenation (P2PHead.get_pred_points)."""
+        assert len(lazy) == len(head.strides), 'one FPN output per head stride (%d outputs, strides %s)' % (len(lazy), head.strides)
+        cls_outs, reg_outs, cls_tapes, reg_tapes, hws = [], [], [], [], []
+        for raw, (a, b) in lazy:
+            x = ops.gn_apply(raw, a, b, relu=False)               # FPN output, materialised once for the two towers
+            cls_tape, reg_tape = [], []
+            cls_outs.append(ops.as_nchw(head._tower(head.cls_convs, head.cls_out, x, tape=cls_tape)))
+            reg_outs.append(ops.as_nchw(head._tower(head.reg_convs, head.reg_out, x, tape=reg_tape)))
+            cls_tapes.append(cls_tape), reg_tapes.append(reg_tape), hws.append(tuple(x.shape[1:3]))
+        save = {}
+        losses = head.loss(cls_outs, reg_outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore, save=save)
+        save.update(cls_tapes=cls_tapes, reg_tapes=reg_tapes, hws=hws)
         return losses, save
 
     def _backward_head(self, head, s, upstream=None):
+        """-> the gradient wrt the FPN output: one map for a single level, else a list with one per level."""
         from .dense_heads.p2p_head import _get
         lc, lr = head.loss_cls_cfg, head.loss_reg_cfg
-        B, M, C = s['cls'].shape
-        H, W = s['hw']
-        Cp = 4 if C <= 4 else (C + 31) // 32 * 32
-        dcls, dreg = ops.p2p_loss_bwd(s['cls'], s['pred'], s['gt_inds'], s['gt_pts'], s['gt_labels'], s['gt_start'],
-                                      lc.get('alpha', 0.25), lc.get('gamma', 2.0), lr.get('beta', 1.0),
-                                      _get(head.train_cfg, 'pos_weight', 1.0), _get(head.train_cfg, 'neg_weight', 1.0),
-                                      head.reg_norm, lc.get('loss_weight', 1.0), lr.get('loss_weight', 1.0),
-                                      head.pts_gamma, Cp, 4, upstream=upstream, cls_mode=head.cls_mode, reg_mode=head.reg_mode)
+        C, P = s['cls'].shape[2], head.num_points
+        # one launch writes every level's output-conv gradient maps (channel p*C + c / p*2 + k, padding zero)
+        dcls, dreg = ops.p2p_loss_bwd_levels(s['cls'], s['pred'], s['gt_inds'], s['gt_pts'], s['gt_labels'], s['gt_start'],
+                                             s['hws'], P, lc.get('alpha', 0.25), lc.get('gamma', 2.0), lr.get('beta', 1.0),
+                                             _get(head.train_cfg, 'pos_weight', 1.0), _get(head.train_cfg, 'neg_weight', 1.0),
+                                             head.reg_norm, lc.get('loss_weight', 1.0), lr.get('loss_weight', 1.0),
+                                             head.pts_gamma, upstream=upstream, cls_mode=head.cls_mode, reg_mode=head.reg_mode)
         dz = None
-        for tape, dout, n_out, last in ((s['reg_tape'], dreg.view(B, H, W, 4), 2, head.reg_convs[0]),
-                                        (s['cls_tape'], dcls.view(B, H, W, Cp), C, head.cls_convs[0])):
-            if tape[-1]['x'].dtype == torch.bfloat16:
-                d = self._p2p_tower_backward_mixed(tape, dout, n_out)
-                dz = d if dz is None else ops.axpby(dz, d, 1.0, 1.0)
-                continue
-            d = self._out_conv_backward(tape[-1], dout, n_out)
-            self._done(tape[-1]['conv'].bias)
-            for rec in reversed(tape[:-1]):
-                d = self._gn_conv_backward(rec, d, relu=True, need_dx=True)
-                self._done(rec['module'].conv.weight)
-            dz = d if dz is None else ops.axpby(dz, d, 1.0, 1.0)
-        return dz
+        for tapes, douts, n_out in ((s['reg_tapes'], dreg, 2 * P), (s['cls_tapes'], dcls, P * C)):
+            ds = self._p2p_tower_backward(tapes, douts, n_out)
+            dz = ds if dz is None else [ops.axpby(a, b, 1.0, 1.0) for a, b in zip(dz, ds)]
+        return dz[0] if len(dz) == 1 else dz
 
-    def _p2p_tower_backward_mixed(self, tape, dout, n_out):
+    def _p2p_tower_backward(self, tapes, douts, n_out):
+        """One tower (output conv + stacked conv/GN/ReLU layers) over every FPN level, layer-major and level-minor: each
+        layer's parameter gradients are summed over the levels (``_level_grads``) and declared final once, after the last
+        level, so the trainer's flat order and bucket protocol hold for any number of levels.  -> dz per level."""
+        out = tapes[0][-1]['conv']
+        ds = []
+        for lvl, (tape, dout) in enumerate(zip(tapes, douts)):
+            with self._level_grads(lvl, (out.weight, out.bias)):
+                if tape[-1]['x'].dtype == torch.bfloat16:
+                    ds.append(self._p2p_out_conv_backward_mixed(tape, dout, n_out))
+                else:
+                    ds.append(self._out_conv_backward(tape[-1], dout, n_out))
+        self._done(out.bias)
+        for i in range(len(tapes[0]) - 2, -1, -1):
+            cm = tapes[0][i]['module']
+            for lvl, tape in enumerate(tapes):
+                # mixed precision: the gradient map travels to the next GroupNorm backward in bf16 (fp32 at the tower's input)
+                to16 = i > 0 and self._mixed and MIXED_BF16['dz16'] and FUSED_CAST and tape[i - 1]['raw'].dtype == torch.bfloat16
+                with self._level_grads(lvl, (cm.gn.weight, cm.gn.bias, cm.conv.weight)):
+                    ds[lvl] = self._gn_conv_backward(tape[i], ds[lvl], relu=True, need_dx=True, dx_bf16=to16)
+            self._done(cm.conv.weight)
+        return ds
+
+    def _p2p_out_conv_backward_mixed(self, tape, dout, n_out):
         """Mixed precision (the bf16 forward recorded bf16 tower maps): the output conv's gradients straight from the raw bf16 last layer
         and its GroupNorm affine (csrc/p2p_out_bf16.hip: J <= 8; MIXED_BF16 p2p_out / wgrad / dgrad off, or larger J: the fp32 kernels
-        on the widened map), then the tower as in the CPR head -- bf16 gradient maps between its layers, fp32 at its input."""
+        on the widened map).  The tower below it runs as in the CPR head -- bf16 gradient maps between its layers, fp32 at its input --
+        so the data gradient is bf16 when the layer below reads it so."""
         rec = tape[-1]
         conv = rec['conv']
         w, x, ab = conv.weight, rec['x'], rec['in_ab']
         ok = self._mixed and MIXED_BF16['p2p_out'] and ops.p2p_out_bf16_supported(x.shape, n_out)
         wgrad16, dgrad16 = ok and MIXED_BF16['wgrad'], ok and MIXED_BF16['dgrad']
-        order = list(reversed(tape[:-1]))
-        to16 = bool(order) and self._mixed and MIXED_BF16['dz16'] and FUSED_CAST and order[0]['raw'].dtype == torch.bfloat16
+        to16 = len(tape) > 1 and self._mixed and MIXED_BF16['dz16'] and FUSED_CAST and tape[-2]['raw'].dtype == torch.bfloat16
         if not (wgrad16 or dgrad16):
-            d = self._out_conv_backward(rec, dout, n_out)
+            return self._out_conv_backward(rec, dout, n_out)
+        gw, gb = self._g(w), self._g(conv.bias)
+        if wgrad16:
+            self._param_side(lambda: ops.p2p_out_bf16_wgrad(dout, x, ab, tuple(w.shape), out_w=gw, out_b=gb), dout, x, ab[0], ab[1])
         else:
-            gw, gb = self._g(w), self._g(conv.bias)
-            if wgrad16:
-                self._param_side(lambda: ops.p2p_out_bf16_wgrad(dout, x, ab, tuple(w.shape), out_w=gw, out_b=gb), dout, x, ab[0], ab[1])
-            else:
-                xw = self._f32(x)
-                Cp = dout.shape[-1]
-                self._param_side(lambda: (gw.copy_(ops.conv2d_wgrad(dout, xw, (Cp,) + tuple(w.shape[1:]), 1, 1, in_ab=ab,
-                                                                    in_relu=True)[:n_out]),
-                                          gb.copy_(ops.relu_bwd_colsum(dout, None, want_g=False)[1][:n_out])), dout, xw)
-            if dgrad16:
-                d = ops.p2p_out_bf16_dgrad(dout, w.detach(), tuple(x.shape), torch.bfloat16 if to16 else torch.float32)
-            else:
-                wpad = torch.zeros((dout.shape[-1],) + tuple(w.shape[1:]), device=w.device, dtype=torch.float32)
-                wpad[:n_out] = w.detach()
-                d = ops.conv2d_dgrad(dout, ops.dgrad_pack(wpad, 1, 1), (x.shape[1], x.shape[2]), 1)
-        self._done(conv.bias)
-        for i, r in enumerate(order):
-            nxt = order[i + 1] if i + 1 < len(order) else None
-            to16 = nxt is not None and self._mixed and MIXED_BF16['dz16'] and FUSED_CAST and nxt['raw'].dtype == torch.bfloat16
-            d = self._gn_conv_backward(r, d, relu=True, need_dx=True, dx_bf16=to16)
-            self._done(r['module'].conv.weight)
-        return d
+            xw = self._f32(x)
+            Cp = dout.shape[-1]
+            self._param_side(lambda: (gw.copy_(ops.conv2d_wgrad(dout, xw, (Cp,) + tuple(w.shape[1:]), 1, 1, in_ab=ab,
+                                                                in_relu=True)[:n_out]),
+                                      gb.copy_(ops.relu_bwd_colsum(dout, None, want_g=False)[1][:n_out])), dout, xw)
+        if dgrad16:
+            return ops.p2p_out_bf16_dgrad(dout, w.detach(), tuple(x.shape), torch.bfloat16 if to16 else torch.float32)
+        wpad = torch.zeros((dout.shape[-1],) + tuple(w.shape[1:]), device=w.device, dtype=torch.float32)
+        wpad[:n_out] = w.detach()
+        return ops.conv2d_dgrad(dout, ops.dgrad_pack(wpad, 1, 1), (x.shape[1], x.shape[2]), 1)
 
 
 class P2PTrainer(P2PHeadRules, CprTrainer):
