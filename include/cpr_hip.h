@@ -171,6 +171,25 @@ int cpr_nhwc_to_nchw(const float* in, float* out, int N, int C, int H, int W, vo
 int cpr_stem7x7s2_pool_f32(const float* in, const float* wgt, const float* scale, const float* bias, float* out, int N, int H,
                            int W, int layout, void* stream);
 int cpr_maxpool3x3s2(const float* in, float* out, int N, int H, int W, int C, void* stream);
+/* Recording instances (training with a trainable stem): the same pooled map, bit for bit, and next to it arg (N, PH, PW, 64) uint8 =
+ * the window position 0..8 (row-major) of each maximum, the first of tied positions (torch's max_pool2d rule), 255 where the pooled
+ * value is 0 (the ReLU passes no gradient there).  The bf16 instances take the argmax of their own bf16-rounded values. */
+int cpr_maxpool3x3s2_rec(const float* in, float* out, unsigned char* arg, int N, int H, int W, int C, void* stream);
+int cpr_maxpool3x3s2_bf16_rec(const void* in, void* out, unsigned char* arg, int N, int H, int W, int C, void* stream);
+int cpr_stem7x7s2_pool_f32_rec(const float* in, const float* wgt, const float* scale, const float* bias, float* out,
+                               unsigned char* arg, int N, int H, int W, int layout, void* stream);
+int cpr_stem7x7s2_pool_bf16_rec(const float* in, const void* wgt, const float* scale, const float* bias, void* out,
+                                unsigned char* arg, int N, int H, int W, int layout, void* stream);
+/* Stem backward (csrc/stem_bwd.hip).  cpr_stem_pool_bwd: pooled gradient dp (N, PH, PW, 64) fp32 + the recorded arg map -> dy
+ * (N, OH, OW, 64) fp32, the gradient at the BatchNorm output (through max-pool and ReLU; each conv pixel sums the windows that chose
+ * it, pooled row then column ascending), and part [cpr_stem_pool_bwd_blocks(N*OH*OW)][64][2] per-block column sums of dy (element 0).
+ * cpr_stem_wgrad_f32: gw (64, 3, 7, 7) = the weight gradient of conv 7x7 / 2 / pad 3 given dy (N, OH, OW, 64) and the image (layout 0:
+ * (N, H, W, 4) fp32, layout 1: (N, 3, H, W) fp32), exact fp32 on the matrix pipe, deterministic; ws: cpr_stem_wgrad_f32_workspace
+ * floats. */
+int cpr_stem_pool_bwd_blocks(long long M);
+int cpr_stem_pool_bwd(const float* dp, const unsigned char* arg, float* dy, float* part, int N, int OH, int OW, void* stream);
+int cpr_stem_wgrad_f32_workspace(int N, int H, int W);
+int cpr_stem_wgrad_f32(const float* dy, const float* in, float* gw, float* ws, int N, int H, int W, int layout, void* stream);
 
 /* GroupNorm of mmcv ConvModule (fpn.py:124-144, cpr_head.py:990-991) as three streaming steps:
  *   stats    part [N][P][C][2] per-slot per-channel (sum, sumsq)

@@ -49,6 +49,14 @@ SIGNATURES = {
     'cpr_nhwc_to_nchw': [_p, _p, _i, _i, _i, _i, _p],
     'cpr_stem7x7s2_pool_f32': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     'cpr_maxpool3x3s2': [_p, _p, _i, _i, _i, _i, _p],
+    'cpr_maxpool3x3s2_rec': [_p, _p, _p, _i, _i, _i, _i, _p],
+    'cpr_maxpool3x3s2_bf16_rec': [_p, _p, _p, _i, _i, _i, _i, _p],
+    'cpr_stem7x7s2_pool_f32_rec': [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'cpr_stem7x7s2_pool_bf16_rec': [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'cpr_stem_pool_bwd_blocks': [_l],
+    'cpr_stem_pool_bwd': [_p, _p, _p, _p, _i, _i, _i, _p],
+    'cpr_stem_wgrad_f32_workspace': [_i, _i, _i],
+    'cpr_stem_wgrad_f32': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     'cpr_gn_stats': [_p, _p, _i, _i, _i, _i, _p],
     'cpr_gn_finalize': [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p],
     'cpr_gn_apply': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],

@@ -7,6 +7,7 @@ calls ``loss.backward()`` + ``clip_grad_norm_`` + ``optimizer.step()``, and ``MM
 One Function per module boundary at which a TRUE gradient tensor exists (the lazy GroupNorm hand-offs inside the neck / head
 chain have none: a raw map travels with a pending affine):
 
+    image -> _StemFn (a trainable stem, frozen_stages=-1) -> _StageFn (layer1)            d(pooled stem map) between them
     image -> stem + frozen stages (no graph)
           -> _StageFn (layer2) -> _StageFn (layer3) -> _StageFn (layer4)          d(stage output) between them
           -> _LateralsFn: lateral 1x1 convs + GN + top-down adds -> the lateral sums the output convs read   d(lateral sums)
@@ -21,7 +22,8 @@ pinned to ``loss.backward()`` through the reference's own modules by tests/golde
 Both compute modes (round 5: the bf16 mode = mixed precision, the reference analogue being mmcv's ``Fp16OptimizerHook`` around an
 unmodified ``loss.backward()``, T/mmdet/apis/train.py:116-119 -- see ``Bridge.carrier`` for how bf16 maps cross the Function
 boundaries), every CPRHead option set that runs forward (``CPRHead.train_step_supported``) with one FPN output level, P2PHead with any number of
-FPN output levels and points per cell, a frozen stem.  Anything else keeps the forward-only path and warns once."""
+FPN output levels and points per cell, a frozen stem or the standard trainable one (conv1 7x7/2, 3 -> 64).  Anything else keeps
+the forward-only path and warns once."""
 import os
 import warnings
 
@@ -56,6 +58,8 @@ class Bridge:
         self.engine = engine
         bb, neck = model.backbone, model.neck
         self._maps = {}         # bf16 compute mode: data_ptr of an fp32 carrier -> the bf16 map it stands for (see carrier())
+        self.stem_params = [p for m in (getattr(bb, 'conv1', None), getattr(bb, 'bn1', None)) if m is not None
+                            for p in m.parameters() if p.requires_grad]
         self.stage_params = [[p for p in getattr(bb, name).parameters() if p.requires_grad] for name in bb.res_layers]
         self.lateral_params = [p for cm in neck.lateral_convs for p in cm.parameters() if p.requires_grad]
         self.head_params = [p for p in [q for cm in neck.fpn_convs for q in cm.parameters()] + list(head.parameters())
@@ -96,8 +100,8 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
         return 'BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only, not with the bf16 compute mode'
     if bb.compute_dtype != torch.float32 and type(head).__name__ not in ('CPRHead', 'P2PHead'):
         return 'the mixed-precision step (bf16 compute mode) covers the CPR and P2P locators'
-    if any(p.requires_grad for m in (bb.conv1, bb.bn1) for p in m.parameters()):
-        return 'a trainable stem (frozen_stages < 0) has no backward rule'
+    if any(p.requires_grad for m in (bb.conv1, bb.bn1) for p in m.parameters()) and bb.stem_train_reason() is not None:
+        return bb.stem_train_reason()
     if tuple(bb.out_indices) != tuple(range(len(bb.res_layers))):
         return 'out_indices must name every stage'
     for name in bb.res_layers:
@@ -146,6 +150,27 @@ def get_bridge(model):
 # maps alive until the garbage collector runs): the engine's state holds the output's storage under another tensor object
 # (``.detach()`` aliases), never the returned object itself.
 _CONSUMED = 'the recorded forward of this step was already consumed (a second backward / retain_graph is not supported)'
+
+
+class _StemFn(torch.autograd.Function):
+    """The standard ResNet stem (conv1 7x7/2 + bn1 + ReLU + max-pool 3x3/2, resnet.py:630-637) when it trains: the image (no
+    gradient) -> the pooled NHWC map; conv1.weight, bn1.weight, bn1.bias as inputs."""
+
+    @staticmethod
+    def forward(ctx, bridge, img, *params):
+        out, rec = bridge.engine.forward_stem(img)
+        ctx.bridge, ctx.rec, ctx.params = bridge, rec, params
+        return bridge.carrier(out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        eng = ctx.bridge.engine
+        assert ctx.rec is not None, _CONSUMED
+        eng.backward_stem(ctx.rec, dout.contiguous())
+        grads = eng.collect(ctx.params)
+        ctx.rec = None
+        return (None, None) + grads
 
 
 class _StageFn(torch.autograd.Function):
@@ -242,8 +267,11 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
     eng._sink.clear()
     bridge._maps.clear()
     bb, neck = model.backbone, model.neck
-    with torch.no_grad():
-        x = bb.stem(img)
+    if bridge.stem_params:
+        x = _StemFn.apply(bridge, img.detach(), *bridge.stem_params)
+    else:
+        with torch.no_grad():
+            x = bb.stem(img)
     feats = []
     for i in range(len(bb.res_layers)):
         params = bridge.stage_params[i]

@@ -6,7 +6,8 @@ BatchNorm in eval mode (norm_eval=True, every CPR/P2P config; or model.eval()) u
 conv epilogue; the bottleneck shortcut add + ReLU are fused into conv3's epilogue.  With norm_eval=False the BatchNorm modules of the
 non-frozen stages are in training mode (the reference's ``train()``) and normalise with batch statistics: raw conv, statistics pass,
 normalise / residual / ReLU pass (csrc/bn_train.hip), running statistics updated on the device.
-The backward of the trainable stages is driven by training.CprTrainer from the per-block records of ``forward(tape=)``."""
+The backward of the trainable stages -- and of a trainable stem (frozen_stages=-1) -- is driven by training.CprTrainer from the records
+of ``forward(tape=)``."""
 import os
 
 import torch
@@ -227,19 +228,50 @@ class ResNet(nn.Module):
                     nn.init.constant_((blk.bn3 if blk.kind == 'bottleneck' else blk.bn2).weight, 0)
         bump_weight_epoch()
 
-    def stem(self, x):
-        """(N,3,H,W) image -> the NHWC map after conv1 + bn1 + ReLU + max-pool (resnet.py:630-637)."""
+    def stem_train_reason(self):
+        """None when the stem has a backward rule (the standard stem: conv1 7x7 / stride 2 / pad 3, 3 -> 64, no bias, + bn1 + ReLU +
+        the 3x3 / 2 max-pool, csrc/stem_bwd.hip), else why not, naming the shape."""
+        c1 = self.conv1
+        if not all(p.requires_grad for p in getattr(self, self.res_layers[0]).parameters()):
+            return 'a trainable stem needs a trainable %s (its backward starts from that stage\'s input gradient)' % self.res_layers[0]
+        if tuple(c1.weight.shape) == (64, 3, 7, 7) and c1.stride == (2, 2) and c1.padding == (3, 3) and c1.bias is None and \
+                c1.dilation == (1, 1) and c1.groups == 1:
+            return None
+        return 'a trainable stem has a backward rule for conv1 7x7 / stride 2 / pad 3, 3 -> 64 only, not for weight %s stride %s ' \
+            'padding %s' % (tuple(c1.weight.shape), c1.stride, c1.padding)
+
+    def stem(self, x, tape=None):
+        """(N,3,H,W) image -> the NHWC map after conv1 + bn1 + ReLU + max-pool (resnet.py:630-637).
+        tape (list): when conv1 or bn1 trains, the recording pool instances run and one record (``stem=True``) is appended: the input as the
+        kernels read it, the argmax byte map of the pool (csrc/stem_bwd.hip reads both), and with batch statistics the raw conv map and
+        its BnStats."""
         c = self._cache
         c1 = self.conv1
+        rec = None
+        if tape is not None and any(p.requires_grad for p in (c1.weight, self.bn1.weight, self.bn1.bias)):
+            reason = self.stem_train_reason()
+            if reason is not None:
+                raise NotImplementedError(reason)
+            rec = dict(stem=True, stage=-1)
+            tape.append(rec)
+
+        def pool(m, inp, planar):
+            if rec is None:
+                return ops.maxpool3x3s2(m)
+            out, arg = ops.maxpool3x3s2(m, record=True)
+            rec.update(x=inp, planar=planar, arg=arg, conv_hw=(m.shape[1], m.shape[2]))
+            return out
         if self.training and self.bn1.training:
-            # a stem BatchNorm in training mode (frozen_stages < 0, norm_eval=False; forward only: a trainable stem has no backward rule):
-            # the implicit-GEMM stem conv, batch statistics, normalise + ReLU, then the max-pool
+            # a stem BatchNorm in training mode (frozen_stages < 0, norm_eval=False): the implicit-GEMM stem conv, batch statistics,
+            # normalise + ReLU, then the max-pool
             self._check_mode()
             x = ops.from_nchw(x) if (x.shape[1] > 4 or (x.shape[1] == 4 and x.stride(1) == 1)) else ops.nchw_to_nhwc(x)
             y = ops.conv2d(x, packed_conv(c, c1))
             bn = self.bn1
             t = ops.bn_batch_stats(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps)
-            return ops.maxpool3x3s2(ops.bn_apply(y, t.scale, t.cshift, center=t.center, relu=True))
+            if rec is not None:
+                rec.update(y=y, stats=t, batch_stats=True)
+            return pool(ops.bn_apply(y, t.scale, t.cshift, center=t.center, relu=True), x, False)
         s, b = folded_bn(c, self.bn1)
         std7 = tuple(c1.weight.shape) == (64, 3, 7, 7) and c1.stride == (2, 2) and c1.padding == (3, 3)
         # the fused stem kernels read the three planes of a contiguous (N,3,H,W) fp32 image themselves (no nchw_to_nhwc4 pass)
@@ -249,22 +281,35 @@ class ResNet(nn.Module):
             # (N,3,H,W) float image -> NHWC4; a 4-channel channels-last view (datasets.GpuImagePipeline output) is taken as is
             x = ops.from_nchw(x) if (x.shape[1] > 4 or (x.shape[1] == 4 and x.stride(1) == 1)) else ops.nchw_to_nhwc(x)
         fused_in = std7 and x.dtype == torch.float32 and (planar or x.shape[-1] == 4)
+        record = rec is not None
         if self.compute_dtype == torch.bfloat16 and BF16_STEM[0] and fused_in and ops.stem_bf16_fits(x, planar):
             # bf16 compute mode: the stem on the bf16 matrix cores (csrc/stem_bf16.hip; round 4)
             wp = c.get(('stem_bf16', id(c1)), [c1.weight], lambda: ops.stem_weight_bf16(c1.weight))
             if BF16_STEM_POOL[0]:
-                return ops.stem7x7s2_pool_bf16(x, wp, scale=s, bias=b, planar=planar)       # conv + BN + ReLU + max-pool, one kernel
-            x = ops.stem7x7s2_bf16(x, wp, scale=s, bias=b, relu=True, planar=planar)
+                # conv + BN + ReLU + max-pool, one kernel
+                r = ops.stem7x7s2_pool_bf16(x, wp, scale=s, bias=b, planar=planar, record=record)
+                if not record:
+                    return r
+                OH, OW = (x.shape[-2] if planar else x.shape[1]) - 1, (x.shape[-1] if planar else x.shape[2]) - 1
+                rec.update(x=x, planar=planar, arg=r[1], conv_hw=(OH // 2 + 1, OW // 2 + 1))
+                return r[0]
+            return pool(ops.stem7x7s2_bf16(x, wp, scale=s, bias=b, relu=True, planar=planar), x, planar)
         elif self.compute_dtype == torch.float32 and F32_STEM[0] and fused_in:
             # conv + BN + ReLU + max-pool in one exact-fp32 kernel (csrc/stem_f32.hip; round 4)
             wp = c.get(('stem_f32', id(c1)), [c1.weight], lambda: ops.stem_weight_f32(c1.weight))
-            return ops.stem7x7s2_pool_f32(x, wp, scale=s, bias=b, planar=planar)
+            r = ops.stem7x7s2_pool_f32(x, wp, scale=s, bias=b, planar=planar, record=record)
+            if not record:
+                return r
+            OH, OW = (x.shape[-2] if planar else x.shape[1]) - 1, (x.shape[-1] if planar else x.shape[2]) - 1
+            rec.update(x=x, planar=planar, arg=r[1], conv_hw=(OH // 2 + 1, OW // 2 + 1))
+            return r[0]
         else:
             # (other stems: the implicit-GEMM kernel in its stem mode; in the bf16 mode it emits the bf16 map)
             if planar:          # (a bf16-mode map too large for the bf16 stem kernel's 32-bit offsets)
                 x = ops.nchw_to_nhwc(x)
+            x4 = x
             x = ops.conv2d(x, packed_conv(c, c1), scale=s, bias=b, relu=True, out_dtype=self.compute_dtype)
-        return ops.maxpool3x3s2(x)
+        return pool(x, x4, False)
 
     def run_stage(self, i, x, tape=None):
         """Stage ``i`` (``layer{i+1}``) on an NHWC map.  tape (list): one record per block with trainable parameters."""
@@ -281,7 +326,7 @@ class ResNet(nn.Module):
         """x: (N,3,H,W) -> tuple of NCHW-shaped (channels_last) stage outputs.
         tape (list): training mode -- one record per block with trainable parameters, in forward order."""
         self._check_mode()
-        x = self.stem(x)
+        x = self.stem(x, tape)
         outs = []
         for i in range(len(self.res_layers)):
             x = self.run_stage(i, x, tape)

@@ -57,8 +57,9 @@ extern "C" int cpr_nhwc_to_nchw(const float* in, float* out, int N, int C, int H
 }
 
 // ------------------------------------------------------------------------------------------------
-__global__ void maxpool3x3s2_kernel(const float* __restrict__ in, float* __restrict__ out, int N, int H, int W,
-                                    int C4, int OH, int OW) {
+template <bool REC>
+__global__ void maxpool3x3s2_kernel(const float* __restrict__ in, float* __restrict__ out, unsigned char* __restrict__ arg, int N,
+                                    int H, int W, int C4, int OH, int OW) {
     const long long total = (long long)N * OH * OW * C4;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
@@ -69,6 +70,7 @@ __global__ void maxpool3x3s2_kernel(const float* __restrict__ in, float* __restr
         const int oy = (int)(r % OH);
         const int n = (int)(r / OH);
         f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        unsigned ks = 0;                                  // REC: four argmax bytes (window position 0..8, first of ties)
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
             const int iy = oy * 2 - 1 + dy;
@@ -78,20 +80,40 @@ __global__ void maxpool3x3s2_kernel(const float* __restrict__ in, float* __restr
                 const int ix = ox * 2 - 1 + dx;
                 if ((unsigned)ix >= (unsigned)W) continue;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(in + (((size_t)n * H + iy) * W + ix) * C4 * 4 + c * 4);
+                if constexpr (REC) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (v[e] > m[e]) ks = (ks & ~(0xffu << (8 * e))) | ((unsigned)(dy * 3 + dx) << (8 * e));
+                }
                 m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
             }
         }
         *reinterpret_cast<f32x4*>(out + i * 4) = m;
+        if constexpr (REC) {                              // the map is a ReLU output: a maximum of 0 passes no gradient (255)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (m[e] == 0.f) ks |= 0xffu << (8 * e);
+            *reinterpret_cast<unsigned*>(arg + i * 4) = ks;
+        }
     }
 }
 
-extern "C" int cpr_maxpool3x3s2(const float* in, float* out, int N, int H, int W, int C, hipStream_t stream) {
+static int maxpool3x3s2_launch(const float* in, float* out, unsigned char* arg, int N, int H, int W, int C, hipStream_t stream) {
     CPR_CHECK_ARG(in && out && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0);
     const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
     const long long total = (long long)N * OH * OW * (C / 4);
     const int grid = (int)(cdivll(total, 256) < 16384 ? cdivll(total, 256) : 16384);
-    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid), dim3(256), 0, stream, in, out, N, H, W, C / 4, OH, OW);
+    if (arg) hipLaunchKernelGGL(maxpool3x3s2_kernel<true>, dim3(grid), dim3(256), 0, stream, in, out, arg, N, H, W, C / 4, OH, OW);
+    else hipLaunchKernelGGL(maxpool3x3s2_kernel<false>, dim3(grid), dim3(256), 0, stream, in, out, arg, N, H, W, C / 4, OH, OW);
     CPR_LAUNCH_STATUS();
+}
+extern "C" int cpr_maxpool3x3s2(const float* in, float* out, int N, int H, int W, int C, hipStream_t stream) {
+    return maxpool3x3s2_launch(in, out, nullptr, N, H, W, C, stream);
+}
+// recording instance: also arg (N, OH, OW, C) uint8 = window position 0..8 of each maximum, 255 where the maximum is 0
+extern "C" int cpr_maxpool3x3s2_rec(const float* in, float* out, unsigned char* arg, int N, int H, int W, int C, hipStream_t stream) {
+    CPR_CHECK_ARG(arg);
+    return maxpool3x3s2_launch(in, out, arg, N, H, W, C, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -280,8 +302,9 @@ __device__ __forceinline__ void st_bf16x4(unsigned short* p, f32x4 v) {
     *reinterpret_cast<uint2*>(p) = u;
 }
 
-__global__ void maxpool3x3s2_bf16_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int N,
-                                         int H, int W, int C4, int OH, int OW) {
+template <bool REC>
+__global__ void maxpool3x3s2_bf16_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out,
+                                         unsigned char* __restrict__ arg, int N, int H, int W, int C4, int OH, int OW) {
     const long long total = (long long)N * OH * OW * C4;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
@@ -292,6 +315,7 @@ __global__ void maxpool3x3s2_bf16_kernel(const unsigned short* __restrict__ in, 
         const int oy = (int)(r % OH);
         const int n = (int)(r / OH);
         f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        unsigned ks = 0;                                  // REC: four argmax bytes (window position 0..8, first of ties)
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
             const int iy = oy * 2 - 1 + dy;
@@ -301,20 +325,40 @@ __global__ void maxpool3x3s2_bf16_kernel(const unsigned short* __restrict__ in, 
                 const int ix = ox * 2 - 1 + dx;
                 if ((unsigned)ix >= (unsigned)W) continue;
                 const f32x4 v = ld_bf16x4(in + (((size_t)n * H + iy) * W + ix) * C4 * 4 + c * 4);
+                if constexpr (REC) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (v[e] > m[e]) ks = (ks & ~(0xffu << (8 * e))) | ((unsigned)(dy * 3 + dx) << (8 * e));
+                }
                 m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
             }
         }
         st_bf16x4(out + i * 4, m);
+        if constexpr (REC) {                              // the map is a ReLU output: a maximum of 0 passes no gradient (255)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (m[e] == 0.f) ks |= 0xffu << (8 * e);
+            *reinterpret_cast<unsigned*>(arg + i * 4) = ks;
+        }
     }
 }
-extern "C" int cpr_maxpool3x3s2_bf16(const void* in, void* out, int N, int H, int W, int C, hipStream_t stream) {
+static int maxpool3x3s2_bf16_launch(const void* in, void* out, unsigned char* arg, int N, int H, int W, int C, hipStream_t stream) {
     CPR_CHECK_ARG(in && out && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0);
     const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
     const long long total = (long long)N * OH * OW * (C / 4);
     const int grid = (int)(cdivll(total, 256) < 16384 ? cdivll(total, 256) : 16384);
-    hipLaunchKernelGGL(maxpool3x3s2_bf16_kernel, dim3(grid), dim3(256), 0, stream, (const unsigned short*)in,
-                       (unsigned short*)out, N, H, W, C / 4, OH, OW);
+    if (arg) hipLaunchKernelGGL(maxpool3x3s2_bf16_kernel<true>, dim3(grid), dim3(256), 0, stream, (const unsigned short*)in,
+                                (unsigned short*)out, arg, N, H, W, C / 4, OH, OW);
+    else hipLaunchKernelGGL(maxpool3x3s2_bf16_kernel<false>, dim3(grid), dim3(256), 0, stream, (const unsigned short*)in,
+                            (unsigned short*)out, arg, N, H, W, C / 4, OH, OW);
     CPR_LAUNCH_STATUS();
+}
+extern "C" int cpr_maxpool3x3s2_bf16(const void* in, void* out, int N, int H, int W, int C, hipStream_t stream) {
+    return maxpool3x3s2_bf16_launch(in, out, nullptr, N, H, W, C, stream);
+}
+extern "C" int cpr_maxpool3x3s2_bf16_rec(const void* in, void* out, unsigned char* arg, int N, int H, int W, int C, hipStream_t stream) {
+    CPR_CHECK_ARG(arg);
+    return maxpool3x3s2_bf16_launch(in, out, arg, N, H, W, C, stream);
 }
 
 __global__ void gn_stats_bf16_kernel(const unsigned short* __restrict__ x, float* __restrict__ part, int HW, int C,

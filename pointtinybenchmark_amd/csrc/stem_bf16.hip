@@ -146,9 +146,11 @@ struct StemPoolParams {
     const float* scale;
     const float* bias;
     unsigned short* out;         // (N, PH, PW, 64) bf16
+    unsigned char* arg;          // recording instance: (N, PH, PW, 64) window position of the bf16 maximum, 255 where it is 0
     int N, H, W, OH, OW, PH, PW, tilesY, tilesX, layout;
 };
 
+template <bool REC>
 __global__ __launch_bounds__(512, 4) void stem_pool_bf16_kernel(StemPoolParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[SP_LDS];
     unsigned char* patch = smem;
@@ -258,6 +260,7 @@ __global__ __launch_bounds__(512, 4) void stem_pool_bf16_kernel(StemPoolParams p
         float mx[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) mx[e] = 0.f;
+        unsigned long long ks = ~0ull;                          // REC: eight argmax bytes, 255 = nothing above 0
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
@@ -265,24 +268,32 @@ __global__ __launch_bounds__(512, 4) void stem_pool_bf16_kernel(StemPoolParams p
                 const u32x4 v = *reinterpret_cast<const u32x4*>(ct + ((2 * py + dy) * 33 + 2 * px + dx) * 64 + g * 8);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    mx[2 * e] = fmaxf(mx[2 * e], __uint_as_float(v[e] << 16));
-                    mx[2 * e + 1] = fmaxf(mx[2 * e + 1], __uint_as_float(v[e] & 0xffff0000u));
+                    const float lo = __uint_as_float(v[e] << 16), hi = __uint_as_float(v[e] & 0xffff0000u);
+                    if constexpr (REC) {              // the first of tied bf16 values wins (torch's rule)
+                        const unsigned long long pos = (unsigned long long)(dy * 3 + dx);
+                        if (lo > mx[2 * e]) ks = (ks & ~(0xffull << (16 * e))) | (pos << (16 * e));
+                        if (hi > mx[2 * e + 1]) ks = (ks & ~(0xffull << (16 * e + 8))) | (pos << (16 * e + 8));
+                    }
+                    mx[2 * e] = fmaxf(mx[2 * e], lo);
+                    mx[2 * e + 1] = fmaxf(mx[2 * e + 1], hi);
                 }
             }
         u32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = (__float_as_uint(mx[2 * e]) >> 16) | (__float_as_uint(mx[2 * e + 1]) & 0xffff0000u);
-        *reinterpret_cast<u32x4*>(p.out + (((size_t)n * p.PH + gy) * p.PW + gx) * 64 + g * 8) = o;
+        const size_t oo = (((size_t)n * p.PH + gy) * p.PW + gx) * 64 + g * 8;
+        *reinterpret_cast<u32x4*>(p.out + oo) = o;
+        if constexpr (REC) *reinterpret_cast<unsigned long long*>(p.arg + oo) = ks;
     }
 }
 
 // in (N,H,W,4) fp32 -> out (N,PH,PW,64) bf16 = maxpool3x3/2/pad 1 (ReLU(conv7x7/2/pad 3 (in) * scale + bias)); OH = (H-1)/2+1,
 // PH = (OH-1)/2+1.
-extern "C" int cpr_stem7x7s2_pool_bf16(const float* in, const void* wgt, const float* scale, const float* bias, void* out, int N,
-                                       int H, int W, int layout, hipStream_t stream) {
+static int stem_pool_bf16_launch(const float* in, const void* wgt, const float* scale, const float* bias, void* out,
+                                 unsigned char* arg, int N, int H, int W, int layout, hipStream_t stream) {
     CPR_CHECK_ARG(in && wgt && out && N > 0 && H > 0 && W > 0 && (layout == 0 || layout == 1));
     StemPoolParams p;
-    p.in = in; p.wgt = (const unsigned short*)wgt; p.scale = scale; p.bias = bias; p.out = (unsigned short*)out;
+    p.in = in; p.wgt = (const unsigned short*)wgt; p.scale = scale; p.bias = bias; p.out = (unsigned short*)out; p.arg = arg;
     p.N = N; p.H = H; p.W = W; p.layout = layout;
     p.OH = (H - 1) / 2 + 1;
     p.OW = (W - 1) / 2 + 1;
@@ -292,8 +303,19 @@ extern "C" int cpr_stem7x7s2_pool_bf16(const float* in, const void* wgt, const f
     p.tilesX = (p.PW + 15) / 16;
     const long long blocks = (long long)N * p.tilesY * p.tilesX;
     if (blocks >= (1ll << 31)) return CPR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(stem_pool_bf16_kernel, dim3((unsigned)blocks), dim3(512), 0, stream, p);
+    if (arg) hipLaunchKernelGGL(stem_pool_bf16_kernel<true>, dim3((unsigned)blocks), dim3(512), 0, stream, p);
+    else hipLaunchKernelGGL(stem_pool_bf16_kernel<false>, dim3((unsigned)blocks), dim3(512), 0, stream, p);
     CPR_LAUNCH_STATUS();
+}
+extern "C" int cpr_stem7x7s2_pool_bf16(const float* in, const void* wgt, const float* scale, const float* bias, void* out, int N,
+                                       int H, int W, int layout, hipStream_t stream) {
+    return stem_pool_bf16_launch(in, wgt, scale, bias, out, nullptr, N, H, W, layout, stream);
+}
+// the recording instance: also arg (N, PH, PW, 64) uint8, the window position of each bf16 maximum (255 where it is 0)
+extern "C" int cpr_stem7x7s2_pool_bf16_rec(const float* in, const void* wgt, const float* scale, const float* bias, void* out,
+                                           unsigned char* arg, int N, int H, int W, int layout, hipStream_t stream) {
+    CPR_CHECK_ARG(arg);
+    return stem_pool_bf16_launch(in, wgt, scale, bias, out, arg, N, H, W, layout, stream);
 }
 
 // in (N,H,W,4) fp32 -> out (N,OH,OW,64) bf16, OH = (H - 1) / 2 + 1; wgt = the (64, 224) bf16 image described above.

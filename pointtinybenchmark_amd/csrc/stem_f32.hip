@@ -33,9 +33,11 @@ struct StemF32Params {
     const float* scale;    // folded BatchNorm (64) or null
     const float* bias;
     float* out;            // (N, PH, PW, 64)
+    unsigned char* arg;    // recording instance: (N, PH, PW, 64) window position 0..8 of the maximum, 255 where the pooled value is 0
     int N, H, W, OH, OW, PH, PW, tilesY, tilesX, layout;
 };
 
+template <bool REC>
 __global__ __launch_bounds__(512, 4) void stem_pool_f32_kernel(StemF32Params p) {
     __shared__ __attribute__((aligned(16))) float smem[SF_LDS_FLOATS];
     float* patch = smem;
@@ -152,15 +154,23 @@ __global__ __launch_bounds__(512, 4) void stem_pool_f32_kernel(StemF32Params p) 
             const int gy = 8 * ty + py, gx = 16 * tx + px;
             if (gy >= p.PH || gx >= p.PW) continue;
             f32x4 mx = {0.f, 0.f, 0.f, 0.f};
+            unsigned ks = 0xffffffffu;                            // REC: four argmax bytes, 255 = nothing above 0 (the ReLU's zero)
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) {
                     const f32x4 v = *reinterpret_cast<const f32x4*>(ct + ((2 * py + dy) * 33 + 2 * px + dx) * 32 + g * 4);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], v[e]);
+                    for (int e = 0; e < 4; ++e) {
+                        if constexpr (REC) {              // strictly greater: the first of tied positions wins (torch's rule)
+                            if (v[e] > mx[e]) ks = (ks & ~(0xffu << (8 * e))) | ((unsigned)(dy * 3 + dx) << (8 * e));
+                        }
+                        mx[e] = fmaxf(mx[e], v[e]);
+                    }
                 }
-            *reinterpret_cast<f32x4*>(p.out + (((size_t)n * p.PH + gy) * p.PW + gx) * 64 + hb * 32 + g * 4) = mx;
+            const size_t o = (((size_t)n * p.PH + gy) * p.PW + gx) * 64 + hb * 32 + g * 4;
+            *reinterpret_cast<f32x4*>(p.out + o) = mx;
+            if constexpr (REC) *reinterpret_cast<unsigned*>(p.arg + o) = ks;
         }
     };
     __syncthreads();                                              // all fragment reads of the K loop are done
@@ -175,11 +185,11 @@ __global__ __launch_bounds__(512, 4) void stem_pool_f32_kernel(StemF32Params p) 
 
 // in (N,H,W,4) fp32 -> out (N,PH,PW,64) fp32 = maxpool3x3/2/pad 1 (ReLU(conv7x7/2/pad 3 (in) * scale + bias)); OH = (H-1)/2+1,
 // PH = (OH-1)/2+1; wgt = the (64, 154) image described above.
-extern "C" int cpr_stem7x7s2_pool_f32(const float* in, const float* wgt, const float* scale, const float* bias, float* out, int N,
-                                      int H, int W, int layout, hipStream_t stream) {
+static int stem_pool_f32_launch(const float* in, const float* wgt, const float* scale, const float* bias, float* out,
+                                unsigned char* arg, int N, int H, int W, int layout, hipStream_t stream) {
     CPR_CHECK_ARG(in && wgt && out && N > 0 && H > 0 && W > 0 && (layout == 0 || layout == 1));
     StemF32Params p;
-    p.in = in; p.wgt = wgt; p.scale = scale; p.bias = bias; p.out = out;
+    p.in = in; p.wgt = wgt; p.scale = scale; p.bias = bias; p.out = out; p.arg = arg;
     p.N = N; p.H = H; p.W = W; p.layout = layout;
     p.OH = (H - 1) / 2 + 1;
     p.OW = (W - 1) / 2 + 1;
@@ -189,6 +199,17 @@ extern "C" int cpr_stem7x7s2_pool_f32(const float* in, const float* wgt, const f
     p.tilesX = (p.PW + 15) / 16;
     const long long blocks = (long long)N * p.tilesY * p.tilesX;
     if (blocks >= (1ll << 31)) return CPR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(stem_pool_f32_kernel, dim3((unsigned)blocks), dim3(512), 0, stream, p);
+    if (arg) hipLaunchKernelGGL(stem_pool_f32_kernel<true>, dim3((unsigned)blocks), dim3(512), 0, stream, p);
+    else hipLaunchKernelGGL(stem_pool_f32_kernel<false>, dim3((unsigned)blocks), dim3(512), 0, stream, p);
     CPR_LAUNCH_STATUS();
+}
+extern "C" int cpr_stem7x7s2_pool_f32(const float* in, const float* wgt, const float* scale, const float* bias, float* out, int N,
+                                      int H, int W, int layout, hipStream_t stream) {
+    return stem_pool_f32_launch(in, wgt, scale, bias, out, nullptr, N, H, W, layout, stream);
+}
+// the recording instance (training with a trainable stem): also arg (N, PH, PW, 64) uint8, the window position of each maximum
+extern "C" int cpr_stem7x7s2_pool_f32_rec(const float* in, const float* wgt, const float* scale, const float* bias, float* out,
+                                          unsigned char* arg, int N, int H, int W, int layout, hipStream_t stream) {
+    CPR_CHECK_ARG(arg);
+    return stem_pool_f32_launch(in, wgt, scale, bias, out, arg, N, H, W, layout, stream);
 }

@@ -594,13 +594,19 @@ def stem_weight_f32(weight):
     return w.reshape(64, 154).contiguous()
 
 
-def stem7x7s2_pool_f32(x, wpack, scale=None, bias=None, planar=None):
+def stem7x7s2_pool_f32(x, wpack, scale=None, bias=None, planar=None, record=False):
     """The whole ResNet stem in one kernel, exact fp32: x (N,H,W,4) NHWC4 or the (N,3,H,W) network input -> (N,PH,PW,64) =
-    maxpool3x3s2(ReLU(conv7x7/2(x) * scale + bias))."""
+    maxpool3x3s2(ReLU(conv7x7/2(x) * scale + bias)).  record: the recording instance -> (out, arg), arg (N,PH,PW,64) uint8 = the
+    window position 0..8 of each maximum (first of ties), 255 where the pooled value is 0 (stem_pool_bwd's input)."""
     N, H, W, layout = _stem_input(_check(x), planar)
     assert wpack.dtype == torch.float32 and tuple(wpack.shape) == (64, 154)
     OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     out = torch.empty((N, (OH - 1) // 2 + 1, (OW - 1) // 2 + 1, 64), device=x.device, dtype=torch.float32)
+    if record:
+        arg = torch.empty(tuple(out.shape), device=x.device, dtype=torch.uint8)
+        _lib.call('cpr_stem7x7s2_pool_f32_rec', _ptr(x), _ptr(wpack), _ptr(scale), _ptr(bias), _ptr(out), _ptr(arg), N, H, W, layout,
+                  _stream())
+        return out, arg
     _lib.call('cpr_stem7x7s2_pool_f32', _ptr(x), _ptr(wpack), _ptr(scale), _ptr(bias), _ptr(out), N, H, W, layout, _stream())
     return out
 
@@ -642,21 +648,63 @@ def stem7x7s2_bf16(x, wpack, scale=None, bias=None, relu=True, planar=None):
     return out
 
 
-def stem7x7s2_pool_bf16(x, wpack, scale=None, bias=None, planar=None):
+def stem7x7s2_pool_bf16(x, wpack, scale=None, bias=None, planar=None, record=False):
     """stem7x7s2_bf16 (with ReLU) + maxpool3x3s2 in one kernel: x (N,H,W,4) or (N,3,H,W) fp32 -> (N,PH,PW,64) bf16; same bits as
-    the pair."""
+    the pair.  record: -> (out, arg), the argmax byte map of the bf16 values (see stem7x7s2_pool_f32)."""
     N, H, W, layout = _stem_input(_check(x), planar)
     assert wpack.dtype == torch.bfloat16 and tuple(wpack.shape) == (64, 224)
     OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     out = torch.empty((N, (OH - 1) // 2 + 1, (OW - 1) // 2 + 1, 64), device=x.device, dtype=torch.bfloat16)
+    if record:
+        arg = torch.empty(tuple(out.shape), device=x.device, dtype=torch.uint8)
+        _lib.call('cpr_stem7x7s2_pool_bf16_rec', _ptr(x), _ptr(wpack), _ptr(scale), _ptr(bias), _ptr(out), _ptr(arg), N, H, W, layout,
+                  _stream())
+        return out, arg
     _lib.call('cpr_stem7x7s2_pool_bf16', _ptr(x), _ptr(wpack), _ptr(scale), _ptr(bias), _ptr(out), N, H, W, layout, _stream())
     return out
 
 
-def maxpool3x3s2(x):
+def maxpool3x3s2(x, record=False):
+    """record: -> (out, arg), arg (N,PH,PW,C) uint8 = the window position 0..8 of each maximum (first of ties, out-of-map positions
+    never win), 255 where the maximum is 0 -- x is a ReLU output there (the stem)."""
     N, H, W, C = _check(x, ACT).shape
     out = torch.empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), device=x.device, dtype=x.dtype)
+    if record:
+        arg = torch.empty(tuple(out.shape), device=x.device, dtype=torch.uint8)
+        _lib.call('cpr_maxpool3x3s2' + _sfx(x) + '_rec', _ptr(x), _ptr(out), _ptr(arg), N, H, W, C, _stream())
+        return out, arg
     _lib.call('cpr_maxpool3x3s2' + _sfx(x), _ptr(x), _ptr(out), N, H, W, C, _stream())
+    return out
+
+
+def stem_pool_bwd(dp, arg, conv_hw):
+    """Backward of the stem's max-pool 3x3/2/1 and the ReLU before it: dp (N,PH,PW,64) fp32 (the pooled map's gradient) and the
+    recorded arg map (uint8, same shape) -> (dy (N,OH,OW,64) fp32 = the gradient at the BatchNorm output, TilePartials of its column
+    sums).  conv_hw = (OH, OW), the conv map's size.  Each conv pixel sums the windows that chose it in a fixed order (pooled row,
+    then pooled column, ascending); exact zeros where none did."""
+    N, PH, PW, C = _check(dp).shape
+    OH, OW = conv_hw
+    assert C == 64 and (PH, PW) == ((OH - 1) // 2 + 1, (OW - 1) // 2 + 1), (tuple(dp.shape), conv_hw)
+    assert _check(arg, torch.uint8).shape == dp.shape, (tuple(arg.shape), tuple(dp.shape))
+    M = N * OH * OW
+    tiles = _lib.call('cpr_stem_pool_bwd_blocks', M, positive=True)
+    dy = torch.empty((N, OH, OW, 64), device=dp.device, dtype=torch.float32)
+    part = torch.empty((tiles, 64, 2), device=dp.device, dtype=torch.float32)
+    _lib.call('cpr_stem_pool_bwd', _ptr(dp), _ptr(arg), _ptr(dy), _ptr(part), N, OH, OW, _stream())
+    return dy, TilePartials(part, tiles, 64)
+
+
+def stem_wgrad_f32(dy, x, planar=None, out=None):
+    """Weight gradient of the stem conv (7x7, stride 2, pad 3, 3 -> 64): dy (N,OH,OW,64) fp32 and the stem's input as the forward
+    read it -- NHWC4 (N,H,W,4) or the (N,3,H,W) planes -> (64,3,7,7) fp32 (written into ``out`` when given), exact fp32 on the matrix
+    pipe, the split-K partials summed in a fixed order."""
+    N, H, W, layout = _stem_input(_check(x), planar)
+    assert _check(dy).shape == (N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64), (tuple(dy.shape), tuple(x.shape))
+    if out is None:
+        out = torch.empty((64, 3, 7, 7), device=x.device, dtype=torch.float32)
+    assert _check(out).shape == (64, 3, 7, 7), tuple(out.shape)
+    ws = torch.empty((_lib.call('cpr_stem_wgrad_f32_workspace', N, H, W, positive=True),), device=x.device, dtype=torch.float32)
+    _lib.call('cpr_stem_wgrad_f32', _ptr(dy), _ptr(x), _ptr(out), _ptr(ws), N, H, W, layout, _stream())
     return out
 
 

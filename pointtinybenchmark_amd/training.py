@@ -345,6 +345,16 @@ class BackwardEngine:
         assert tape, 'a stage segment is only built for trainable stages'
         return out, tape
 
+    def forward_stem(self, img):
+        """-> (the pooled stem map, its record) for a trainable stem."""
+        tape = []
+        out = self.model.backbone.stem(img, tape)
+        assert tape and tape[0].get('stem'), 'a stem segment is only built for a trainable stem'
+        return out, tape[0]
+
+    def backward_stem(self, rec, dout):
+        self._backward_stem(self.model.backbone, rec, dout)
+
     def backward_stage(self, tape, dout, need_in):
         cache = self.model.backbone._cache
         dx = dout
@@ -743,7 +753,8 @@ class BackwardEngine:
         c = bb._cache
         dx = None            # gradient flowing down from the block above
         cur_stage = None
-        for idx in range(len(tape) - 1, -1, -1):
+        stem = tape[0] if tape and tape[0].get('stem') else None      # a trainable stem: layer1's first block hands it its input gradient
+        for idx in range(len(tape) - 1, 0 if stem is not None else -1, -1):
             rec = tape[idx]
             blk, stage = rec['block'], rec['stage']
             if stage != cur_stage:       # entering a stage from above: its output also feeds an FPN lateral
@@ -757,6 +768,44 @@ class BackwardEngine:
             dx = self._block_backward(c, blk, rec, dx, need_dx,
                                       mask_in=need_dx and blk.downsample is None and tape[idx - 1]['stage'] == stage)
         self._wide = {}      # nothing below the lowest trainable block reads a widened copy
+        if stem is not None:
+            self._backward_stem(bb, stem, dx)
+
+    def _backward_stem(self, bb, rec, dp):
+        """The standard stem (conv1 7x7/2 -> bn1 -> ReLU -> max-pool 3x3/2) given dp = d(pooled map), fp32 (csrc/stem_bwd.hip):
+        stem_pool_bwd takes it through the pool and the ReLU with the recorded byte map -> dy at the BatchNorm output.  Eval-mode bn1:
+        stem_wgrad_f32(dy) against the folded weight, then bn_fold_bwd -> dW = s*Gw, dgamma, dbeta (the convention of every folded BN
+        here).  Batch statistics: the BatchNorm backward on the recorded conv map -> dconv, then stem_wgrad_f32(dconv).  The weight
+        gradient reads the image as the forward read it (planes or NHWC4) and runs on the side stream; the mixed-precision step feeds
+        the same fp32 kernels (its byte map is the bf16 stem kernel's)."""
+        c1, bn = bb.conv1, bb.bn1
+        w = c1.weight
+        # any subset of (conv1.weight, bn1.weight, bn1.bias) may train: each gradient is written only where its parameter trains
+        dg_out = self._g(bn.weight) if bn.weight.requires_grad else None
+        db_out = self._g(bn.bias) if bn.bias.requires_grad else None
+        dy, part = ops.stem_pool_bwd(dp, rec['arg'], rec['conv_hw'])
+        x, planar = rec['x'], rec['planar']
+        if rec.get('batch_stats'):
+            st = rec['stats']
+            dconv, _, _ = ops.bn_train_bwd(dy, rec['y'], st.cmean, st.rstd, bn.weight, center=st.center, out_dgamma=dg_out,
+                                           out_dbeta=db_out)
+            if w.requires_grad:
+                self._param_side(lambda: ops.stem_wgrad_f32(dconv, x, planar=planar, out=self._g(w)), dconv, x)
+        else:
+            cache = bb._cache
+            scale, _ = folded_bn(cache, bn)
+            inv_sigma = cache.get(('bn_is', id(bn)), [bn.running_var],
+                                  lambda: ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, True)[2])
+
+            def param_grads():
+                # dgamma = inv_sigma * (sum(Gw * W) - mean * colsum): it needs Gw even when conv1 itself is frozen (then Gw goes to
+                # a scratch tensor -- the same kernels, so bn1's gradients are the same bits either way)
+                gw = self._g(w) if w.requires_grad else torch.empty(tuple(w.shape), device=dy.device, dtype=torch.float32)
+                ops.stem_wgrad_f32(dy, x, planar=planar, out=gw)
+                ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, part, want_affine=False, out_dgamma=dg_out,
+                                out_dbeta=db_out)
+            self._param_side(param_grads, dy, part, x)
+        self._done([p for p in (w, bn.weight, bn.bias) if p.requires_grad][-1])
 
     def _reads_bf16_only(self, conv, x, has_add, need_dx):
         """True when the backward rule of ``conv`` (input map x) reads nothing but the bf16 rounding of its output gradient: both of
@@ -999,7 +1048,9 @@ class CprTrainer(BackwardEngine):
         order = self._backward_order()
         seen = {id(p) for p in order}
         missing = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in seen]
-        assert not missing, 'trainable parameters without a backward rule: %s' % missing[:8]
+        assert not missing, 'trainable parameters without a backward rule: %s%s' % (
+            missing[:8], ''.join(' (%s)' % model.backbone.stem_train_reason() for n in missing[:1] if n.startswith('backbone.conv1.') or
+                                 n.startswith('backbone.bn1.')))
         self.params = order
         dev = order[0].device
         n = sum(p.numel() for p in order)
@@ -1215,7 +1266,9 @@ class CprTrainer(BackwardEngine):
                 add(blk.conv2.weight, blk.bn2.weight, blk.bn2.bias, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
                 if blk.downsample is not None:
                     add(blk.downsample[0].weight, blk.downsample[1].weight, blk.downsample[1].bias)
-        return out      # a trainable stem (frozen_stages < 0) has no backward rule and trips the constructor's check
+        if bb.stem_train_reason() is None:          # frozen_stages < 0: the stem's gradients complete last
+            add(bb.conv1.weight, bb.bn1.weight, bb.bn1.bias)
+        return out      # (a trainable non-standard stem has no backward rule and trips the constructor's check)
 
     @staticmethod
     def _head_param_order(head, add):
