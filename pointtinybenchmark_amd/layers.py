@@ -4,32 +4,107 @@ nn.Conv2d / nn.BatchNorm2d / nn.GroupNorm objects are used ONLY as parameter hol
 keys match the reference checkpoint layout; their ``forward`` is never called -- all
 compute goes through ``ops`` (HIP kernels)."""
 import os
+import struct
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops
 
 
 _WEIGHT_EPOCH = [0]
-_STALE_PACKS = __import__('os').environ.get('CPR_EXPERIMENT_STALE_PACKS', '0') == '1'
 
 
 def bump_weight_epoch():
     """Called by the native optimizer: its kernels update parameters through raw pointers, which torch's version counter
     does not see."""
-    if _STALE_PACKS:       # measurement only (CPR_EXPERIMENT_STALE_PACKS=1: WRONG results): what the per-step re-packs and re-folds cost
-        return
     _WEIGHT_EPOCH[0] += 1
+
+
+# CPR_REFRESH_IN_PLACE=0: every fold / pack lapses with the weight epoch and is rebuilt lazily (rounds 3-5; A/B switch)
+REFRESH_IN_PLACE = [os.environ.get('CPR_REFRESH_IN_PLACE', '1') != '0']
+
+_FOLDS, _PACKS16, _PACKS32 = 'cpr_bn_fold_multi', 'cpr_pack_weights_bf16_multi', 'cpr_pack_weights_multi'
+
+
+class FoldJob:
+    """Recomputes a folded BatchNorm's (scale, shift) in place: one 64-byte FoldJob row of cpr_bn_fold_multi (csrc/pack.hip)."""
+    multi = _FOLDS
+    fold = None
+    _ROW = struct.Struct('<7Qif')
+
+    def __init__(self, bn, value):
+        self.bn, self.value, self.C = bn, value, bn.weight.numel()
+        self._tensors = (bn.weight, bn.bias, bn.running_mean, bn.running_var) + tuple(value)
+
+    def ptrs(self):
+        """The device pointers of this job's row: gamma, beta, mean, var, scale, shift."""
+        return tuple(map(torch.Tensor.data_ptr, self._tensors))
+
+    def row(self, ptrs, extent):
+        """-> (this job's table row, the launch extent with it: the widest channel count)."""
+        return self._ROW.pack(*ptrs, 0, self.C, self.bn.eps), max(extent, self.C)
+
+
+class PackJob:
+    """Re-packs ``weight`` into the PackedConv ``value`` in place: one 64-byte row of cpr_pack_weights_bf16_multi (csrc/pack.hip
+    PackJob: the bf16 [rows][K] image and the fragment image) or of cpr_pack_weights_multi (Pack32Job: the fp32 [rows][Kpad] image,
+    after which the Winograd images are transformed again).  transpose: a data-gradient pack; ``fold``: the FoldJob whose scale it
+    multiplies in."""
+    _ROW16, _ROW32 = struct.Struct('<4Q8i'), struct.Struct('<3Q10i')
+
+    def __init__(self, weight, value, transpose, fold):
+        self.weight, self.value, self.transpose, self.fold = weight, value, transpose, fold
+        self.shape = O, I, KH, KW = weight.shape
+        rows, cols = (I, O) if transpose else (O, I)
+        bf16 = value.dtype == torch.bfloat16
+        self.multi = _PACKS16 if bf16 else _PACKS32
+        self.nblocks = max(1, min(64, (rows * (KH * KW * cols // 2 if bf16 else value.Kpad) + 255) // 256))
+
+    def ptrs(self):
+        """The device pointers of this job's row: weight, scale, pack, fragment image (built on first use, frag_image)."""
+        pc = self.value
+        return (self.weight.data_ptr(), 0 if self.fold is None else self.fold.value[0].data_ptr(), pc.w.data_ptr(),
+                0 if pc.wfrag is None else pc.wfrag.data_ptr())
+
+    def row(self, ptrs, block0):
+        """-> (this job's table row, the launch extent with it: the blocks of the jobs so far, this job's start at block0)."""
+        pc, nb = self.value, self.nblocks
+        if self.multi is _PACKS16:
+            return self._ROW16.pack(*ptrs, *self.shape, self.transpose, block0, nb, 0), block0 + nb
+        return self._ROW32.pack(*ptrs[:3], nb, 0, *self.shape, pc.Cin, pc.Kpad, self.transpose, block0), block0 + nb
+
+    def refresh_images(self, stream):
+        """The Winograd images of a refreshed fp32 pack: G g G^T again, in place (one launch each)."""
+        pc = self.value
+        for img, fn in ((pc.wino, 'cpr_wino_pack_weights'), (pc.wino32, 'cpr_wino32_pack_weights')):
+            if img is not None:
+                _lib.call(fn, pc.w.data_ptr(), img.data_ptr(), pc.Cin, pc.Cout, pc.Kpad, stream)
+
+
+def _pack_job(pc, weight, transpose=0, fold=None):
+    """The PackJob of a pack that a pack kernel built from an fp32 contiguous device weight; None for anything else (the strided
+    layers' PhasedDgrad, the torch-built bf16 packs of CPR_PACK_BF16_KERNEL=0): that entry lapses with the weight epoch."""
+    if isinstance(pc, ops.PackedConv) and weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous() and \
+            (pc.dtype == torch.float32 or ops.PACK_BF16_KERNEL[0]):
+        return PackJob(weight, pc, transpose, fold)
+    return None
+
+
+class _Entry:
+    __slots__ = ('tensors', 'ver', 'val', 'ready')
+
+    def __init__(self, tensors, ver, val, ready):
+        self.tensors, self.ver, self.val, self.ready = tensors, ver, val, ready
 
 
 class _PackCache:
     """Repacked weights / folded norms, rebuilt when the source parameter is modified in place."""
 
     def __init__(self):
-        self._d = {}
-        self._jobs = {}          # key -> (tensors, job): entries the native trainer refreshes IN PLACE after its optimizer step
-        self._tables = None      # device job tables of refresh_all (rebuilt when a job is registered or a pointer moved)
+        self._d = {}             # key -> _Entry
+        self._jobs = {}          # key -> FoldJob | PackJob of that key's current value: refresh_all recomputes it IN PLACE
+        self._tables = None      # (row pointers, launches) of refresh_all's device job tables: None when a job came or went
 
     @staticmethod
     def _ver(tensors):
@@ -39,158 +114,70 @@ class _PackCache:
         return ver
 
     def get(self, key, tensors, make, refresh=None):
-        """refresh (optional): val -> job, how the native trainer re-computes ``val`` IN PLACE after an optimizer step instead of
-        letting the entry lapse (refresh_all): ('fold', bn, scale | None, shift | None, inv | None) or
-        ('pack' | 'pack32', weight, key of the fold entry whose scale is multiplied in | None, packed_conv, transpose) (bf16 / fp32 pack)."""
+        """refresh (optional): val -> FoldJob | PackJob | None, how refresh_all recomputes ``val`` in place after the native trainer's
+        optimizer step instead of letting the entry lapse.  A rebuild drops the key's previous job."""
         ver = self._ver(tensors)
         hit = self._d.get(key)
-        if hit is not None and hit[0] == ver:
-            self._order_behind(hit)
-            return hit[1]
+        if hit is not None and hit.ver == ver:
+            hit.ready = ops.wait_ready(hit.ready)
+            return hit.val
         val = make()
-        if refresh is not None and REFRESH_IN_PLACE[0]:
-            job = refresh(val)
-            if job is not None:
-                self._jobs[key] = (list(tensors), job)
-                self._tables = None
-        elif key in self._jobs:
-            del self._jobs[key]
+        job = refresh(val) if refresh is not None else None
+        if self._jobs.pop(key, None) is not None or job is not None:
             self._tables = None
+        if job is not None:
+            self._jobs[key] = job
         # whatever make() enqueued (pack kernels, torch ops building a bf16 pack / a folded norm / a bias vector) ran on the
         # CURRENT stream: a reader on another stream (sub-batches of CPR_STREAMS > 1, the trainer's side stream) must order
         # itself behind it -- the event lives with the entry until it has completed
-        ev = None
-        if torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
-            ev = torch.cuda.Event()
-            ev.record()
-        self._d[key] = [ver, val, ev, torch.cuda.current_stream().cuda_stream if ev is not None else None]
+        self._d[key] = _Entry(list(tensors), ver, val, ops.record_ready())
         return val
+
+    def _live(self):
+        """(entry, job) of every job refresh_all recomputes: its value is still its entry's, and a pack linked to a fold only
+        goes with that very fold job (a fold rebuilt since, or left without a job, lets the pack lapse and rebuild from it)."""
+        if not REFRESH_IN_PLACE[0]:
+            return []
+        live = [(self._d[k], j) for k, j in self._jobs.items() if self._d[k].val is j.value]
+        jobs = {j for _, j in live}
+        return [(e, j) for e, j in live if j.fold is None or j.fold in jobs]
 
     def refresh_all(self):
         """Called by the native trainer right after its optimizer step (the parameters changed through raw pointers, the weight epoch
-        was bumped): every registered fold / bf16 pack is recomputed in place by ONE multi-tensor launch per kind (csrc/pack.hip,
-        cpr_bn_fold_multi / cpr_pack_weights_bf16_multi: bit for bit the single-tensor kernels) and its entry re-stamped with the
-        current version, instead of ~320 lazy rebuilds -- launches, allocations and Python -- spread over the next step (4.3 of the
-        37 ms of a configs[4] step, profiles/round6_stale_packs_ab.txt).  Entries without a job lapse and rebuild as before."""
-        import numpy as np
-        from . import _lib
-        live = []
-        for k, (t, j) in self._jobs.items():
-            if k not in self._d:
-                continue
-            if j[0] in ('pack', 'pack32') and j[2] is not None:
-                # a data-gradient pack multiplies a folded-BN scale in: only while that fold is refreshed in place too (else this
-                # entry lapses with the epoch like any other and is rebuilt from the new fold)
-                if j[2] not in self._jobs or j[2] not in self._d:
-                    continue
-            live.append((k, t, j))
+        was bumped): every live job is recomputed in place by ONE multi-tensor launch per kind -- folds first, the data-gradient
+        packs multiply the refreshed scales in (csrc/pack.hip: bit for bit the single-tensor kernels) -- and its entry re-stamped with
+        the current version, instead of ~320 lazy rebuilds -- launches, allocations and Python -- spread over the next step (4.3 of
+        the 37 ms of a configs[4] step, profiles/round6_stale_packs_ab.txt).  Entries without a job lapse and rebuild as before."""
+        live = self._live()
         if not live:
             return
-
-        def scale_of(j):
-            return None if j[2] is None else self._d[j[2]][1][0]
-        ptrs = tuple(x.data_ptr() for _, t, _ in live for x in t) + \
-            tuple((0 if scale_of(j) is None else scale_of(j).data_ptr(), j[3].w.data_ptr(),
-                   0 if getattr(j[3], 'wfrag', None) is None else j[3].wfrag.data_ptr()) for _, _, j in live if j[0] in ('pack', 'pack32'))
-        if self._tables is None or self._tables[0] != ptrs:
-            folds, packs, packs32, blocks, blocks32, max_c = [], [], [], 0, 0, 1
-            for k, t, j in live:
-                if j[0] == 'fold':
-                    _, bn, sc, sh, inv = j
-                    C = bn.weight.numel()
-                    max_c = max(max_c, C)
-                    folds.append((bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                  0 if sc is None else sc.data_ptr(), 0 if sh is None else sh.data_ptr(),
-                                  0 if inv is None else inv.data_ptr(), C, float(bn.eps)))
-            # folds first: the data-gradient packs multiply the refreshed scale in
-            for k, t, j in live:
-                if j[0] == 'pack':
-                    _, w, _, pc, transpose = j
-                    sc = scale_of(j)
-                    O, I, KH, KW = w.shape
-                    rows, cols = (I, O) if transpose else (O, I)
-                    nb = max(1, min(64, (rows * (KH * KW * cols // 2) + 255) // 256))
-                    packs.append((w.data_ptr(), 0 if sc is None else sc.data_ptr(), pc.w.data_ptr(),
-                                  0 if pc.wfrag is None else pc.wfrag.data_ptr(), O, I, KH, KW, int(transpose), blocks, nb, 0))
-                    blocks += nb
-                elif j[0] == 'pack32':          # the fp32 implicit-GEMM pack [rows][Kpad] (forward: colsp = padded Cin, dgrad: padded Cout)
-                    _, w, _, pc, transpose = j
-                    sc = scale_of(j)
-                    O, I, KH, KW = w.shape
-                    rows = I if transpose else O
-                    nb = max(1, min(64, (rows * pc.Kpad + 255) // 256))
-                    packs32.append((w.data_ptr(), 0 if sc is None else sc.data_ptr(), pc.w.data_ptr(), nb, 0,
-                                    O, I, KH, KW, pc.Cin, pc.Kpad, int(transpose), blocks32))
-                    blocks32 += nb
-            dev = live[0][1][0].device
-            fdt = np.dtype([('p', '<u8', (7,)), ('C', '<i4'), ('eps', '<f4')])
-            pdt = np.dtype([('p', '<u8', (4,)), ('i', '<i4', (8,))])
-            p32dt = np.dtype([('p', '<u8', (3,)), ('i', '<i4', (10,))])
-            ft = pt = p32t = None
-            if packs32:
-                qa = np.zeros((len(packs32),), dtype=p32dt)
-                for i, q in enumerate(packs32):
-                    qa[i] = (q[:3], q[3:])
-                p32t = torch.from_numpy(qa.view(np.uint8).reshape(-1).copy()).to(dev)
-            if folds:
-                fa = np.zeros((len(folds),), dtype=fdt)
-                for i, f in enumerate(folds):
-                    fa[i] = (f[:7], f[7], f[8])
-                ft = torch.from_numpy(fa.view(np.uint8).reshape(-1).copy()).to(dev)
-            if packs:
-                pa = np.zeros((len(packs),), dtype=pdt)
-                for i, q in enumerate(packs):
-                    pa[i] = (q[:4], q[4:])
-                pt = torch.from_numpy(pa.view(np.uint8).reshape(-1).copy()).to(dev)
-            self._tables = (ptrs, ft, len(folds), max_c, pt, len(packs), blocks, p32t, len(packs32), blocks32)
-        _, ft, nf, max_c, pt, npk, blocks, p32t, np32, blocks32 = self._tables
+        ptrs = [j.ptrs() for _, j in live]
+        if self._tables is None or self._tables[0] != ptrs:       # the job set changed or a pointer moved
+            rows = {_FOLDS: [], _PACKS16: [], _PACKS32: []}
+            extent = dict.fromkeys(rows, 0)
+            for (_, j), p in zip(live, ptrs):
+                row, extent[j.multi] = j.row(p, extent[j.multi])
+                rows[j.multi].append(row)
+            dev = live[0][0].tensors[0].device
+            self._tables = ptrs, [(fn, torch.frombuffer(bytearray(b''.join(r)), dtype=torch.uint8).to(dev), len(r), extent[fn])
+                                  for fn, r in rows.items() if r]
         stream = torch.cuda.current_stream().cuda_stream
-        if ft is not None:
-            _lib.call('cpr_bn_fold_multi', ft.data_ptr(), nf, max_c, stream)
-        if pt is not None:
-            _lib.call('cpr_pack_weights_bf16_multi', pt.data_ptr(), npk, blocks, stream)
-        if p32t is not None:
-            _lib.call('cpr_pack_weights_multi', p32t.data_ptr(), np32, blocks32, stream)
-            for k, t, j in live:        # the Winograd images of a refreshed fp32 pack: G g G^T again, in place (one launch each)
-                if j[0] == 'pack32':
-                    pc = j[3]
-                    for attr, fn in (('wino', 'cpr_wino_pack_weights'), ('wino32', 'cpr_wino32_pack_weights')):
-                        img = getattr(pc, attr, None)
-                        if img is not None:
-                            _lib.call(fn, pc.w.data_ptr(), img.data_ptr(), pc.Cin, pc.Cout, pc.Kpad, stream)
-        ev = torch.cuda.Event()
-        ev.record()
-        for k, t, j in live:
-            hit = self._d[k]
-            hit[0], hit[2], hit[3] = self._ver(t), ev, stream
-            if j[0] in ('pack', 'pack32'):
-                j[3].ready = ev
-
-    @staticmethod
-    def _order_behind(entry):
-        ev = entry[2]
-        if ev is None or torch.cuda.is_current_stream_capturing():     # (a capture starts after a synchronised warm-up)
-            return
-        if ev.query():
-            entry[2] = None
-        elif torch.cuda.current_stream().cuda_stream != entry[3]:
-            torch.cuda.current_stream().wait_event(ev)
-
-
-# CPR_REFRESH_IN_PLACE=0: every fold / pack lapses with the weight epoch and is rebuilt lazily (rounds 3-5; A/B switch)
-REFRESH_IN_PLACE = [__import__('os').environ.get('CPR_REFRESH_IN_PLACE', '1') != '0']
+        for fn, table, n, ext in self._tables[1]:
+            _lib.call(fn, table.data_ptr(), n, ext, stream)
+        for _, j in live:
+            if j.multi is _PACKS32:
+                j.refresh_images(stream)
+        ready = ops.record_ready()
+        for e, j in live:
+            e.ver, e.ready = self._ver(e.tensors), ready
+            if isinstance(j, PackJob):
+                j.value.ready = ready
 
 
 def packed_conv(cache, conv, dtype=torch.float32):
-    def job(pc):        # the bf16 pack kernel's outputs can be refreshed in place; the fp32 / Winograd packs lapse as before
-        if dtype == torch.bfloat16 and conv.weight.is_cuda and ops.PACK_BF16_KERNEL[0] and conv.weight.dtype == torch.float32 \
-                and conv.weight.is_contiguous():
-            return ('pack', conv.weight, None, pc, 0)
-        if dtype == torch.float32 and conv.weight.is_cuda and conv.weight.dtype == torch.float32 and conv.weight.is_contiguous():
-            return ('pack32', conv.weight, None, pc, 0)
-        return None
     return cache.get(('pc', id(conv), dtype), [conv.weight],
-                     lambda: ops.PackedConv(conv.weight, conv.stride[0], conv.padding[0], dtype), refresh=job)
+                     lambda: ops.PackedConv(conv.weight, conv.stride[0], conv.padding[0], dtype),
+                     lambda pc: _pack_job(pc, conv.weight))
 
 
 def folded_bn(cache, bn):
@@ -206,8 +193,36 @@ def folded_bn(cache, bn):
     def job(val):
         ok = bn.weight.is_cuda and all(t.dtype == torch.float32 and t.is_contiguous()
                                        for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var, val[0], val[1]))
-        return ('fold', bn, val[0], val[1], None) if ok else None
-    return cache.get(('bn', id(bn)), [bn.weight, bn.bias, bn.running_mean, bn.running_var], make, refresh=job)
+        return FoldJob(bn, val) if ok else None
+    return cache.get(('bn', id(bn)), [bn.weight, bn.bias, bn.running_mean, bn.running_var], make, job)
+
+
+def bn_inv_sigma(cache, bn):
+    """1 / sqrt(running_var + eps) of an eval-mode BatchNorm (the folded-BN parameter gradients, ops.bn_fold_bwd)."""
+    return cache.get(('bn_is', id(bn)), [bn.running_var],
+                     lambda: ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, True)[2])
+
+
+def dgrad_packed(cache, conv, bn=None, dtype=torch.float32):
+    """The packed weights of the data gradient of ``conv`` (ops.dgrad_pack; bf16 stride 1: PackedConv.for_dgrad_bf16) with the
+    folded scale of the eval-mode ``bn`` multiplied in -- or the raw weights (bn None: a batch-statistics layer)."""
+    w, stride, pad = conv.weight, conv.stride[0], conv.padding[0]
+    if bn is None:
+        return cache.get(('dgrad_raw', id(conv)), [w], lambda: ops.dgrad_pack(w, stride, pad), lambda pc: _pack_job(pc, w, 1))
+
+    def make():
+        scale, _ = folded_bn(cache, bn)
+        if dtype == torch.float32 or stride != 1:
+            return ops.dgrad_pack(w, stride, pad, scale=scale, dtype=dtype)
+        if ops.PACK_BF16_KERNEL[0]:
+            return ops.PackedConv.for_dgrad_bf16(w, pad, scale=scale)
+        wt = (w.detach() * scale[:, None, None, None]).flip(2, 3).permute(1, 0, 2, 3)
+        return ops.PackedConv(wt, 1, conv.kernel_size[0] - 1 - pad, torch.bfloat16)
+
+    def job(pc):        # linked to the fold job of the scale make() multiplied in
+        fold = cache._jobs.get(('bn', id(bn)))
+        return None if fold is None else _pack_job(pc, w, 1, fold)
+    return cache.get(('dgrad', id(conv), dtype), [w, bn.weight, bn.running_var], make, job)
 
 
 class ConvModule(nn.Module):

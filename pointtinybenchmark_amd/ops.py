@@ -71,14 +71,12 @@ class PackedConv:
     wfrag = None    # bf16: the weights in MFMA-fragment order (frag_image), built on first use for Cout % 256 == 0
     wino = None     # transformed weights of the Winograd path, built on first use (conv3x3_wino)
     wino32 = None   # the same for the two-workgroups-per-CU kernel (csrc/conv_wino32.hip: chunks of 4 input channels)
-    ready = None    # event recorded behind the last pack kernel (weights / Winograd image); see pack_ready()
+    ready = None    # record_ready() behind the last pack kernel (weights / Winograd image); see pack_ready()
 
     def _packed(self):
         """A pack kernel was just enqueued on the current stream: consumers on OTHER streams (CPR_STREAMS > 1 sub-batches)
         must order themselves behind it."""
-        if torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
-            self.ready = torch.cuda.Event()
-            self.ready.record()
+        self.ready = record_ready()
 
     def __init__(self, weight, stride=1, padding=0, dtype=torch.float32):
         Cout, Cin, KH, KW = weight.shape
@@ -205,16 +203,35 @@ WINOGRAD = [os.environ.get('CPR_WINOGRAD', '1') != '0']
 WINO_MIN_FILL = 0.6      # useful share of the 16x16 regions (40x40 -> 0.69 runs Winograd, 20x20 -> 0.39 stays direct)
 
 
+def record_ready():
+    """(event, stream) recorded behind the work just enqueued on the current stream, for wait_ready; None without a device or
+    while the stream is being captured."""
+    if not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
+        return None
+    ev = torch.cuda.Event()
+    ev.record()
+    return ev, torch.cuda.current_stream().cuda_stream
+
+
+def wait_ready(ready):
+    """Order the current stream behind ``ready`` (record_ready) unless it is the producer's own stream.  Returns what the holder
+    keeps: None once the event has completed."""
+    if ready is None or torch.cuda.is_current_stream_capturing():      # (a capture starts after a synchronised warm-up)
+        return ready
+    ev, stream = ready
+    if ev.query():
+        return None
+    cur = torch.cuda.current_stream()
+    if cur.cuda_stream != stream:
+        cur.wait_event(ev)
+    return ready
+
+
 def pack_ready(pc):
     """Order the current stream behind the kernels that packed ``pc`` (they may have run on another stream: the first
-    sub-batch of a multi-stream forward packs, the others only read).  The event is dropped once it has completed."""
-    ev = pc.ready
-    if ev is None or torch.cuda.is_current_stream_capturing():      # (a capture starts after a synchronised warm-up)
-        return
-    if ev.query():
-        pc.ready = None
-    else:
-        torch.cuda.current_stream().wait_event(ev)
+    sub-batch of a multi-stream forward packs, the others only read)."""
+    if pc.ready is not None:
+        pc.ready = wait_ready(pc.ready)
 
 
 def wino_eligible(pc, H, W, dtype=torch.float32):

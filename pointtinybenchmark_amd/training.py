@@ -19,7 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .layers import bump_weight_epoch, folded_bn
+from .layers import _PackCache, bn_inv_sigma, bump_weight_epoch, dgrad_packed, folded_bn
 
 
 WINO_DGRAD = [os.environ.get('CPR_WINO_DGRAD', '1') == '1']     # A/B switch (tools): 3x3 data gradients as Winograd + a mask pass
@@ -794,8 +794,7 @@ class BackwardEngine:
         else:
             cache = bb._cache
             scale, _ = folded_bn(cache, bn)
-            inv_sigma = cache.get(('bn_is', id(bn)), [bn.running_var],
-                                  lambda: ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, True)[2])
+            inv_sigma = bn_inv_sigma(cache, bn)
 
             def param_grads():
                 # dgamma = inv_sigma * (sum(Gw * W) - mean * colsum): it needs Gw even when conv1 itself is frozen (then Gw goes to
@@ -834,8 +833,7 @@ class BackwardEngine:
         -- ReLU backward, bf16 rounding and column sums in its epilogue, no fp32 map, no streaming pass -- and returns
         (None, column-sum partials, gradient16).  g may be None when g16 is given and both gradients of this conv are bf16."""
         scale, _ = folded_bn(cache, bn)
-        inv_sigma = cache.get(('bn_is', id(bn)), [bn.running_var],
-                              lambda: ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, True)[2])
+        inv_sigma = bn_inv_sigma(cache, bn)
         w = conv.weight
         k = conv.kernel_size[0]
         # mixed precision: ONE bf16 copy of the gradient map feeds the bf16 weight gradient and the bf16 data gradient (round 6: the
@@ -879,13 +877,7 @@ class BackwardEngine:
             # mixed precision: the data gradient on the bf16 matrix pipe (a forward conv of the bf16-rounded gradient map with the
             # rotated, BN-scaled weights, fp32 out), the residual add, the ReLU mask (the bf16 recorded map as it is) and the column
             # sums as streaming passes over the (small) result
-            def pack16():
-                if ops.PACK_BF16_KERNEL[0]:
-                    return ops.PackedConv.for_dgrad_bf16(w, conv.padding[0], scale=scale)
-                wt = (w.detach() * scale[:, None, None, None]).flip(2, 3).permute(1, 0, 2, 3)
-                return ops.PackedConv(wt, 1, k - 1 - conv.padding[0], torch.bfloat16)
-            pc16 = cache.get(('dgrad16', id(conv)), [w, bn.weight, bn.running_var], pack16,
-                             refresh=(lambda pc: ('pack', w, ('bn', id(bn)), pc, 1)) if ops.PACK_BF16_KERNEL[0] else None)
+            pc16 = dgrad_packed(cache, conv, bn, torch.bfloat16)
             if MIXED_BF16['mask_mode'] and not need32 and mask is not None and add is None and want_colsum and want16 and \
                     mask.dtype == torch.bfloat16 and ops.conv2d_bf16_mask_slots(g16.shape, pc16) > 0:
                 dx16, part = ops.conv2d(g16, pc16, residual=mask, res_mask=True, colsum=True)
@@ -900,15 +892,11 @@ class BackwardEngine:
                 conv.padding[0] == k // 2 and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0 and ops._PHASED[0]:
             # mixed precision, the strided layers of a stage's first block (round 6): the four parity sub-convolutions of the phase-
             # decomposed data gradient on the bf16 pipe (fp32 out, scattered / summed in fp32 as before)
-            pt16 = cache.get(('dgrad16s2', id(conv)), [w, bn.weight, bn.running_var],
-                             lambda: ops.dgrad_pack(w, 2, conv.padding[0], scale=scale, dtype=torch.bfloat16))
+            pt16 = dgrad_packed(cache, conv, bn, torch.bfloat16)
             if g16 is None:
                 g16 = g.to(torch.bfloat16)
             return finish(pt16(g16, (x.shape[1], x.shape[2]), add=add))
-        pt = cache.get(('dgrad', id(conv)), [w, bn.weight, bn.running_var],
-                       lambda: ops.dgrad_pack(w, conv.stride[0], conv.padding[0], scale=scale),
-                       refresh=lambda q: ('pack32', w, ('bn', id(bn)), q, 1) if isinstance(q, ops.PackedConv) and
-                       q.dtype == torch.float32 and w.dtype == torch.float32 and w.is_contiguous() else None)
+        pt = dgrad_packed(cache, conv, bn)
         if WINO_DGRAD[0] and k == 3 and conv.stride[0] == 1 and add is None and \
                 (mask is not None or want_colsum) and ops.wino_eligible(pt, x.shape[1], x.shape[2], torch.float32):
             # a 3x3 stride-1 data gradient with a mask / column-sum epilogue would run the direct kernel (2.25x the multiplies of
@@ -985,10 +973,7 @@ class BackwardEngine:
             self._param_side(param_grads, dy, x)
         if not need_dx:
             return None
-        pt = cache.get(('dgrad_raw', id(conv)), [w], lambda: ops.dgrad_pack(w, conv.stride[0], conv.padding[0]),
-                       refresh=lambda q: ('pack32', w, None, q, 1) if isinstance(q, ops.PackedConv) and
-                       w.dtype == torch.float32 and w.is_contiguous() else None)
-        return ops.conv2d_dgrad(dy, pt, (x.shape[1], x.shape[2]), conv.stride[0], add=add)
+        return ops.conv2d_dgrad(dy, dgrad_packed(cache, conv), (x.shape[1], x.shape[2]), conv.stride[0], add=add)
 
     def _block_backward_batch_stats(self, cache, blk, rec, dout, need_dx):
         """A block recorded with batch-statistics BatchNorm (resnet._Block._run_batch_stats): same parameter order and ``_done``
@@ -1344,9 +1329,8 @@ class CprTrainer(BackwardEngine):
                           decoupled=o['type'] == 'AdamW')
         self.steps += 1
         bump_weight_epoch()
-        # the folds / bf16 packs the last step registered are recomputed in place now, in two launches, instead of lapsing (round 6)
+        # the folds / packs the last step registered are recomputed in place now, one launch per kind, instead of lapsing (round 6)
         if self._pack_caches is None:
-            from .layers import _PackCache
             self._pack_caches = [m._cache for m in self.model.modules() if isinstance(getattr(m, '_cache', None), _PackCache)]
         for c in self._pack_caches:
             c.refresh_all()

@@ -276,9 +276,9 @@ def test_mixed_precision_mask_mode_changes_only_the_column_sum_order():
 
 
 @pytest.mark.parametrize('mode', ['fp32', 'bf16'])
-def test_in_place_refresh_of_folds_and_packs_changes_no_bit(mode):
-    """Round 6: after its optimizer step the native trainer recomputes every BatchNorm fold and bf16 weight pack the last step used IN
-    PLACE with two multi-tensor launches (layers._PackCache.refresh_all, cpr_bn_fold_multi / cpr_pack_weights_bf16_multi) instead of
+def test_in_place_refresh_jobs_change_no_bit(mode):
+    """Round 6: after its optimizer step the native trainer recomputes every BatchNorm fold and weight pack the last step used IN
+    PLACE with one multi-tensor launch per kind (layers._PackCache.refresh_all: layers.FoldJob / PackJob rows) instead of
     letting ~320 cache entries lapse and rebuild one by one.  Four training steps with and without it (CPR_REFRESH_IN_PLACE) must give
     the same losses and the same parameters BIT for bit; and after the last step every refreshed buffer must equal a fresh
     single-tensor fold / pack of the current parameters."""
@@ -305,25 +305,25 @@ def test_in_place_refresh_of_folds_and_packs_changes_no_bit(mode):
             if inplace:
                 n_fold = n_pack = n_pack32 = 0
                 for c in tr._pack_caches:
-                    for key, (tensors, job) in c._jobs.items():
-                        val = c._d[key][1]
-                        if job[0] == 'fold':
-                            bn = job[1]
+                    for key, job in c._jobs.items():
+                        assert c._d[key].val is job.value, key
+                        if isinstance(job, layers.FoldJob):
+                            bn = job.bn
                             sc, sh, _ = ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-                            assert torch.equal(val[0], sc) and torch.equal(val[1], sh), key
+                            assert torch.equal(job.value[0], sc) and torch.equal(job.value[1], sh), key
                             n_fold += 1
-                        elif job[0] == 'pack32':
-                            _, w, skey, pc, transpose = job
-                            if transpose:
-                                fresh = ops.PackedConv.for_dgrad(w, pc.KH - 1 - pc.padding, c._d[skey][1][0])
+                            continue
+                        w, pc, scale = job.weight, job.value, None if job.fold is None else job.fold.value[0]
+                        if pc.dtype == torch.float32:
+                            if job.transpose:
+                                fresh = ops.PackedConv.for_dgrad(w, pc.KH - 1 - pc.padding, scale)
                             else:
                                 fresh = ops.PackedConv(w, pc.stride, pc.padding, torch.float32)
                             assert torch.equal(fresh.w, pc.w), key
                             n_pack32 += 1
                         else:
-                            _, w, skey, pc, transpose = job
-                            if transpose:
-                                fresh = ops.PackedConv.for_dgrad_bf16(w, pc.KH - 1 - pc.padding, scale=c._d[skey][1][0])
+                            if job.transpose:
+                                fresh = ops.PackedConv.for_dgrad_bf16(w, pc.KH - 1 - pc.padding, scale=scale)
                             else:
                                 fresh = ops.PackedConv(w, pc.stride, pc.padding, torch.bfloat16)
                             assert torch.equal(fresh.w, pc.w), key
