@@ -6,7 +6,8 @@
  *   - all pointers are DEVICE pointers unless marked [host]; the caller allocates every output and workspace
  *     (no hidden allocation, no ownership transfer); the library keeps NO mutable state: every call is a pure function of
  *     its arguments and may be issued from any host thread on any stream (what a launch did -- e.g. which template instance
- *     the tile heuristic picked -- comes back through [host] out-parameters, never through a "last call" global).
+ *     the tile heuristic picked -- comes back through [host] out-parameters, never through a "last call" global); it reads no
+ *     environment variable either.
  *     The only exception is the measurement build (-DCPR_BENCH_HOOKS, libcprhip_bench.so, see the end of this file)
  *   - work is enqueued on `stream` (a hipStream_t passed as void*); no host synchronisation inside
  *   - activations are NHWC fp32; index outputs are int64 (torch long) where the reference returns long
@@ -64,23 +65,16 @@ int cpr_conv2d_dual_fwd(const float* in, const float* wgt, const float* in2, con
 int cpr_conv1x1_stream_fwd(const float* in, const float* wgt, float* out, const float* scale, const float* bias,
                            const float* residual, long long M, int Cin, int Cout, int flags, void* stream);
 
-/* Weight gradient of a stride-1 conv (k = 1, or k = 3 with padding 1) on the bf16 matrix cores -- the mixed-precision training
- * step (reference analogue: torch autograd under mmcv's Fp16OptimizerHook, T/mmdet/apis/train.py:116-119).  dy (N,H,W,Cout) and
- * x (N,H,W,Cin) fp32 or bf16 (dy_bf16, x_bf16; fp32 maps are rounded on the way in), grad [Cout][Cin][k][k] fp32 (accumulate: +=), Cin % 256 == 0, Cout % 64 == 0.  Both maps
- * are rewritten channel-major over a zero-bordered pixel axis (bf16), every tap is an NT GEMM on the LDS-DMA kernel split over
- * the pixels, the partials are summed in fp32 (csrc/conv_wgrad_bf16.hip).  ws: cpr_conv_wgrad_bf16_workspace(...) x 256 bytes
- * (the query returns units of 256 bytes; negative = unsupported shape). */
-int cpr_conv_wgrad_bf16_workspace(int N, int H, int W, int Cin, int Cout, int k);
-int cpr_conv_wgrad_bf16(const void* dy, int dy_bf16, const void* x, int x_bf16, float* grad, void* ws, int N, int H, int W, int Cin,
-                        int Cout, int k, int accumulate, void* stream);
-/* Which kernel cpr_conv_wgrad_bf16 takes when both maps are bf16: 0 = channel-major rewrites of both maps + NT GEMM (rounds 3-6 default),
- * 1 = the pixel-major kernel of csrc/conv_wgrad_bf16_tn.hip (round 6: reads the NHWC maps as they are through ds_read_b64_tr_b16, no
- * rewrites).  Initial value from CPR_WGRAD_TN; on < 0 only queries.  Returns the previous value. */
-int cpr_wgrad_bf16_set_tn(int on);
-/* cpr_conv_wgrad_bf16 with a stride (1 or 2; dy is (N,OH,OW,Cout), OH = (H + 2 (k/2) - k) / stride + 1) -- the strided 3x3 / projection
- * layers of a stage's first block.  Stride 2, Cin % 256 != 0 (Cin % 64 == 0 suffices) and 1x1 layers below 256 couts are the pixel-major
- * kernel's alone: both maps bf16, else CPR_ERR_UNSUPPORTED.  Workspace: cpr_conv_wgrad_bf16_workspace_s (units of 256 bytes). */
-int cpr_conv_wgrad_bf16_workspace_s(int N, int H, int W, int Cin, int Cout, int k, int stride);
+/* Weight gradient of a conv (k = 1, or k = 3 with padding 1; stride 1 or 2) on the bf16 matrix cores -- the mixed-precision training
+ * step (reference analogue: torch autograd under mmcv's Fp16OptimizerHook, T/mmdet/apis/train.py:116-119).  dy (N,OH,OW,Cout),
+ * OH = (H + 2 (k/2) - k) / stride + 1, and x (N,H,W,Cin) fp32 or bf16 (dy_bf16, x_bf16; fp32 maps are rounded on the way in), grad
+ * [Cout][Cin][k][k] fp32 (accumulate: +=), Cin % 64 == 0, Cout % 64 == 0.  Both maps bf16: the pixel-major kernel of
+ * csrc/conv_wgrad_bf16_tn.hip (reads the NHWC maps as they are through ds_read_b64_tr_b16).  Otherwise -- or for a shape beyond that
+ * kernel's index range -- both maps are rewritten channel-major over a zero-bordered pixel axis (bf16) and every tap is an NT GEMM on the
+ * LDS-DMA kernel (stride 1, Cin % 256 == 0 only); the partials of either path are split over the pixels and summed in fp32
+ * (csrc/conv_wgrad_bf16.hip).  ws: cpr_conv_wgrad_bf16_workspace_s(...) x 256 bytes; the query returns units of 256 bytes, or
+ * CPR_ERR_UNSUPPORTED exactly where cpr_conv_wgrad_bf16_s is for maps of those dtypes. */
+int cpr_conv_wgrad_bf16_workspace_s(int N, int H, int W, int Cin, int Cout, int k, int stride, int dy_bf16, int x_bf16);
 int cpr_conv_wgrad_bf16_s(const void* dy, int dy_bf16, const void* x, int x_bf16, float* grad, void* ws, int N, int H, int W, int Cin,
                           int Cout, int k, int stride, int accumulate, void* stream);
 

@@ -8,17 +8,12 @@ non-frozen stages are in training mode (the reference's ``train()``) and normali
 normalise / residual / ReLU pass (csrc/bn_train.hip), running statistics updated on the device.
 The backward of the trainable stages -- and of a trainable stem (frozen_stages=-1) -- is driven by training.CprTrainer from the records
 of ``forward(tape=)``."""
-import os
-
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..layers import _PackCache, folded_bn, packed_conv
 from ..registry import BACKBONES
-
-
-FUSE_SHORTCUT = [os.environ.get('CPR_FUSE_SHORTCUT', '1') == '1']   # A/B switch (tests, tools)
 
 
 def _bn_not_mixed():
@@ -64,8 +59,7 @@ class _Block(nn.Module):
         dt = x.dtype
         # forward-only fp32 bottleneck with a projection shortcut: the shortcut GEMM rides in conv3's launch (bit-identical,
         # ops.conv2d_dual); the training step keeps the two launches (its backward walks the recorded maps)
-        fuse_shortcut = FUSE_SHORTCUT[0] and self.downsample is not None and save is None and self.kind == 'bottleneck' and \
-            dt == torch.float32
+        fuse_shortcut = self.downsample is not None and save is None and self.kind == 'bottleneck' and dt == torch.float32
         if self.downsample is not None and not fuse_shortcut:
             s, b = folded_bn(cache, self.downsample[1])
             identity = ops.conv2d(x, packed_conv(cache, self.downsample[0], x.dtype), scale=s, bias=b)
@@ -124,9 +118,9 @@ class _Block(nn.Module):
         return out
 
 
-F32_STEM = [os.environ.get('CPR_F32_STEM', '1') != '0']       # 0: stem conv on the implicit-GEMM kernel + separate max-pool (A/B, tests)
-BF16_STEM_POOL = [os.environ.get('CPR_BF16_STEM_POOL', '1') != '0']   # 0: stem conv and max-pool as two kernels
-BF16_STEM = [os.environ.get('CPR_BF16_STEM', '1') != '0']     # 0: the bf16 mode keeps its stem on the fp32 kernel (A/B, tests)
+F32_STEM = [True]         # False: stem conv on the implicit-GEMM kernel + separate max-pool (tests)
+BF16_STEM_POOL = [True]   # False: stem conv and max-pool as two kernels
+BF16_STEM = [True]        # False: the bf16 mode keeps its stem on the fp32 kernel (tests)
 
 
 @BACKBONES.register_module()

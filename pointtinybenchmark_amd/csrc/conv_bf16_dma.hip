@@ -24,7 +24,6 @@
 // cannot fill the chip with big tiles, and -- in the 256 x 256 instance -- an interleaved cout layout that lets every lane store
 // adjacent couts (dma_epilogue_pairs).  Which layer takes which instance: bf16_dma_shape in conv_mfma_bf16.hip.
 #include "conv_bf16_dma.h"
-#include <cstdlib>
 
 // BD = true (round 5, <4, 2, 4, true> only): the WEIGHT operand goes global -> VGPR directly, only the activations go through LDS.
 // The host hands over a second image of the weights in fragment order -- wfrag[g = cout / 64][ks = k / 16][j][lane][8]: lane
@@ -489,10 +488,9 @@ int conv_bf16_dma_nt_launch(const void* a, const void* b, float* part, int M, in
     // the ping-pong instance (conv_bf16_pp.hip) takes this mode too (bit-equal partials).  First measured SLOWER (configs[4] training
     // step 55.3 ms with it, 54.3 without: profiles/round6_mixed_train_ab.txt); after the backward lost its streaming passes the same
     // A/B reads 47.7 vs 48.8 ms on configs[4] and 95.0 vs 96.9 ms on R50 640^2 B = 64 (profiles/round6_mixed_backward_ab.txt, two
-    // boxes alike): the weight gradients share the chip with fewer HBM-bound kernels of the main stream.  Default: wherever it can
-    // run (>= 4 chunks per split); CPR_BF16_NT_PP=0 keeps the lock-step instance, =n asks for splits of >= n chunks.
-    static const int nt_pp_min = []() { const char* e = getenv("CPR_BF16_NT_PP"); const int v = e ? atoi(e) : 1; return v <= 0 ? (1 << 30) : v < 4 ? 4 : v; }();
-    if (chunks >= nt_pp_min) conv_bf16_pp_launch(p, (unsigned)blocks, stream);
+    // boxes alike): the weight gradients share the chip with fewer HBM-bound kernels of the main stream.  It runs wherever it can
+    // (>= 4 chunks per split), the lock-step instance takes the rest.
+    if (chunks >= 4) conv_bf16_pp_launch(p, (unsigned)blocks, stream);
     else hipLaunchKernelGGL((conv_bf16_dma_kernel<4, 2, 4>), dim3((unsigned)blocks), dim3(512), 0, stream, p);
     CPR_LAUNCH_STATUS();
 }

@@ -4,7 +4,7 @@
 //
 // Since round 6 this file is the SECOND choice: with both maps in bf16 the entry point runs the pixel-major kernel of
 // conv_wgrad_bf16_tn.hip (no rewritten operands; stride 2, Cin % 64, small 1x1 layers included) and the rewriting path below takes
-// what is left -- an fp32 map among the two (rounded on the way in), or CPR_WGRAD_TN=0 / cpr_wgrad_bf16_set_tn(0).
+// what is left -- an fp32 map among the two (rounded on the way in), or a shape beyond the pixel-major kernel's index range.
 //
 //   dW[co][kh][kw][ci] = sum over pixels of dy[n, y, x, co] * x[n, y + kh - p, x + kw - p, ci]
 //
@@ -19,7 +19,6 @@
 // partials are summed -- and laid out as the [Cout][Cin][k][k] gradient -- by wgrad_bf16_reduce_kernel.
 #include "common.h"
 #include <type_traits>
-#include <cstdlib>
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
@@ -32,6 +31,7 @@ int wgrad_bf16_tn_launch(const void* dy, const void* x, float* part, int N, int 
 struct WgradBf16Plan {
     int pad, Hp, Wp, G, splits, chunks, taps;
     bool nt_ok;                   // the rewriting path can take this shape (Cin % 256 == 0, row length within the descriptors' range)
+    bool tn_ok;                   // the pixel-major kernel can (both maps bf16 only)
     int tn_splits, tn_chunks;     // the pixel-major kernel's split of the UNPADDED pixel axis
     long long Q, Qk, rs;          // real cells, cells covered by the K loop, row length (elements, guards included)
     long long off_dy, off_x, off_part, bytes;   // workspace layout
@@ -63,15 +63,14 @@ static bool wgrad_bf16_plan(int N, int H, int W, int Cin, int Cout, int k, Wgrad
     const int OH = (H + 2 * pl->pad - k) / stride + 1, OW = (W + 2 * pl->pad - k) / stride + 1;      // (stride 2: the strided layers of a stage's first block)
     if (OH <= 0 || OW <= 0) return false;
     const long long P = (long long)N * OH * OW, pchunks = (P + 63) / 64;
-    // (CPR_WGRAD_TN_WGS: the workgroup budget of the rule, default 512 = two rounds of 256 CUs: R50 640^2 B = 64 69.2 - 69.7 ms against 70.8 at 1024 and 72.7 at 2048, the configs[4] training line under torchrun 198 img/s against 196 (768) and 195 (1024) -- fewer slabs to write and sum; profiles/round6_wgrad_tn_splits_ab.txt)
-    static const long long tn_wgs = []() { const char* e = getenv("CPR_WGRAD_TN_WGS"); const long long v = e ? atoll(e) : 0; return v >= 64 ? v : 512; }();
-    long long ts = tn_wgs / (8 * pl->taps * tilesMN) * 8;
+    // (the workgroup budget of the rule, 512 = two rounds of 256 CUs: R50 640^2 B = 64 69.2 - 69.7 ms against 70.8 at 1024 and 72.7 at 2048, the configs[4] training line under torchrun 198 img/s against 196 (768) and 195 (1024) -- fewer slabs to write and sum; profiles/round6_wgrad_tn_splits_ab.txt)
+    long long ts = 512 / (8 * pl->taps * tilesMN) * 8;
     if (ts > pchunks / 8 / 8 * 8) ts = pchunks / 8 / 8 * 8;
     if (ts < 8) ts = 8;
     pl->tn_splits = (int)ts;
     pl->tn_chunks = (int)((pchunks + ts - 1) / ts);
-    const bool tn_ok = P * Cout * 2 < (1ll << 31) && (long long)N * H * W * Cin * 2 < (1ll << 31);
-    if (!pl->nt_ok && !tn_ok) return false;
+    pl->tn_ok = P * Cout * 2 < (1ll << 31) && (long long)N * H * W * Cin * 2 < (1ll << 31);
+    if (!pl->nt_ok && !pl->tn_ok) return false;
     pl->off_dy = 0;
     pl->off_x = pl->nt_ok ? (long long)Cout * pl->rs * 2 : 0;
     pl->off_part = pl->nt_ok ? pl->off_x + (long long)k * Cin * pl->rs * 2 : 0;
@@ -83,13 +82,13 @@ static bool wgrad_bf16_plan(int N, int H, int W, int Cin, int Cout, int k, Wgrad
 // src (N,H,W,C) NHWC (fp32 or bf16) -> NC copies dst_j[c][rs] bf16 (copy j at dst + j * copy): dst_j[c][G + q] = src at cell
 // (q + j - NC / 2), zero at border / guard cells.
 //
-// Round 6 (this kernel; the round-3 one below stays for A/B, CPR_WGRAD_T64=1): one workgroup = 256 positions x 64 channels.  A
-// thread owns an 8 x 8 block -- eight 16-byte loads along the channels of eight consecutive cells (a granule: granules never
-// straddle a row of the padded grid, Wp % 8 == 0) -- transposes it in registers (one v_perm_b32 per output dword) and parks the
-// eight channel granules (8 cells x 2 bytes) in LDS as [channel][granule], the granule column XORed with twice the channel group
-// (16 lanes = 16 distinct bank quads).  The read-out runs along the cells: 32 lanes = 512 contiguous bytes of one channel row,
-// whole lines; the +-1-cell copies of the 3x3 layers are funnel shifts (v_alignbit_b32) of three neighbouring granules.  Against
-// the round-3 kernel (two-byte LDS writes and reads, 64-position tiles): 16 LDS instructions per 64 elements instead of 128.
+// Round 6: one workgroup = 256 positions x 64 channels.  A thread owns an 8 x 8 block -- eight 16-byte loads along the channels of
+// eight consecutive cells (a granule: granules never straddle a row of the padded grid, Wp % 8 == 0) -- transposes it in registers
+// (one v_perm_b32 per output dword) and parks the eight channel granules (8 cells x 2 bytes) in LDS as [channel][granule], the
+// granule column XORed with twice the channel group (16 lanes = 16 distinct bank quads).  The read-out runs along the cells: 32 lanes
+// = 512 contiguous bytes of one channel row, whole lines; the +-1-cell copies of the 3x3 layers are funnel shifts (v_alignbit_b32) of
+// three neighbouring granules.  Against the round-3 kernel it replaced (two-byte LDS writes and reads, 64-position tiles; git history
+// has it): 16 LDS instructions per 64 elements instead of 128.
 template <bool SRC_BF16, int NC>
 __global__ __launch_bounds__(256) void wgrad_bf16_transpose_kernel(const void* __restrict__ src, unsigned short* __restrict__ dst,
                                                                    int N, int H, int W, int C, int pad, int Hp, int Wp, int G,
@@ -170,66 +169,6 @@ __global__ __launch_bounds__(256) void wgrad_bf16_transpose_kernel(const void* _
     }
 }
 
-// The round-3 form of the kernel above (one workgroup = 64 positions x 64 channels through a two-byte-granular LDS tile): kept for
-// A/B (CPR_WGRAD_T64=1) and as the second opinion of the tests.
-template <bool SRC_BF16, int NC>
-__global__ __launch_bounds__(256) void wgrad_bf16_transpose64_kernel(const void* __restrict__ src, unsigned short* __restrict__ dst,
-                                                                   int N, int H, int W, int C, int pad, int Hp, int Wp, int G,
-                                                                   long long rs, long long copy) {
-    constexpr int ROWS = 64 + NC - 1;
-    __shared__ unsigned short tile[ROWS][72];    // [cell][channel], rows padded against bank conflicts of the column reads
-    const long long r0 = (long long)blockIdx.x * 64;     // first row position of this block (0 = start of the leading guard)
-    const int c0 = blockIdx.y * 64;
-    const int tid = threadIdx.x;
-    {
-        const int c4 = (tid & 15) * 4;
-#pragma unroll
-        for (int j = 0; j < (ROWS + 15) / 16; ++j) {
-            const int t = (tid >> 4) + 16 * j;
-            if (t >= ROWS) break;
-            const int q = (int)(r0 + t) - G - NC / 2;           // padded cell of tile row t (the plan keeps rs < 2^30)
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
-            if (q >= 0 && q < N * Hp * Wp) {
-                const int n = q / (Hp * Wp);
-                const int rem = q - n * Hp * Wp;
-                const int yp = rem / Wp, xp = rem - yp * Wp;
-                const int y = yp - pad, x = xp - pad;
-                if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) {
-                    const size_t e = (((size_t)n * H + y) * W + x) * C + c0 + c4;
-                    if (SRC_BF16) {
-                        const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(src) + e);
-                        v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-                        v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
-                    } else {
-                        const f32x4 f = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(src) + e);
-                        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-                    }
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) tile[t][c4 + e] = __builtin_bit_cast(unsigned short, (__bf16)v[e]);
-        }
-    }
-    __syncthreads();
-    {
-        const int q8 = (tid & 7) * 8;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int ch = (tid >> 3) + 32 * j;
-#pragma unroll
-            for (int cp = 0; cp < NC; ++cp) {       // copy cp at position i shows tile row i + cp
-                unsigned short o[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = tile[q8 + e + cp][ch];
-                uint4 w;
-                w.x = o[0] | ((unsigned)o[1] << 16); w.y = o[2] | ((unsigned)o[3] << 16);
-                w.z = o[4] | ((unsigned)o[5] << 16); w.w = o[6] | ((unsigned)o[7] << 16);
-                *reinterpret_cast<uint4*>(dst + (size_t)cp * copy + (size_t)(c0 + ch) * rs + r0 + q8) = w;
-            }
-        }
-    }
-}
-
 // part [splits][taps][Cout][Cin] fp32 -> grad [Cout][Cin][k][k] (the nn.Conv2d weight layout), summed over the splits: a block sums
 // 256 consecutive elements (64 threads x 4), its four 64-thread rows take every fourth split.  Round 6: 16-byte loads, four splits
 // requested before the first add (the round-3 form read 4 bytes per thread, one split at a time: 2.1 TB/s on the 64-slab layers of
@@ -272,39 +211,20 @@ __global__ __launch_bounds__(256) void wgrad_bf16_reduce_kernel(const float* __r
     }
 }
 
-// which kernel takes the bf16 weight gradient when both maps are bf16: 0 = channel-major rewrites + NT GEMM, 1 = the pixel-major kernel
-// (conv_wgrad_bf16_tn.hip).  Initial value: CPR_WGRAD_TN (default 1); cpr_wgrad_bf16_set_tn switches at run time (tests, A/B tools).
-static int& wgrad_bf16_tn_mode() {
-    static int mode = []() { const char* e = getenv("CPR_WGRAD_TN"); return (e && e[0] == '0') ? 0 : 1; }();
-    return mode;
-}
-extern "C" int cpr_wgrad_bf16_set_tn(int on) {
-    const int old = wgrad_bf16_tn_mode();
-    if (on >= 0) wgrad_bf16_tn_mode() = on != 0;
-    return old;
-}
-
-// workspace size in units of 256 bytes (the byte count of a B=64 head layer does not fit the int every entry point returns)
-extern "C" int cpr_conv_wgrad_bf16_workspace_s(int N, int H, int W, int Cin, int Cout, int k, int stride) {
+// workspace size in units of 256 bytes (the byte count of a B=64 head layer does not fit the int every entry point returns), or
+// CPR_ERR_UNSUPPORTED exactly where cpr_conv_wgrad_bf16_s is for maps of these dtypes: both bf16 -> the pixel-major kernel or the
+// rewriting path, an fp32 map among them -> the rewriting path alone
+extern "C" int cpr_conv_wgrad_bf16_workspace_s(int N, int H, int W, int Cin, int Cout, int k, int stride, int dy_bf16, int x_bf16) {
     WgradBf16Plan pl;
-    if (!wgrad_bf16_plan(N, H, W, Cin, Cout, k, &pl, stride)) return CPR_ERR_UNSUPPORTED;
+    if (!wgrad_bf16_plan(N, H, W, Cin, Cout, k, &pl, stride) || !((dy_bf16 && x_bf16 && pl.tn_ok) || pl.nt_ok)) return CPR_ERR_UNSUPPORTED;
     const long long units = (pl.bytes + 255) / 256;
     return units < (1ll << 31) ? (int)units : CPR_ERR_UNSUPPORTED;
 }
-extern "C" int cpr_conv_wgrad_bf16_workspace(int N, int H, int W, int Cin, int Cout, int k) {
-    return cpr_conv_wgrad_bf16_workspace_s(N, H, W, Cin, Cout, k, 1);
-}
 
-// dy (N,H,W,Cout) fp32 or bf16 (dy_bf16); x (N,H,W,Cin) fp32 or bf16 (x_bf16); grad [Cout][Cin][k][k] fp32 (accumulate: += ); ws: workspace of
-// cpr_conv_wgrad_bf16_workspace x 256 bytes, 256-byte aligned.  k in {1, 3}, stride 1, padding k / 2, Cin % 256 == 0, Cout % 64 == 0.
-// _s (round 6): + stride (1 or 2; dy is then (N,OH,OW,Cout)).  Stride 2, Cin % 256 != 0 and 1x1 layers are the pixel-major kernel's
-// alone: both maps must be bf16 (else CPR_ERR_UNSUPPORTED).
-extern "C" int cpr_conv_wgrad_bf16_s(const void* dy, int dy_bf16, const void* x, int x_bf16, float* grad, void* ws, int N, int H, int W,
-                                     int Cin, int Cout, int k, int stride, int accumulate, hipStream_t stream);
-extern "C" int cpr_conv_wgrad_bf16(const void* dy, int dy_bf16, const void* x, int x_bf16, float* grad, void* ws, int N, int H, int W,
-                                   int Cin, int Cout, int k, int accumulate, hipStream_t stream) {
-    return cpr_conv_wgrad_bf16_s(dy, dy_bf16, x, x_bf16, grad, ws, N, H, W, Cin, Cout, k, 1, accumulate, stream);
-}
+// dy (N,OH,OW,Cout) fp32 or bf16 (dy_bf16); x (N,H,W,Cin) fp32 or bf16 (x_bf16); grad [Cout][Cin][k][k] fp32 (accumulate: += ); ws:
+// workspace of cpr_conv_wgrad_bf16_workspace_s x 256 bytes, 256-byte aligned.  k in {1, 3}, padding k / 2, stride 1 or 2, Cin % 64 == 0,
+// Cout % 64 == 0.  Stride 2, Cin % 256 != 0 and 1x1 layers are the pixel-major kernel's alone: both maps must be bf16 (else
+// CPR_ERR_UNSUPPORTED).
 extern "C" int cpr_conv_wgrad_bf16_s(const void* dy, int dy_bf16, const void* x, int x_bf16, float* grad, void* ws, int N, int H, int W,
                                      int Cin, int Cout, int k, int stride, int accumulate, hipStream_t stream) {
     CPR_CHECK_ARG(dy && x && grad && ws);
@@ -313,8 +233,8 @@ extern "C" int cpr_conv_wgrad_bf16_s(const void* dy, int dy_bf16, const void* x,
     unsigned short* dyT = reinterpret_cast<unsigned short*>((char*)ws + pl.off_dy);
     unsigned short* xT = reinterpret_cast<unsigned short*>((char*)ws + pl.off_x);
     float* part = reinterpret_cast<float*>((char*)ws + pl.off_part);
-    // both maps bf16 -> the pixel-major kernel (no dyT / xT rewrites) unless switched off (CPR_WGRAD_TN=0 / cpr_wgrad_bf16_set_tn(0))
-    if (wgrad_bf16_tn_mode() != 0 && dy_bf16 && x_bf16) {
+    // both maps bf16 -> the pixel-major kernel (no dyT / xT rewrites)
+    if (dy_bf16 && x_bf16) {
         const int rc = wgrad_bf16_tn_launch(dy, x, part, N, H, W, Cin, Cout, k, stride, pl.tn_splits, pl.tn_chunks, stream);
         if (rc == CPR_OK) {
             const long long n = (long long)pl.taps * Cout * Cin;
@@ -326,14 +246,11 @@ extern "C" int cpr_conv_wgrad_bf16_s(const void* dy, int dy_bf16, const void* x,
     }
     if (!pl.nt_ok) return CPR_ERR_UNSUPPORTED;
     const long long copy = (long long)Cin * pl.rs;
-    static const bool t64 = []() { const char* e = getenv("CPR_WGRAD_T64"); return e && e[0] == '1'; }();     // A/B: the round-3 kernel
     auto rewrite = [&](auto bf, auto nc, const void* src, unsigned short* dst, int C, long long cp) {
         constexpr bool B = decltype(bf)::value;
         constexpr int NC = decltype(nc)::value;
-        if (t64) hipLaunchKernelGGL((wgrad_bf16_transpose64_kernel<B, NC>), dim3((unsigned)(pl.rs / 64), C / 64), dim3(256), 0, stream, src, dst,
-                                    N, H, W, C, pl.pad, pl.Hp, pl.Wp, pl.G, pl.rs, cp);
-        else hipLaunchKernelGGL((wgrad_bf16_transpose_kernel<B, NC>), dim3((unsigned)(pl.rs / 256), C / 64), dim3(256), 0, stream, src, dst,
-                                N, H, W, C, pl.pad, pl.Hp, pl.Wp, pl.G, pl.rs, cp);
+        hipLaunchKernelGGL((wgrad_bf16_transpose_kernel<B, NC>), dim3((unsigned)(pl.rs / 256), C / 64), dim3(256), 0, stream, src, dst,
+                           N, H, W, C, pl.pad, pl.Hp, pl.Wp, pl.G, pl.rs, cp);
     };
     using std::integral_constant;
     if (dy_bf16) rewrite(integral_constant<bool, true>{}, integral_constant<int, 1>{}, dy, dyT, Cout, 0ll);

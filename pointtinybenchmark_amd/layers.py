@@ -3,7 +3,6 @@
 nn.Conv2d / nn.BatchNorm2d / nn.GroupNorm objects are used ONLY as parameter holders so the state-dict
 keys match the reference checkpoint layout; their ``forward`` is never called -- all
 compute goes through ``ops`` (HIP kernels)."""
-import os
 import struct
 
 import torch
@@ -21,8 +20,8 @@ def bump_weight_epoch():
     _WEIGHT_EPOCH[0] += 1
 
 
-# CPR_REFRESH_IN_PLACE=0: every fold / pack lapses with the weight epoch and is rebuilt lazily (rounds 3-5; A/B switch)
-REFRESH_IN_PLACE = [os.environ.get('CPR_REFRESH_IN_PLACE', '1') != '0']
+# False: every fold / pack lapses with the weight epoch and is rebuilt lazily (rounds 3-5; tests)
+REFRESH_IN_PLACE = [True]
 
 _FOLDS, _PACKS16, _PACKS32 = 'cpr_bn_fold_multi', 'cpr_pack_weights_bf16_multi', 'cpr_pack_weights_multi'
 
@@ -84,9 +83,8 @@ class PackJob:
 
 def _pack_job(pc, weight, transpose=0, fold=None):
     """The PackJob of a pack that a pack kernel built from an fp32 contiguous device weight; None for anything else (the strided
-    layers' PhasedDgrad, the torch-built bf16 packs of CPR_PACK_BF16_KERNEL=0): that entry lapses with the weight epoch."""
-    if isinstance(pc, ops.PackedConv) and weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous() and \
-            (pc.dtype == torch.float32 or ops.PACK_BF16_KERNEL[0]):
+    layers' PhasedDgrad): that entry lapses with the weight epoch."""
+    if isinstance(pc, ops.PackedConv) and weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous():
         return PackJob(weight, pc, transpose, fold)
     return None
 
@@ -214,10 +212,7 @@ def dgrad_packed(cache, conv, bn=None, dtype=torch.float32):
         scale, _ = folded_bn(cache, bn)
         if dtype == torch.float32 or stride != 1:
             return ops.dgrad_pack(w, stride, pad, scale=scale, dtype=dtype)
-        if ops.PACK_BF16_KERNEL[0]:
-            return ops.PackedConv.for_dgrad_bf16(w, pad, scale=scale)
-        wt = (w.detach() * scale[:, None, None, None]).flip(2, 3).permute(1, 0, 2, 3)
-        return ops.PackedConv(wt, 1, conv.kernel_size[0] - 1 - pad, torch.bfloat16)
+        return ops.PackedConv.for_dgrad_bf16(w, pad, scale=scale)
 
     def job(pc):        # linked to the fold job of the scale make() multiplied in
         fold = cache._jobs.get(('bn', id(bn)))
@@ -278,7 +273,7 @@ def conv_gn(cache, m, x, in_ab=None, in_relu=False, materialize=True, up=None, s
     cout tile on its way into the 4x4 patch transform -- 2 packed FMA/max per 8 bytes, invisible behind the MFMAs -- so they
     always fuse.  The direct kernel's KxK consumers re-transform every element K*K x (cout tiles) times (3x3 256->256 at
     160x160, B=16: 3.52 ms fused vs 3.30 ms plain) while gn_apply touches it once at HBM speed (0.14 ms): those take the
-    materialised input in forward-only mode, 1x1 consumers fuse (CPR_GN_FUSE_IN=1 forces the fused form).
+    materialised input in forward-only mode, 1x1 consumers fuse.
     """
     pc = packed_conv(cache, m.conv, x.dtype)
     gn = m.norm
@@ -295,7 +290,7 @@ def conv_gn(cache, m, x, in_ab=None, in_relu=False, materialize=True, up=None, s
     fused_stats = wino or (OH * OW) % 128 == 0
     fuse_in = in_ab is not None and (wino or ((H * W) % 128 == 0 and pc.stride == 1 and (OH, OW) == (H, W)
                                               and x.dtype == torch.float32))   # the bf16 kernel does not fuse the producer GN
-    if fuse_in and not wino and save is None and pc.KH * pc.KW > 1 and os.environ.get('CPR_GN_FUSE_IN', '0') != '1':
+    if fuse_in and not wino and save is None and pc.KH * pc.KW > 1:
         fuse_in = False
     if in_ab is not None and not fuse_in:
         x = ops.gn_apply(x, in_ab[0], in_ab[1], relu=in_relu, out=x if (consume_input and save is None) else None)

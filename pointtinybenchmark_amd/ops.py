@@ -8,7 +8,6 @@ NCHW-shaped (channels_last-strided) tensors, which is what crosses the reference
 import collections
 import ctypes
 import math
-import os
 
 import torch
 
@@ -87,7 +86,7 @@ class PackedConv:
             assert Cin % 64 == 0, 'bf16 conv needs Cin % 64 == 0'
             self.Cout, self.Cin, self.KH, self.KW, self.Kpad = Cout, Cin, KH, KW, KH * KW * Cin
             self.stride, self.padding = stride, padding
-            if weight.is_cuda and PACK_BF16_KERNEL[0]:
+            if weight.is_cuda:
                 self._pack_bf16(weight, None, 0)      # one launch: the [Cout][K] image and, where it is used, the fragment image
                 return
             self.w = w.reshape(Cout, KH * KW * Cin).to(torch.bfloat16).contiguous()
@@ -189,17 +188,15 @@ class PackedConv:
 
 CONV_RELU, CONV_OUT_BF16, CONV_RES_MASK, CONV_COLSUM = 1, 2, 4, 8      # include/cpr_hip.h CPR_CONV_*
 # bf16 mode: hand the fragment-order weight image to the conv launcher (the 256 x 256 tile then loads its weight operand
-# straight into registers, csrc/conv_bf16_dma.hip BD instance).  CPR_BF16_WFRAG=0 keeps both operands on the LDS-DMA path (A/B).
-WFRAG = [os.environ.get('CPR_BF16_WFRAG', '1') != '0']
-# bf16 weight packs by one HIP launch per layer (csrc/pack.hip); CPR_PACK_BF16_KERNEL=0: the torch expression of rounds 3-4 (A/B, tests)
-PACK_BF16_KERNEL = [os.environ.get('CPR_PACK_BF16_KERNEL', '1') != '0']
+# straight into registers, csrc/conv_bf16_dma.hip BD instance).  False keeps both operands on the LDS-DMA path (tests).
+WFRAG = [True]
 # profilers (bench.py) set [0] = True; the template instance of the last conv launch is then left in [1] as
 # (kind, code).  Host-side, single-threaded bookkeeping of a value the C ABI returns through an out-parameter.
 TRACE_CONV_VARIANT = [False, None]
 
 # 3x3 / stride 1 / pad 1 fp32 layers run as fused Winograd F(2x2,3x3) (csrc/conv_wino.hip, 2.25x fewer multiplies) when the
-# map fills its 16x16 output regions well enough; CPR_WINOGRAD=0 keeps every layer on the direct implicit GEMM (A/B runs).
-WINOGRAD = [os.environ.get('CPR_WINOGRAD', '1') != '0']
+# map fills its 16x16 output regions well enough; False keeps every layer on the direct implicit GEMM (tests).
+WINOGRAD = [True]
 WINO_MIN_FILL = 0.6      # useful share of the 16x16 regions (40x40 -> 0.69 runs Winograd, 20x20 -> 0.39 stays direct)
 
 
@@ -245,8 +242,8 @@ def wino_eligible(pc, H, W, dtype=torch.float32):
 # Which fused Winograd kernel serves a 3x3 layer: '32' = the two-workgroups-per-CU form (csrc/conv_wino32.hip: 8 x 16 pixel
 # regions, 4-wave workgroups), '64' = the one-workgroup-per-CU form (csrc/conv_wino.hip: 16 x 16 regions).  The choice is a function
 # of the LAYER alone (never of the batch size: an image of a big batch must equal its single-image run bit for bit, and the two
-# kernels differ in accumulation order).  CPR_WINO_TILE=64 / 32 forces one of them everywhere it can run (A/B runs, tests).
-WINO_TILE = [os.environ.get('CPR_WINO_TILE', 'auto')]
+# kernels differ in accumulation order).  '64' / '32' forces one of them everywhere it can run (tests).
+WINO_TILE = ['auto']
 
 
 def wino_instance(pc, H, W, fused_affine):
@@ -1271,25 +1268,18 @@ def conv2d_dgrad(dy, pc_t, in_hw, stride=1, mask=None, add=None, colsum=False):
     return out
 
 
-def wgrad_tn(on=None):
-    """The kernel choice of the bf16 weight gradient for bf16 maps (include/cpr_hip.h, cpr_wgrad_bf16_set_tn): True = the pixel-major
-    kernel (csrc/conv_wgrad_bf16_tn.hip, the default), False = channel-major rewrites + NT GEMM.  Returns the value before the
-    call; on=None only queries."""
-    return bool(_lib.call('cpr_wgrad_bf16_set_tn', -1 if on is None else int(bool(on)), positive=True))      # (the previous value)
-
-
 def conv_wgrad_bf16_supported(x_shape, weight_shape, stride, padding, maps_bf16=False):
-    """Shapes the bf16 weight gradient takes: stride 1, 1x1 or 3x3 / padding 1, Cout % 64 == 0 and -- maps_bf16 (both maps are bf16:
-    the pixel-major kernel, csrc/conv_wgrad_bf16_tn.hip) Cin % 64 == 0, else (csrc/conv_wgrad_bf16.hip: channel-major rewrites + NT
-    GEMM) Cin % 256 == 0 and, for 1x1 layers, Cout >= 256."""
+    """Whether conv_wgrad_bf16 takes this layer (1x1 or 3x3 / padding 1): maps_bf16 (both maps are bf16) -- the pixel-major kernel
+    (csrc/conv_wgrad_bf16_tn.hip) or the rewriting path; else the rewriting path alone (csrc/conv_wgrad_bf16.hip), and not for a 1x1
+    layer below 256 couts.  The shape rule itself is the C query's (cpr_conv_wgrad_bf16_workspace_s: negative = unsupported, called
+    directly -- here that is an answer, not an error)."""
     Cout, Cin, KH, KW = weight_shape
-    tn = maps_bf16 and wgrad_tn()
-    if KH == 1 and Cout < 256 and not tn:      # measured (tools/wgrad_bf16_bench.py): the two rewrites cost what the bf16 GEMM saves
+    if KH == 1 and Cout < 256 and not maps_bf16:      # measured (tools/wgrad_bf16_bench.py): the two rewrites cost what the bf16 GEMM saves
         return False
-    if not (stride == 1 or (tn and stride == 2)):      # the strided 3x3 / projection layers: the pixel-major kernel only
+    if KH != KW or padding != KH // 2:                 # (the query sees one kernel size and no padding)
         return False
-    return KH == KW and KH in (1, 3) and padding == KH // 2 and Cin % (64 if tn else 256) == 0 and Cout % 64 == 0 and \
-        _lib.call('cpr_conv_wgrad_bf16_workspace_s', x_shape[0], x_shape[1], x_shape[2], Cin, Cout, KH, stride, positive=True) > 0
+    return _lib.load().cpr_conv_wgrad_bf16_workspace_s(x_shape[0], x_shape[1], x_shape[2], Cin, Cout, KH, stride, int(maps_bf16),
+                                                       int(maps_bf16)) > 0
 
 
 def conv_wgrad_bf16(dy, x, weight_shape, out=None, accumulate=False, stride=1):
@@ -1301,14 +1291,15 @@ def conv_wgrad_bf16(dy, x, weight_shape, out=None, accumulate=False, stride=1):
     assert Cin_w == Cin and tuple(dy.shape) == (N, OH, OW, Cout) and KH == KW, (tuple(dy.shape), (N, OH, OW, Cout))
     assert x.dtype in (torch.float32, torch.bfloat16) and dy.dtype in (torch.float32, torch.bfloat16)
     assert x.is_contiguous() and dy.is_contiguous()
-    units = _lib.call('cpr_conv_wgrad_bf16_workspace_s', N, H, W, Cin, Cout, KH, stride, positive=True)
+    dy16, x16 = int(dy.dtype == torch.bfloat16), int(x.dtype == torch.bfloat16)
+    units = _lib.call('cpr_conv_wgrad_bf16_workspace_s', N, H, W, Cin, Cout, KH, stride, dy16, x16, positive=True)
     ws = torch.empty((units * 256,), device=x.device, dtype=torch.uint8)
     if out is None:
         assert not accumulate
         out = torch.empty(tuple(weight_shape), device=x.device, dtype=torch.float32)
     assert tuple(out.shape) == tuple(weight_shape) and out.is_contiguous() and out.dtype == torch.float32
-    _lib.call('cpr_conv_wgrad_bf16_s', _ptr(dy), int(dy.dtype == torch.bfloat16), _ptr(x), int(x.dtype == torch.bfloat16), _ptr(out),
-              _ptr(ws), N, H, W, Cin, Cout, KH, stride, int(accumulate), _stream())
+    _lib.call('cpr_conv_wgrad_bf16_s', _ptr(dy), dy16, _ptr(x), x16, _ptr(out), _ptr(ws), N, H, W, Cin, Cout, KH, stride, int(accumulate),
+              _stream())
     return out
 
 

@@ -22,9 +22,6 @@ from . import ops
 from .layers import _PackCache, bn_inv_sigma, bump_weight_epoch, dgrad_packed, folded_bn
 
 
-WINO_DGRAD = [os.environ.get('CPR_WINO_DGRAD', '1') == '1']     # A/B switch (tools): 3x3 data gradients as Winograd + a mask pass
-
-
 class GradBuckets:
     """Contiguous buckets over a flat gradient buffer.  ``ready(end)`` says gradients [0, end) are final; every bucket
     fully below ``end`` is reduced asynchronously (on the process group's own stream).  Works on CPU tensors with
@@ -263,16 +260,13 @@ class StepLrSchedule:
         return reg * (1 - (1 - it / self.warmup_iters) * (1 - self.warmup_ratio))
 
 
-# mixed precision: dtype hand-offs fused into the producing kernels (CPR_MIXED_FUSED_CAST=0: the separate torch passes of rounds 3-4, A/B)
-FUSED_CAST = os.environ.get('CPR_MIXED_FUSED_CAST', '1') != '0'
-# measurement switches (tests/report_mixed_precision_grads.py: where the mixed-precision gradient error comes from): the weight /
-# data gradients of the mixed-precision step on the fp32 kernels; force = bf16 backward rules behind an fp32 recorded forward
-MIXED_BF16 = dict(wgrad=os.environ.get('CPR_MIXED_WGRAD', 'bf16') != 'fp32', dgrad=os.environ.get('CPR_MIXED_DGRAD', 'bf16') != 'fp32',
-                  dgrad1x1=os.environ.get('CPR_MIXED_DGRAD_1X1', 'bf16') != 'fp32',
-                  dz16=os.environ.get('CPR_MIXED_DZ16', '1') != '0',
-                  dgrad_s2=os.environ.get('CPR_MIXED_DGRAD_S2', 'bf16') != 'fp32',
-                  mask_mode=os.environ.get('CPR_MIXED_MASK_MODE', '1') != '0',
-                  p2p_out=os.environ.get('CPR_MIXED_P2P_OUT', 'bf16') != 'fp32', force=False)
+# mixed precision: dtype hand-offs fused into the producing kernels (False: the separate torch passes of rounds 3-4; tests)
+FUSED_CAST = True
+# reference paths of the mixed-precision step (tests, bench.py, tests/report_mixed_precision_grads.py: where its gradient error comes
+# from): wgrad / dgrad False = the weight / data gradients on the fp32 kernels; dz16 False = fp32 gradient maps between the head
+# tower's layers; mask_mode False = the streaming passes behind the bf16 data gradients; force = bf16 backward rules behind an fp32
+# recorded forward
+MIXED_BF16 = dict(wgrad=True, dgrad=True, dz16=True, mask_mode=True, force=False)
 
 
 class BackwardEngine:
@@ -471,7 +465,7 @@ class BackwardEngine:
         if wgrad16:
             x = rec['x']       # the weight gradient on the bf16 matrix pipe, straight from the recorded map
             gw = self._g(w)
-            self._param_side(lambda: ops.conv_wgrad_bf16(d16, x, w.shape, out=gw), d16, x)
+            self._param_side(lambda: ops.conv_wgrad_bf16(d16, x, w.shape, out=gw, stride=cm.conv.stride[0]), d16, x)
         else:
             x = self._f32(rec['x'])
             gw = self._g(w)
@@ -491,12 +485,7 @@ class BackwardEngine:
         """Mixed precision: the data gradient of a stride-1 conv on the bf16 matrix pipe -- a forward conv of the bf16-rounded
         gradient map with the rotated weights (channels swapped, taps flipped, padding K-1-p), fp32 out.  The weight gradient
         next to it keeps reading the fp32 map."""
-        if ops.PACK_BF16_KERNEL[0]:
-            pc = ops.PackedConv.for_dgrad_bf16(w, padding)
-        else:
-            k = w.shape[2]
-            wt = w.detach().flip(2, 3).permute(1, 0, 2, 3)
-            pc = ops.PackedConv(wt, 1, k - 1 - padding, torch.bfloat16)
+        pc = ops.PackedConv.for_dgrad_bf16(w, padding)
         return ops.conv2d(dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16), pc, out_dtype=out_dtype)
 
     # ------------------------------------------------------------------ CPR head
@@ -806,19 +795,25 @@ class BackwardEngine:
             self._param_side(param_grads, dy, part, x)
         self._done([p for p in (w, bn.weight, bn.bias) if p.requires_grad][-1])
 
-    def _reads_bf16_only(self, conv, x, has_add, need_dx):
-        """True when the backward rule of ``conv`` (input map x) reads nothing but the bf16 rounding of its output gradient: both of
-        its gradients run on the bf16 matrix pipe (the conditions of _conv_bn_backward), so the producer need not write the fp32 map."""
+    def _bf16_grads(self, conv, x, has_add, need_dx):
+        """(w16, d16): whether the weight / data gradient of the folded conv ``conv`` (input map x, a shortcut gradient summed into
+        its data gradient: has_add) run on the bf16 matrix pipe.  One bf16 copy of the output gradient feeds both (round 6: the stride-1
+        1x1 layers too -- their fp32 form was 13 % of the step's kernel time, profiles/round5_train_cfg4_kernel_stats.csv)."""
         if not self._mixed:
-            return False
+            return False, False
         w = conv.weight
         k = conv.kernel_size[0]
-        w16 = not w.requires_grad or (MIXED_BF16['wgrad'] and
-                                      ops.conv_wgrad_bf16_supported(x.shape, w.shape, conv.stride[0], conv.padding[0],
-                                                                    maps_bf16=x.dtype == torch.bfloat16))
-        d16 = not need_dx or (MIXED_BF16['dgrad'] and conv.stride[0] == 1 and w.shape[0] % 64 == 0 and
-                              (k == 3 and not has_add or k == 1 and MIXED_BF16['dgrad1x1'] and w.shape[1] % 64 == 0))
-        return bool(w16 and d16)
+        w16 = w.requires_grad and MIXED_BF16['wgrad'] and \
+            ops.conv_wgrad_bf16_supported(x.shape, w.shape, conv.stride[0], conv.padding[0], maps_bf16=x.dtype == torch.bfloat16)
+        d16 = need_dx and MIXED_BF16['dgrad'] and conv.stride[0] == 1 and w.shape[0] % 64 == 0 and \
+            (k == 3 and not has_add or k == 1 and w.shape[1] % 64 == 0)
+        return bool(w16), bool(d16)
+
+    def _reads_bf16_only(self, conv, x, has_add, need_dx):
+        """True when the backward rule of ``conv`` (input map x) reads nothing but the bf16 rounding of its output gradient: both of
+        its gradients run on the bf16 matrix pipe (_bf16_grads), so the producer need not write the fp32 map."""
+        w16, d16 = self._bf16_grads(conv, x, has_add, need_dx)
+        return self._mixed and (w16 or not conv.weight.requires_grad) and (d16 or not need_dx)
 
     def _conv_bn_backward(self, cache, conv, bn, g, colsum, x, need_dx, mask=None, add=None, want_colsum=False, g16=None, want16=False,
                           need32=True):
@@ -836,12 +831,7 @@ class BackwardEngine:
         inv_sigma = bn_inv_sigma(cache, bn)
         w = conv.weight
         k = conv.kernel_size[0]
-        # mixed precision: ONE bf16 copy of the gradient map feeds the bf16 weight gradient and the bf16 data gradient (round 6: the
-        # stride-1 1x1 layers too -- their fp32 form was 13 % of the step's kernel time, profiles/round5_train_cfg4_kernel_stats.csv)
-        w16 = w.requires_grad and self._mixed and MIXED_BF16['wgrad'] and \
-            ops.conv_wgrad_bf16_supported(x.shape, w.shape, conv.stride[0], conv.padding[0], maps_bf16=x.dtype == torch.bfloat16)
-        d16 = need_dx and self._mixed and MIXED_BF16['dgrad'] and conv.stride[0] == 1 and w.shape[0] % 64 == 0 and \
-            (k == 3 and add is None or k == 1 and MIXED_BF16['dgrad1x1'] and w.shape[1] % 64 == 0)
+        w16, d16 = self._bf16_grads(conv, x, add is not None, need_dx)      # mixed precision: ONE bf16 copy of g feeds both
         if g16 is None and (w16 or d16):
             g16 = g.to(torch.bfloat16)
         if w.requires_grad:
@@ -888,7 +878,7 @@ class BackwardEngine:
                 dx32, dx16, part = ops.conv2d_dgrad_bf16_fused(g16, pc16, mask, add)
                 return dx32, part, dx16
             return finish(ops.conv2d(g16, pc16, out_dtype=torch.float32), add)
-        if need_dx and self._mixed and MIXED_BF16['dgrad'] and MIXED_BF16['dgrad_s2'] and conv.stride[0] == 2 and k in (1, 3) and \
+        if need_dx and self._mixed and MIXED_BF16['dgrad'] and conv.stride[0] == 2 and k in (1, 3) and \
                 conv.padding[0] == k // 2 and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0 and ops._PHASED[0]:
             # mixed precision, the strided layers of a stage's first block (round 6): the four parity sub-convolutions of the phase-
             # decomposed data gradient on the bf16 pipe (fp32 out, scattered / summed in fp32 as before)
@@ -897,7 +887,7 @@ class BackwardEngine:
                 g16 = g.to(torch.bfloat16)
             return finish(pt16(g16, (x.shape[1], x.shape[2]), add=add))
         pt = dgrad_packed(cache, conv, bn)
-        if WINO_DGRAD[0] and k == 3 and conv.stride[0] == 1 and add is None and \
+        if k == 3 and conv.stride[0] == 1 and add is None and \
                 (mask is not None or want_colsum) and ops.wino_eligible(pt, x.shape[1], x.shape[2], torch.float32):
             # a 3x3 stride-1 data gradient with a mask / column-sum epilogue would run the direct kernel (2.25x the multiplies of
             # the Winograd launch the plain form gets); the epilogue as one streaming pass over the result is cheaper
@@ -1425,13 +1415,13 @@ class P2PHeadRules:
 
     def _p2p_out_conv_backward_mixed(self, tape, dout, n_out):
         """Mixed precision (the bf16 forward recorded bf16 tower maps): the output conv's gradients straight from the raw bf16 last layer
-        and its GroupNorm affine (csrc/p2p_out_bf16.hip: J <= 8; MIXED_BF16 p2p_out / wgrad / dgrad off, or larger J: the fp32 kernels
+        and its GroupNorm affine (csrc/p2p_out_bf16.hip: J <= 8; MIXED_BF16 wgrad / dgrad off, or larger J: the fp32 kernels
         on the widened map).  The tower below it runs as in the CPR head -- bf16 gradient maps between its layers, fp32 at its input --
         so the data gradient is bf16 when the layer below reads it so."""
         rec = tape[-1]
         conv = rec['conv']
         w, x, ab = conv.weight, rec['x'], rec['in_ab']
-        ok = self._mixed and MIXED_BF16['p2p_out'] and ops.p2p_out_bf16_supported(x.shape, n_out)
+        ok = self._mixed and ops.p2p_out_bf16_supported(x.shape, n_out)
         wgrad16, dgrad16 = ok and MIXED_BF16['wgrad'], ok and MIXED_BF16['dgrad']
         to16 = len(tape) > 1 and self._mixed and MIXED_BF16['dz16'] and FUSED_CAST and tape[-2]['raw'].dtype == torch.bfloat16
         if not (wgrad16 or dgrad16):

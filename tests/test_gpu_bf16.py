@@ -316,16 +316,12 @@ def test_conv_wgrad_bf16_head_layer_shape_vs_fp32_kernel():
     rel = float((got - ref).norm() / ref.norm())
     assert rel <= 1e-2, rel
     # round 6: the pixel-major kernel on the same maps in bf16 (its splits and chunk boundaries differ from the rewriting path's, the
-    # products are the same): against the rewriting path on the SAME bf16 operands only fp32 summation order differs
+    # products are the same): against the rewriting path on the SAME bf16 operands only fp32 summation order differs (the widened
+    # dy16 sends the gradient down the rewriting path, which rounds it back exactly)
     dy16, x16 = dy.bfloat16(), x.bfloat16()
-    old = ops.wgrad_tn(True)
-    try:
-        tn = ops.conv_wgrad_bf16(dy16, x16, (C, C, 3, 3))
-        ops.wgrad_tn(False)
-        nt = ops.conv_wgrad_bf16(dy16, x16, (C, C, 3, 3))
-        torch.cuda.synchronize()
-    finally:
-        ops.wgrad_tn(old)
+    tn = ops.conv_wgrad_bf16(dy16, x16, (C, C, 3, 3))
+    nt = ops.conv_wgrad_bf16(dy16.float(), x16, (C, C, 3, 3))
+    torch.cuda.synchronize()
     assert float((tn - nt).abs().max()) <= 1e-4 * float(nt.abs().max()), float((tn - nt).abs().max() / nt.abs().max())
 
 
@@ -340,29 +336,25 @@ def test_bf16_weight_pack_kernel_equals_the_torch_expression(shape):
     g = torch.Generator().manual_seed(5)
     w = (torch.randn((Cout, Cin, k, k), generator=g) * 0.05).cuda()
     scale = (torch.rand(Cout, generator=g) + 0.5).cuda()
-    assert ops.PACK_BF16_KERNEL[0]
+    def frag(img, rows, K):         # the fragment order of frag_image, as a torch expression; None where the layer has none
+        return img.view(rows // 64, 32, 2, K // 16, 2, 8).permute(0, 3, 2, 4, 1, 5).reshape(-1) if rows % 256 == 0 else None
+
     pc = ops.PackedConv(w, 1, k // 2, torch.bfloat16)
     ref = w.permute(0, 2, 3, 1).reshape(Cout, k * k * Cin).to(torch.bfloat16).contiguous()
     assert pc.w.dtype == torch.bfloat16 and torch.equal(pc.w, ref)
     if Cout % 256 == 0:
-        G, KS = Cout // 64, k * k * Cin // 16
-        assert pc.wfrag is not None and torch.equal(pc.frag_image().reshape(-1),
-                                                    ref.view(G, 32, 2, KS, 2, 8).permute(0, 3, 2, 4, 1, 5).reshape(-1))
+        assert pc.wfrag is not None and torch.equal(pc.frag_image().reshape(-1), frag(ref, Cout, k * k * Cin))
     else:
         assert pc.frag_image() is None
     for sc in (None, scale):
         pd = ops.PackedConv.for_dgrad_bf16(w, k // 2, scale=sc)
         ws = w if sc is None else w * sc[:, None, None, None]
         wt = ws.flip(2, 3).permute(1, 0, 2, 3)
-        ops.PACK_BF16_KERNEL[0] = False
-        try:
-            old = ops.PackedConv(wt, 1, k - 1 - k // 2, torch.bfloat16)
-        finally:
-            ops.PACK_BF16_KERNEL[0] = True
-        assert (pd.Cout, pd.Cin, pd.KH, pd.Kpad, pd.padding) == (old.Cout, old.Cin, old.KH, old.Kpad, old.padding)
-        assert torch.equal(pd.w, old.w)
-        fo = old.frag_image()
-        assert (fo is None) == (pd.frag_image() is None) and (fo is None or torch.equal(pd.frag_image().reshape(-1), fo.reshape(-1)))
+        refd = wt.permute(0, 2, 3, 1).reshape(Cin, k * k * Cout).to(torch.bfloat16).contiguous()
+        assert (pd.Cout, pd.Cin, pd.KH, pd.Kpad, pd.padding) == (Cin, Cout, k, k * k * Cout, k - 1 - k // 2)
+        assert torch.equal(pd.w, refd)
+        fo = frag(refd, Cin, k * k * Cout)
+        assert (fo is None) == (pd.frag_image() is None) and (fo is None or torch.equal(pd.frag_image().reshape(-1), fo))
 
 
 MASK_CASES = [
@@ -505,24 +497,16 @@ def test_conv_wgrad_bf16_pixel_major_kernel_vs_fp64(case):
     ref = wz.grad
     xc = x.permute(0, 2, 3, 1).contiguous().cuda()
     dyc = dy.permute(0, 2, 3, 1).contiguous().cuda()
-    old = ops.wgrad_tn(True)
-    try:
-        got = ops.conv_wgrad_bf16(dyc, xc, (Cout, Cin, k, k), stride=stride)
-        acc = got.clone()
-        ops.conv_wgrad_bf16(dyc, xc, (Cout, Cin, k, k), out=acc, accumulate=True, stride=stride)
-        torch.cuda.synchronize()
-    finally:
-        ops.wgrad_tn(old)
+    got = ops.conv_wgrad_bf16(dyc, xc, (Cout, Cin, k, k), stride=stride)
+    acc = got.clone()
+    ops.conv_wgrad_bf16(dyc, xc, (Cout, Cin, k, k), out=acc, accumulate=True, stride=stride)
+    torch.cuda.synchronize()
     err = float((got.cpu().double() - ref).abs().max() / ref.abs().max())
     assert err <= 2e-4, 'pixel-major bf16 weight gradient vs fp64 on the same operands: %.3e of the max' % err
     assert torch.equal(acc, got + got)
     assert ops.conv_wgrad_bf16_supported((N, H, W, Cin), (Cout, Cin, k, k), stride, k // 2, maps_bf16=True)
     assert not ops.conv_wgrad_bf16_supported((N, H, W, Cin), (Cout, Cin, k, k), stride, k // 2) or (stride == 1 and Cin % 256 == 0)
     if Cin % 256 == 0 and stride == 1:
-        old = ops.wgrad_tn(False)
-        try:
-            nt = ops.conv_wgrad_bf16(dyc, xc, (Cout, Cin, k, k))
-            torch.cuda.synchronize()
-        finally:
-            ops.wgrad_tn(old)
+        nt = ops.conv_wgrad_bf16(dyc.float(), xc, (Cout, Cin, k, k))      # the rewriting path on the same operands (widening is exact)
+        torch.cuda.synchronize()
         assert float((got - nt).abs().max()) <= 2e-4 * float(ref.abs().max())

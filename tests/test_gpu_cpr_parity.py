@@ -171,7 +171,7 @@ def test_fused_forward_train_matches_module_by_module_path():
 @pytest.mark.parametrize('mode', ['fp32', 'bf16'])
 def test_fused_stem_kernels_and_the_two_kernel_fallback_agree_through_the_network(mode):
     """Round 4: ResNet.stem runs conv + BN + ReLU + max-pool as one kernel (csrc/stem_f32.hip; csrc/stem_bf16.hip in the bf16
-    compute mode); ``CPR_F32_STEM=0`` / ``CPR_BF16_STEM=0`` / ``CPR_BF16_STEM_POOL=0`` (module flags here) keep the implicit-GEMM
+    compute mode); ``resnet.F32_STEM`` / ``BF16_STEM`` / ``BF16_STEM_POOL`` set to False keep the implicit-GEMM
     stem + maxpool3x3s2.  Both paths must give the same network: stage outputs and losses within fp32 summation-order distance
     (fp32 mode) resp. the bf16 mode's own rounding (one bf16 rounding of the stem inputs), and the bf16 fused pool the SAME bits as
     its unfused pair."""

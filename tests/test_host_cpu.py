@@ -37,6 +37,9 @@ def test_library_exports_every_declared_symbol():
     out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = set(re.findall(r'\b(cpr_\w+)$', out, flags=re.M))
     assert exported == declared, exported ^ declared
+    # nor does it read the environment: which kernel a call runs is a function of its arguments alone
+    undefined = subprocess.run(['nm', '-D', '--undefined-only', _lib.LIB_PATH], capture_output=True, text=True).stdout
+    assert not re.search(r'\bgetenv\b', undefined), 'libcprhip.so imports getenv'
 
 
 def test_product_package_never_imports_the_oracle():
