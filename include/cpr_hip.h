@@ -386,7 +386,8 @@ int cpr_conv3x3_wino_wgrad_workspace(int N, int H, int W, int Cin, int Cout);
 int cpr_conv3x3_wino_wgrad(const float* dy, const float* x, const float* in_a, const float* in_b, float* grad_w, float* ws,
                            int N, int H, int W, int Cin, int Cout, int in_relu, int accumulate, void* stream);
 /* nn.GroupNorm (+ReLU) backward from the raw conv output x, the forward affine a,b (N,C), mean/rstd (N,G):
- * dx (N,HW,C), dgamma/dbeta (C).  ws_part N*P*C*2 floats, ws_k 2*N*G + 2*N*C floats. */
+ * dx (N,HW,C), dgamma/dbeta (C).  ws_part N*P*C*2 floats, ws_k 2*N*G + 2*N*C floats.
+ * N, HW, P > 0; C % 4 == 0 with C / 4 dividing 256; G > 0 dividing C (any C / G >= 1); anything else is CPR_ERR_ARG. */
 int cpr_gn_bwd(const float* x, const float* dz, const float* a, const float* b, const float* mean, const float* rstd,
                const float* gamma, float* dx, float* dgamma, float* dbeta, float* ws_part, float* ws_k, int N, int HW,
                int C, int G, int P, int relu, int accumulate, void* stream);

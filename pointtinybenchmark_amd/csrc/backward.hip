@@ -173,7 +173,8 @@ static int gn_bwd_launch(const void* x, const void* dz, const float* a, const fl
                          float* ws_k, int N, int HW, int C, int G, int P, int relu, int accumulate, hipStream_t stream) {
     // ws_part: N*P*C*2 floats; ws_k: 2*N*G + 2*N*C floats (k2 | k3 | per-image dgamma/dbeta contributions)
     CPR_CHECK_ARG(x && dz && a && b && mean && rstd && gamma && (dx || dx16) && dgamma && dbeta && ws_part && ws_k);
-    CPR_CHECK_ARG(N > 0 && HW > 0 && G > 0 && P > 0 && C % G == 0 && (C / G) % 4 == 0 || (C / G) >= 1);
+    // any cpg = C / G >= 1 serves: the kernels derive the group per channel (a thread's four channels may span groups)
+    CPR_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && P > 0 && C % G == 0);
     CPR_CHECK_ARG(C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0);
     float* k2 = ws_k;
     float* k3 = ws_k + (size_t)N * G;
@@ -245,7 +246,7 @@ __global__ void upsample_add_bwd_kernel(const float* __restrict__ dfine, float* 
 }
 extern "C" int cpr_upsample_add_bwd(const float* dfine, float* dcoarse, int N, int H, int W, int UH, int UW, int C,
                                     int accumulate, hipStream_t stream) {
-    CPR_CHECK_ARG(dfine && dcoarse && N > 0 && H > 0 && W > 0 && UH > 0 && UW > 0 && C % 4 == 0);
+    CPR_CHECK_ARG(dfine && dcoarse && N > 0 && H > 0 && W > 0 && UH > 0 && UW > 0 && C > 0 && C % 4 == 0);
     const long long total = (long long)N * UH * UW * (C / 4);
     const int grid = (int)(cdivll(total, 256) < 32768 ? cdivll(total, 256) : 32768);
     hipLaunchKernelGGL(upsample_add_bwd_kernel, dim3(grid), dim3(256), 0, stream, dfine, dcoarse, N, H, W, UH, UW, C / 4,
@@ -530,7 +531,7 @@ __global__ void zero_insert_kernel(const float* __restrict__ dy, float* __restri
 }
 extern "C" int cpr_zero_insert(const float* dy, float* out, int N, int OH, int OW, int C, int H, int W, int s,
                                hipStream_t stream) {
-    CPR_CHECK_ARG(dy && out && N > 0 && OH > 0 && OW > 0 && C % 4 == 0 && H > 0 && W > 0 && s >= 1);
+    CPR_CHECK_ARG(dy && out && N > 0 && OH > 0 && OW > 0 && C > 0 && C % 4 == 0 && H > 0 && W > 0 && s >= 1);
     const long long total = (long long)N * H * W * (C / 4);
     const int grid = (int)(cdivll(total, 256) < 32768 ? cdivll(total, 256) : 32768);
     hipLaunchKernelGGL(zero_insert_kernel, dim3(grid), dim3(256), 0, stream, dy, out, N, OH, OW, C / 4, H, W, s);

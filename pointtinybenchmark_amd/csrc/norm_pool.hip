@@ -155,7 +155,7 @@ __global__ void gn_stats_kernel(const float* __restrict__ x, float* __restrict__
 
 extern "C" int cpr_gn_stats(const float* x, float* part, int N, int HW, int C, int P, hipStream_t stream) {
     CPR_CHECK_ARG(x && part && N > 0 && HW > 0 && P > 0);
-    CPR_CHECK_ARG(C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0);
+    CPR_CHECK_ARG(C > 0 && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0);
     hipLaunchKernelGGL(gn_stats_kernel, dim3(P, N), dim3(256), 0, stream, x, part, HW, C, P);
     CPR_LAUNCH_STATUS();
 }
@@ -396,7 +396,7 @@ __global__ void gn_stats_bf16_kernel(const unsigned short* __restrict__ x, float
 }
 extern "C" int cpr_gn_stats_bf16(const void* x, float* part, int N, int HW, int C, int P, hipStream_t stream) {
     CPR_CHECK_ARG(x && part && N > 0 && HW > 0 && P > 0);
-    CPR_CHECK_ARG(C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0);
+    CPR_CHECK_ARG(C > 0 && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0);
     hipLaunchKernelGGL(gn_stats_bf16_kernel, dim3(P, N), dim3(256), 0, stream, (const unsigned short*)x, part, HW, C, P);
     CPR_LAUNCH_STATUS();
 }
