@@ -433,6 +433,15 @@ int cpr_phase_scatter_add(const float* src, float* dst, int N, int Hs, int Ws, i
 /* out (N,H,W,C) = dy (N,OH,OW,C) with s-1 zeros inserted between pixels (data gradient of a stride-s conv as a
  * stride-1 conv over the dilated gradient) */
 int cpr_zero_insert(const float* dy, float* out, int N, int OH, int OW, int C, int H, int W, int s, void* stream);
+/* FPN extra pyramid levels (fpn.py:195-217; csrc/fpn_extra.hip), NHWC, 16 bytes of channels per lane.
+ * cpr_subsample2: out (N,(H+1)/2,(W+1)/2,C) = y[:, ::2, ::2, :] with y = x, or x*a[n,c] + b[n,c] when a/b (N,C) are given (the producer's
+ * pending GroupNorm affine, cpr_gn_apply's arithmetic) -- F.max_pool2d(y, 1, stride=2) bit for bit.  x/out fp32 (C%4==0) or bf16
+ * (x_bf16, C%8==0). */
+int cpr_subsample2(const void* x, int x_bf16, const float* a, const float* b, void* out, int N, int H, int W, int C, void* stream);
+/* its backward joined with the finer level's own gradient: out (N,H,W,C) = dfine + zero_insert(dcoarse (N,(H+1)/2,(W+1)/2,C)), one pass */
+int cpr_subsample2_bwd_add(const float* dfine, const float* dcoarse, float* out, int N, int H, int W, int C, void* stream);
+/* relu_before_extra_convs: out = dz + (y > 0 ? d : 0) on flat buffers of n floats (n%4==0); y fp32, or bf16 with y_bf16 */
+int cpr_relu_mask_add(const float* dz, const float* d, const void* y, int y_bf16, float* out, long long n, void* stream);
 /* d(gt_loss + pos_loss + neg_loss)/d(logit map) of CPRHead.loss (cpr_head.py:1101-1229): negative-grid term, MIL bag
  * and gt-centre terms taken back through the bilinear taps -- deterministically: every bag's taps are gathered into a
  * win x win cell window (win >= 2 * ceil(max |offset| / stride) + 3; win_ws (G, win, win, J) fp32 and win_org (G, 2) int32

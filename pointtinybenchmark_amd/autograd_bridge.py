@@ -11,7 +11,8 @@ chain have none: a raw map travels with a pending affine):
     image -> stem + frozen stages (no graph)
           -> _StageFn (layer2) -> _StageFn (layer3) -> _StageFn (layer4)          d(stage output) between them
           -> _LateralsFn: lateral 1x1 convs + GN + top-down adds -> the lateral sums the output convs read   d(lateral sums)
-          -> _HeadLossFn: FPN 3x3 output conv(s) + head towers + projection + point stage + losses -> the loss vector
+          -> _HeadLossFn: FPN 3x3 output conv(s) + extra pyramid levels + head towers + projection + point stage + losses -> the loss vector
+             (add_extra_convs='on_input': the last stage's output is one more input of it, d(stage output) comes back from it too)
 
 Every Function takes its trainable parameters as explicit inputs, so they sit in the autograd graph as leaves: gradient
 accumulators fire per Function -- the head's 9.4 MB of gradients (63 % of the backward's time) are final and on the wire while
@@ -22,7 +23,7 @@ pinned to ``loss.backward()`` through the reference's own modules by tests/golde
 Both compute modes (round 5: the bf16 mode = mixed precision, the reference analogue being mmcv's ``Fp16OptimizerHook`` around an
 unmodified ``loss.backward()``, T/mmdet/apis/train.py:116-119 -- see ``Bridge.carrier`` for how bf16 maps cross the Function
 boundaries), every CPRHead option set that runs forward (``CPRHead.train_step_supported``) with one FPN output level, P2PHead with any number of
-FPN output levels and points per cell, a frozen stem or the standard trainable one (conv1 7x7/2, 3 -> 64).  Anything else keeps
+FPN output levels (extra pyramid levels beyond the laterals included) and points per cell, a frozen stem or the standard trainable one (conv1 7x7/2, 3 -> 64).  Anything else keeps
 the forward-only path and warns once."""
 import os
 import warnings
@@ -64,8 +65,9 @@ class Bridge:
         self.lateral_params = [p for cm in neck.lateral_convs for p in cm.parameters() if p.requires_grad]
         self.head_params = [p for p in [q for cm in neck.fpn_convs for q in cm.parameters()] + list(head.parameters())
                             if p.requires_grad]
+        # add_extra_convs='on_input': the first extra conv reads the last backbone stage's output, one more differentiable input
+        self.extra_on_input = bool(getattr(neck, 'extra_levels', 0)) and neck.add_extra_convs == 'on_input'
         self.signature = signature(model)
-
 
     # ---- mixed precision (bf16 compute mode) behind the same Functions.  The recorded maps are bf16, the gradients the backward
     # kernels hand from segment to segment are fp32 -- and autograd casts a gradient to the dtype of the output it belongs to, so
@@ -94,7 +96,8 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     bb, neck, head = model.backbone, model.neck, model.bbox_head
     if neck is None or type(neck).__name__ != 'FPN' or len(neck.fpn_convs) < 1:
         return 'needs an FPN neck'
-    if len(neck.fpn_convs) != 1 and type(head).__name__ != 'P2PHead':
+    n_outs = min(len(neck.lateral_convs), neck.num_outs) + getattr(neck, 'extra_levels', 0)    # outputs, not fpn_convs: max-pool extras
+    if n_outs != 1 and type(head).__name__ != 'P2PHead':
         return 'needs an FPN neck with num_outs == 1 (every shipped CPR config; CPRHead asserts one level, cpr_head.py:487)'
     if bb.compute_dtype != torch.float32 and bb.batch_stats_active():
         return 'BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only, not with the bf16 compute mode'
@@ -119,8 +122,8 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     elif kind == 'P2PHead':
         if not getattr(head, 'train_cfg', None):
             return 'P2PHead trains with a train_cfg (the shipped P2P configs)'
-        if len(head.strides) != len(neck.fpn_convs):
-            return 'P2PHead needs one FPN output per stride (%d strides, num_outs %d)' % (len(head.strides), len(neck.fpn_convs))
+        if len(head.strides) != n_outs:
+            return 'P2PHead needs one FPN output per stride (%d strides, num_outs %d)' % (len(head.strides), n_outs)
     else:
         return 'no backward rules for head %s' % kind
     return None
@@ -229,12 +232,18 @@ class _HeadLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, bridge, pack, n_lat, *args):
+        """args: n_lat maps -- the lateral sums, then (a neck with add_extra_convs='on_input': ``bridge.extra_on_input``) the last
+        backbone stage's output, which the first extra conv reads --, then the parameters."""
         eng = bridge.engine
         lats, params = args[:n_lat], args[n_lat:]
-        lat = bridge.real(lats[0]) if n_lat == 1 else tuple(bridge.real(t) for t in lats)
+        kw = {}
+        if bridge.extra_on_input:
+            kw['extra_src'] = bridge.real(lats[-1])
+            lats = lats[:-1]
+        lat = bridge.real(lats[0]) if len(lats) == 1 else tuple(bridge.real(t) for t in lats)
         out, state = eng.forward_head_loss(lat, pack.img_metas, pack.gt_bboxes, pack.gt_labels,
-                                           pack.gt_bboxes_ignore, pack.gt_true_bboxes)
-        saved = state[1] if isinstance(state, tuple) and len(state) == 2 and isinstance(state[1], dict) else None
+                                           pack.gt_bboxes_ignore, pack.gt_true_bboxes, **kw)
+        saved = state[1] if isinstance(state, tuple) and len(state) in (2, 3) and isinstance(state[1], dict) else None
         if saved is not None and saved.get(eng.loss_vector_key) is out:
             saved[eng.loss_vector_key] = out.detach()
         ctx.bridge, ctx.state, ctx.params, ctx.n_lat = bridge, state, params, n_lat
@@ -247,7 +256,10 @@ class _HeadLossFn(torch.autograd.Function):
         assert ctx.state is not None, _CONSUMED
         # what torch hands over: d(total) / d(loss vector) -- ones where _parse_losses summed a term, zero on bag_acc; a scaled
         # total (loss scaling, gradient accumulation) arrives as that scale.  The loss-backward kernels multiply by it on the device
-        dlat = eng.backward_head_loss(ctx.state, gout.contiguous().float())
+        kw = {}
+        if ctx.bridge.extra_on_input:
+            kw['need_src'] = ctx.needs_input_grad[3 + ctx.n_lat - 1]
+        dlat = eng.backward_head_loss(ctx.state, gout.contiguous().float(), **kw)
         grads = eng.collect(ctx.params)
         ctx.state = None
         return (None, None, None) + (tuple(dlat) if ctx.n_lat > 1 else (dlat,)) + grads
@@ -285,6 +297,8 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
     xs = feats[neck.start_level:neck.start_level + len(neck.lateral_convs)]
     lat = _LateralsFn.apply(bridge, len(xs), *xs, *bridge.lateral_params)
     lats = tuple(lat) if isinstance(lat, (tuple, list)) else (lat,)
+    if bridge.extra_on_input:
+        lats = lats + (feats[neck.backbone_end_level - 1],)
     pack = _GtPack(img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
     out = _HeadLossFn.apply(bridge, pack, len(lats), *lats, *bridge.head_params)
     bridge._maps.clear()          # every forward consumer has run; the backward reads the tapes

@@ -1,6 +1,12 @@
 """FPN neck with the fork's ``num_outs`` < #levels behaviour (T/mmdet/models/necks/fpn.py:67-218; fork edits
 at :96,134,193): every lateral 1x1 conv + GN and the whole top-down nearest-upsample chain run, but only the
-first ``num_outs`` 3x3 output convs exist.  GroupNorm-apply and the top-down add are ONE fused pass per level."""
+first ``num_outs`` 3x3 output convs exist.  GroupNorm-apply and the top-down add are ONE fused pass per level.
+
+``num_outs`` > #levels (fpn.py:146-164, 195-217): the extra pyramid levels are stride-2 3x3 conv + GN modules appended to
+``fpn_convs`` (``add_extra_convs`` 'on_input' / 'on_lateral' / 'on_output'), or ``F.max_pool2d(outs[-1], 1, stride=2)`` without
+them (ops.subsample2)."""
+import warnings
+
 import torch.nn as nn
 
 from .. import ops
@@ -22,6 +28,20 @@ class FPN(nn.Module):
         self.num_ins = len(in_channels)
         self.backbone_end_level = self.num_ins if end_level == -1 else end_level
         self.start_level, self.end_level = start_level, end_level
+        self.relu_before_extra_convs = relu_before_extra_convs
+        if end_level != -1:     # if end_level < inputs, no extra level is allowed (fpn.py:98-101)
+            assert end_level <= len(in_channels)
+            assert num_outs <= end_level - start_level, 'extra pyramid levels need end_level == -1'
+        assert isinstance(add_extra_convs, (str, bool))
+        if isinstance(add_extra_convs, str):
+            assert add_extra_convs in ('on_input', 'on_lateral', 'on_output')
+        elif add_extra_convs:   # True (fpn.py:109-118)
+            if extra_convs_on_inputs:
+                warnings.warn("add_extra_convs=True with extra_convs_on_inputs is deprecated: pass add_extra_convs='on_input'",
+                              DeprecationWarning)
+                add_extra_convs = 'on_input'
+            else:
+                add_extra_convs = 'on_output'
         self.add_extra_convs = add_extra_convs
         self.lateral_convs = nn.ModuleList()
         self.fpn_convs = nn.ModuleList()
@@ -30,8 +50,12 @@ class FPN(nn.Module):
             if i < start_level + num_outs:  # fork change (fpn.py:134)
                 self.fpn_convs.append(ConvModule(out_channels, out_channels, 3, padding=1, norm_cfg=norm_cfg,
                                                  act_cfg=None))
-        extra = num_outs - self.backbone_end_level + start_level
-        assert extra < 1, 'extra pyramid levels are not used by the CPR/P2P configs (num_outs=1)'
+        # extra pyramid levels (fpn.py:146-164): conv modules under the next fpn_convs indices, or max-pool levels without parameters
+        self.extra_levels = max(0, num_outs - self.backbone_end_level + start_level)
+        if self.add_extra_convs:
+            for k in range(self.extra_levels):
+                cin = in_channels[self.backbone_end_level - 1] if k == 0 and self.add_extra_convs == 'on_input' else out_channels
+                self.fpn_convs.append(ConvModule(cin, out_channels, 3, stride=2, padding=1, norm_cfg=norm_cfg, act_cfg=None))
         self._cache = _PackCache()
         self.init_weights()
 
@@ -70,7 +94,49 @@ class FPN(nn.Module):
             if tape is not None:
                 rec = dict(kind='out', level=i)
                 tape.append(rec)
-            outs.append(conv_gn(c, self.fpn_convs[i], lat[i], materialize=not lazy, save=rec, out_b8=out_b8 and lazy))
+            outs.append(conv_gn(c, self.fpn_convs[i], lat[i], materialize=not lazy, save=rec,
+                                out_b8=out_b8 and lazy and not self.extra_levels))
+        if self.extra_levels:
+            src = None if self.add_extra_convs != 'on_input' else ops.from_nchw(inputs[self.backbone_end_level - 1])
+            outs += self.run_extras(outs[-1], lat[-1], src, lazy, tape)
+        return outs
+
+    def run_extras(self, last, lat_last, src, lazy, tape=None):
+        """The extra pyramid levels (fpn.py:195-217) behind the last regular output ``last`` (lazy: (raw, (a, b)), else the
+        materialised map), the coarsest lateral sum ``lat_last`` and, for 'on_input', the last backbone map ``src`` -> their
+        outputs in ``last``'s form.  Max-pool levels are pure selections, which commute with the per-(image, channel) affine:
+        a lazy level is the subsampled raw map with its producer's affine.  An extra conv has stride 2, where no conv kernel
+        applies a pending affine on load: it reads the materialised map (with the ReLU of ``relu_before_extra_convs`` from the
+        second extra conv on)."""
+        c, outs, used = self._cache, [], len(self.lateral_convs)
+        if not self.add_extra_convs:
+            for k in range(self.extra_levels):
+                if tape is not None:
+                    tape.append(dict(kind='pool', level=used + k))
+                if lazy:
+                    last = (ops.subsample2(last[0]), last[1])
+                else:
+                    last = ops.subsample2(last)
+                outs.append(last)
+            return outs
+        cur = None      # the previous extra conv's (raw, (a, b))
+        for k in range(self.extra_levels):
+            relu = k > 0 and self.relu_before_extra_convs
+            if k == 0 and self.add_extra_convs == 'on_input':
+                x = src
+            elif k == 0 and self.add_extra_convs == 'on_lateral':
+                x = lat_last
+            elif k == 0 and not lazy:
+                x = last
+            else:
+                raw, (a, b) = last if k == 0 else cur
+                x = ops.gn_apply(raw, a, b, relu=relu)
+            rec = None
+            if tape is not None:
+                rec = dict(kind='extra', level=used + k, index=k, relu_in=relu)
+                tape.append(rec)
+            cur = conv_gn(c, self.fpn_convs[used + k], x, materialize=False, save=rec)
+            outs.append(cur if lazy else ops.gn_apply(cur[0], cur[1][0], cur[1][1]))
         return outs
 
     def forward(self, inputs):

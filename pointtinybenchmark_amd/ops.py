@@ -1389,6 +1389,34 @@ def upsample_add_bwd(dfine, dcoarse_or_shape, accumulate=True):
     return dc
 
 
+def subsample2(x, a=None, b=None):
+    """F.max_pool2d(y, 1, stride=2) of an NHWC map (fp32 or bf16): y = x, or x*a[n,c] + b[n,c] -- a pending GroupNorm affine
+    applied on load, so a lazy FPN output is never materialised just to be subsampled (csrc/fpn_extra.hip)."""
+    N, H, W, C = _check(x, ACT).shape
+    assert (a is None) == (b is None)
+    out = torch.empty((N, (H + 1) // 2, (W + 1) // 2, C), device=x.device, dtype=x.dtype)
+    _lib.call('cpr_subsample2', _ptr(x), int(x.dtype == torch.bfloat16), _ptr(a), _ptr(b), _ptr(out), N, H, W, C, _stream())
+    return out
+
+
+def subsample2_bwd_add(dfine, dcoarse):
+    """dfine + zero_insert(dcoarse): the gradient of a max-pool extra level joins the finer output's own, one pass."""
+    N, H, W, C = _check(dfine).shape
+    assert tuple(_check(dcoarse).shape) == (N, (H + 1) // 2, (W + 1) // 2, C), (dfine.shape, dcoarse.shape)
+    out = torch.empty_like(dfine)
+    _lib.call('cpr_subsample2_bwd_add', _ptr(dfine), _ptr(dcoarse), _ptr(out), N, H, W, C, _stream())
+    return out
+
+
+def relu_mask_add(dz, d, y):
+    """dz + (y > 0 ? d : 0) (relu_before_extra_convs: y is the map the next extra conv read, fp32 or bf16)."""
+    assert dz.shape == d.shape == y.shape and _check(y, ACT).is_contiguous()
+    out = torch.empty_like(_check(dz))
+    _lib.call('cpr_relu_mask_add', _ptr(dz), _ptr(_check(d)), _ptr(y), int(y.dtype == torch.bfloat16), _ptr(out), dz.numel(),
+              _stream())
+    return out
+
+
 def relu_bwd_colsum(dy, y=None, want_g=True, colsum=None, want16=False, add=None):
     """g = dy*(y>0) (y None: g = dy) and per-channel column sums of g -> (g|None, colsum (C)[, g16]).  y fp32 or the bf16 map the
     mixed-precision forward recorded (read as it is); want16: also the bf16 rounding of g, written by the same pass; add (fp32, same

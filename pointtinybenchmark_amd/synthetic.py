@@ -84,7 +84,11 @@ def resnet_state_dict(depth=50, seed=0, prefix='backbone.'):
     return sd
 
 
-def fpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=1, seed=1, prefix='neck.'):
+def fpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=1, seed=1, prefix='neck.', add_extra_convs=False,
+                   extra_convs_on_inputs=True):
+    """add_extra_convs (False / True / 'on_input' / 'on_lateral' / 'on_output', as FPN takes it): the stride-2 convs of the
+    num_outs - (len(in_channels) - start_level) extra pyramid levels, under the next fpn_convs indices, drawn after the regular
+    levels (so the regular weights of a seed do not depend on them)."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
     for j, i in enumerate(range(start_level, len(in_channels))):
@@ -93,6 +97,13 @@ def fpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=1, see
         if i < start_level + num_outs:
             sd['%sfpn_convs.%d.conv.weight' % (prefix, j)] = _xavier_uniform((out_channels, out_channels, 3, 3), g)
             _gn(sd, '%sfpn_convs.%d.gn' % (prefix, j), out_channels, g)
+    if add_extra_convs is True:
+        add_extra_convs = 'on_input' if extra_convs_on_inputs else 'on_output'
+    levels = len(in_channels) - start_level
+    for k in range(num_outs - levels if add_extra_convs else 0):
+        cin = in_channels[-1] if k == 0 and add_extra_convs == 'on_input' else out_channels
+        sd['%sfpn_convs.%d.conv.weight' % (prefix, levels + k)] = _xavier_uniform((out_channels, cin, 3, 3), g)
+        _gn(sd, '%sfpn_convs.%d.gn' % (prefix, levels + k), out_channels, g)
     return sd
 
 

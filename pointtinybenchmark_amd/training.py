@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from ._lib import CprHipError
 from .layers import _PackCache, bn_inv_sigma, bump_weight_epoch, dgrad_packed, folded_bn
 
 
@@ -364,7 +365,7 @@ class BackwardEngine:
         tape = []
         neck = self.model.neck
         lat = neck.run_laterals(list(xs), tape)
-        n = len(neck.fpn_convs)
+        n = min(len(lat), neck.num_outs)        # the regular output convs (fpn_convs may hold extra levels behind them)
         return (lat[0] if n == 1 else tuple(lat[:n])), {r['level']: r for r in tape}
 
     def backward_laterals(self, recs, dlat, need):
@@ -373,21 +374,38 @@ class BackwardEngine:
         d_stage = self._backward_laterals(neck, recs, dlat, need_dx_of=lambda stage: need[stage - neck.start_level])
         return [d_stage.get(i + neck.start_level) for i in range(len(need))]
 
-    def forward_head_loss(self, lat, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_true_bboxes=None):
-        """FPN output conv(s) (lazy) -> head -> losses: returns the loss vector of the loss kernels and the backward state.
-        lat: what forward_laterals returned (one lateral sum, or one per FPN output level)."""
+    def forward_head_loss(self, lat, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_true_bboxes=None, extra_src=None):
+        """FPN output conv(s) (lazy) -> extra pyramid levels -> head -> losses: returns the loss vector of the loss kernels and the
+        backward state.  lat: what forward_laterals returned (one lateral sum, or one per regular FPN output level).
+        extra_src: the last backbone stage's NHWC output, for a neck with add_extra_convs='on_input'."""
         from .layers import conv_gn
         neck, head = self.model.neck, self.model.bbox_head
         lats = list(lat) if isinstance(lat, (tuple, list)) else [lat]
         recs = [dict(kind='out', level=i) for i in range(len(lats))]
         lazy = [conv_gn(neck._cache, neck.fpn_convs[i], t, materialize=False, save=rec) for i, (t, rec) in enumerate(zip(lats, recs))]
+        extras = []
+        if getattr(neck, 'extra_levels', 0):
+            assert len(lats) == len(neck.lateral_convs) and (extra_src is not None) == (neck.add_extra_convs == 'on_input')
+            lazy += neck.run_extras(lazy[-1], lats[-1], extra_src, True, extras)
         _, saved = self._forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
-        return saved[self.loss_vector_key], (recs if isinstance(lat, (tuple, list)) else recs[0], saved)
+        rec = recs if isinstance(lat, (tuple, list)) else recs[0]
+        return saved[self.loss_vector_key], ((rec, saved, extras) if extras else (rec, saved))
 
-    def backward_head_loss(self, state, upstream):
-        """-> the gradient wrt the lateral sum(s) forward_head_loss read, in the same form."""
-        rec, saved = state
+    def backward_head_loss(self, state, upstream, need_src=True):
+        """-> the gradient wrt the lateral sum(s) forward_head_loss read, in the same form; with an 'on_input' neck a list: those
+        gradients, then the gradient wrt extra_src (None unless need_src)."""
+        rec, saved = state[:2]
         dz = self._backward_head(self.model.bbox_head, saved, upstream=upstream)
+        if len(state) == 3:
+            neck = self.model.neck
+            dzs, d_lat, d_src = self._backward_extras(neck, state[2], list(dz), need_src=need_src)
+            recs = rec if isinstance(rec, list) else [rec]
+            dlats = [self._backward_out_conv(r, d) for r, d in zip(recs, dzs)]
+            if d_lat is not None:
+                dlats[-1] = ops.axpby(dlats[-1], d_lat, 1.0, 1.0)
+            if neck.add_extra_convs == 'on_input':
+                return dlats + [d_src]
+            return dlats if isinstance(rec, list) else dlats[0]
         if isinstance(rec, list):
             return [self._backward_out_conv(r, d) for r, d in zip(rec, dz)]
         return self._backward_out_conv(rec, dz)
@@ -465,7 +483,16 @@ class BackwardEngine:
         if wgrad16:
             x = rec['x']       # the weight gradient on the bf16 matrix pipe, straight from the recorded map
             gw = self._g(w)
-            self._param_side(lambda: ops.conv_wgrad_bf16(d16, x, w.shape, out=gw, stride=cm.conv.stride[0]), d16, x)
+            stride, pad = cm.conv.stride[0], cm.conv.padding[0]
+
+            def wgrad16_or_fp32():      # a shape the bf16 entry point refuses after all takes the fp32 kernel on the widened maps
+                try:
+                    ops.conv_wgrad_bf16(d16, x, w.shape, out=gw, stride=stride)
+                except CprHipError as e:
+                    if 'unsupported configuration' not in str(e):
+                        raise
+                    ops.conv2d_wgrad(draw if draw is not None else d16.float(), x.float(), w.shape, stride, pad, out=gw)
+            self._param_side(wgrad16_or_fp32, d16, x, draw)
         else:
             x = self._f32(rec['x'])
             gw = self._g(w)
@@ -695,15 +722,56 @@ class BackwardEngine:
 
     # ------------------------------------------------------------------ FPN, backbone
     def _backward_neck(self, neck, neck_tape, dz):
-        """Output convs, then the top-down chain from the finest lateral to the coarsest -> {stage: d(stage output)}.
+        """Extra levels (last first), output convs, then the top-down chain from the finest lateral to the coarsest -> {stage: d(stage output)}.
         dz: gradient wrt the (normalised) FPN output -- one map (num_outs == 1), or a list with one per output level."""
         lat_recs = {r['level']: r for r in neck_tape if r['kind'] == 'lateral'}
         out_recs = {r['level']: r for r in neck_tape if r['kind'] == 'out'}
+        extra_recs = [r for r in neck_tape if r['kind'] in ('extra', 'pool')]
         dzs = list(dz) if isinstance(dz, (list, tuple)) else [dz]
-        assert sorted(out_recs) == list(range(len(dzs))), 'one gradient per FPN output level (%d outputs, %d gradients)' \
-            % (len(out_recs), len(dzs))
+        assert sorted(out_recs) == list(range(len(dzs) - len(extra_recs))), 'one gradient per FPN output level (%d outputs, %d gradients)' \
+            % (len(out_recs) + len(extra_recs), len(dzs))
+        dzs, d_lat, d_src = self._backward_extras(neck, extra_recs, dzs)
         dlats = [self._backward_out_conv(out_recs[i], d) for i, d in enumerate(dzs)]     # fpn_convs in the flat order
-        return self._backward_laterals(neck, lat_recs, dlats)
+        if d_lat is not None:
+            dlats[-1] = ops.axpby(dlats[-1], d_lat, 1.0, 1.0)
+        d_stage = self._backward_laterals(neck, lat_recs, dlats)
+        if d_src is not None:
+            stage = neck.backbone_end_level - 1
+            d_stage[stage] = d_src if d_stage.get(stage) is None else ops.axpby(d_stage[stage], d_src, 1.0, 1.0)
+        return d_stage
+
+    def _backward_extras(self, neck, recs, dzs, need_src=None):
+        """The extra pyramid levels, last first (T/mmdet/models/necks/fpn.py:195-217).  dzs: one gradient per output level, the extras'
+        last.  -> (the regular levels' gradients -- the last one joined by what flows down from 'on_output' / max-pool extras --,
+        the gradient an 'on_lateral' extra adds to the coarsest lateral sum | None, the gradient an 'on_input' extra adds to the last
+        backbone stage's output | None: that stage is frozen -- need_src overrides).
+        Max-pool chain: dz + zi(d1 + zi(d2 + ..)), one pass per level.  relu_before_extra_convs: the level feeding the next extra
+        conv receives dz + (y > 0 ? d : 0) (ops.relu_mask_add on the recorded, activated input)."""
+        if not recs:
+            return dzs, None, None
+        n = len(dzs) - len(recs)
+        dzs = list(dzs)
+        d_lat = d_src = None
+        for k in range(len(recs) - 1, -1, -1):
+            rec, d = recs[k], dzs[n + k]
+            if rec['kind'] == 'pool':
+                dzs[n + k - 1] = ops.subsample2_bwd_add(dzs[n + k - 1], d)
+                continue
+            src = neck.add_extra_convs if k == 0 else 'on_output'
+            need_dx = True
+            if src == 'on_input':
+                need_dx = self._stage_trainable(neck.backbone_end_level - 1) if need_src is None else bool(need_src)
+            dx = self._gn_conv_backward(rec, d, relu=False, need_dx=need_dx)
+            self._done(rec['module'].conv.weight)
+            if src == 'on_input':
+                d_src = dx
+            elif src == 'on_lateral':
+                d_lat = dx
+            elif rec['relu_in']:
+                dzs[n + k - 1] = ops.relu_mask_add(dzs[n + k - 1], dx, rec['x'])
+            else:
+                dzs[n + k - 1] = ops.axpby(dx, dzs[n + k - 1], 1.0, 1.0)
+        return dzs[:n], d_lat, d_src
 
     def _backward_out_conv(self, rec, dz):
         """FPN output conv (3x3 + GN, no activation): dz wrt its normalised output -> gradient wrt the finest lateral sum."""
@@ -1230,7 +1298,10 @@ class CprTrainer(BackwardEngine):
                 if p is not None and p.requires_grad and all(p is not q for q in out):
                     out.append(p)
         self._head_param_order(head, add)
-        for cm in neck.fpn_convs:
+        regular = min(len(neck.lateral_convs), neck.num_outs)
+        for cm in reversed(list(neck.fpn_convs)[regular:]):      # the extra levels' convs, last first (_backward_extras)
+            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+        for cm in list(neck.fpn_convs)[:regular]:
             add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
         for cm in neck.lateral_convs:
             add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
