@@ -608,6 +608,33 @@ int cpr_preprocess_u8(const unsigned char* img, const int* flip, const float* me
 int cpr_clip_flip_boxes(float* boxes, const int* img_of, const int* flip, const int* img_hw, int n, int clip,
                         void* stream);
 
+/* Resize in all its forms and the test-time wrappers (MultiScaleFlipAug, the fork's CroppedTilesFlipAug) in front of the same tail:
+ *   crop -> cv2.resize(INTER_LINEAR) of the uint8 image -> horizontal flip -> Normalize -> Pad -> (Hp, Wp, 4) fp32
+ * ONE launch for a table of jobs: a ragged training batch, or all tiles x scales x flips of one test image (tiles are crop
+ * rectangles of one upload).  The resize is OpenCV's 8-bit fixed-point bilinear (11-bit coefficients, x taps clamped with their
+ * coefficient, y rows clamped; csrc/preprocess.hip restates it), so an identity size returns the source exactly.
+ * A job: `src` device address of pixel (0,0) of a decoded uint8 HWC BGR image of src_w x src_h with `pitch` bytes per row; crop
+ * (x0, y0, cw, ch) inside it; resized size (dw, dh); scale_x = 1. / ((double)dw / cw), scale_y likewise (double, set by the host);
+ * flip; out_off = first pixel of its slot in `out`, in pixels; (Hp, Wp) >= (dh, dw) its padded size.  Every job writes its whole
+ * slot (zeros outside dh x dw and in the 4th channel). */
+typedef struct cpr_preprocess_job {
+    const unsigned char* src;
+    long long out_off;
+    double scale_x, scale_y;
+    int pitch, src_w, src_h, x0, y0, cw, ch, dw, dh, flip, Hp, Wp;
+} cpr_preprocess_job;
+/* jobs_dev: n_jobs records ON THE DEVICE (n_jobs <= 65535; 0 is a no-op); mean3 / stdinv3 HOST pointers as for cpr_preprocess_u8;
+ * out holds total_out_pixels (< 2^31) pixels of 4 floats.  CPR_ERR_ARG for a null table / output or a bad count.  The table is device
+ * memory, so a job's geometry is checked where it is read: a job whose crop leaves its image or whose slot leaves `out` writes nothing
+ * (ops.preprocess_jobs refuses it on the host copy, with the same error, before the upload). */
+int cpr_preprocess_jobs_u8(const void* jobs_dev, int n_jobs, const float* mean3, const float* stdinv3, int to_rgb, float* out,
+                           long long total_out_pixels, void* stream);
+/* Box side of Resize -> RandomFlip at any scale, in place: box * scale4[img] in fp32 (the float32 scale_factor array of
+ * Resize._resize_img; one rounding per coordinate), clip to the RESIZED img_shape when `clip`, mirror when flip[img]
+ * (transforms.py:241-249, :397-415).  scale4 (N,4) fp32, img_hw (N,2) int32 = resized img_shape[:2]; the rest as cpr_clip_flip_boxes. */
+int cpr_scale_clip_flip_boxes(float* boxes, const int* img_of, const int* flip, const int* img_hw, const float* scale4, int n,
+                              int clip, void* stream);
+
 /* ---- measurement build only (-DCPR_BENCH_HOOKS; python -m pointtinybenchmark_amd.build --bench-hooks) ------------------
  * Process-global, not thread-safe switches used by the scripts under tools/ to A/B the conv kernels.  NOT part of the
  * product library. */

@@ -105,6 +105,8 @@ SIGNATURES = {
     # data side
     'cpr_preprocess_u8': [_p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
     'cpr_clip_flip_boxes': [_p, _p, _p, _p, _i, _i, _p],
+    'cpr_preprocess_jobs_u8': [_p, _i, _p, _p, _i, _p, _l, _p],
+    'cpr_scale_clip_flip_boxes': [_p, _p, _p, _p, _p, _i, _i, _p],
     'cpr_pack_weights': [_p, _p, _p] + [_i] * 7 + [_p],
     'cpr_pack_weights_bf16': [_p, _p, _p, _p] + [_i] * 5 + [_p],
     'cpr_spin': [ctypes.c_longlong, _p],

@@ -1663,3 +1663,58 @@ def adam_step(p, grad, exp_avg, exp_avg_sq, norm2, lr, betas, eps, weight_decay,
     _lib.call('cpr_adam_step', _ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(norm2), p.numel(), float(lr),
               beta1, beta2, float(eps), float(weight_decay), step_size, bc2_sqrt, float(max_norm), float(grad_scale),
               int(bool(decoupled)), _stream())
+
+
+# ---- data side: the job table of cpr_preprocess_jobs_u8 (include/cpr_hip.h: cpr_preprocess_job, 80 bytes) ----
+PREPROCESS_JOB = [('src', '<u8'), ('out_off', '<i8'), ('scale_x', '<f8'), ('scale_y', '<f8')] + \
+    [(k, '<i4') for k in ('pitch', 'src_w', 'src_h', 'x0', 'y0', 'cw', 'ch', 'dw', 'dh', 'flip', 'Hp', 'Wp')]
+
+
+def preprocess_job_table(jobs, total_out_pixels):
+    """Host copy of a job table, checked and completed: scale_x / scale_y = 1. / (dw / cw) in double (OpenCV's own expression).
+    The library only ever sees the table as device memory, so its geometry is checked here: a job that would read outside its image
+    or write outside the ``total_out_pixels`` of the output is an argument error."""
+    import numpy as np
+    jobs = np.ascontiguousarray(jobs, dtype=np.dtype(PREPROCESS_JOB)).copy()
+    if len(jobs):
+        j = {k: jobs[k].astype(np.int64) for k, _ in PREPROCESS_JOB if k not in ('scale_x', 'scale_y')}
+        ok = (jobs['src'] != 0) & (j['src_w'] > 0) & (j['src_h'] > 0) & (j['pitch'] >= 3 * j['src_w']) & (j['x0'] >= 0) & \
+            (j['y0'] >= 0) & (j['cw'] > 0) & (j['ch'] > 0) & (j['x0'] + j['cw'] <= j['src_w']) & (j['y0'] + j['ch'] <= j['src_h']) & \
+            (j['dw'] > 0) & (j['dh'] > 0) & (j['Hp'] >= j['dh']) & (j['Wp'] >= j['dw']) & (j['out_off'] >= 0) & \
+            (j['out_off'] + j['Hp'] * j['Wp'] <= total_out_pixels)
+        if not ok.all():
+            raise _lib.CprHipError('cpr_preprocess_jobs_u8: invalid argument (job %d)' % int(np.argmin(ok)))
+        jobs['scale_x'] = 1.0 / (jobs['dw'].astype(np.float64) / jobs['cw'].astype(np.float64))
+        jobs['scale_y'] = 1.0 / (jobs['dh'].astype(np.float64) / jobs['ch'].astype(np.float64))
+    return jobs
+
+
+def preprocess_jobs(jobs, mean3, stdinv3, to_rgb, out):
+    """crop -> cv2 fixed-point bilinear resize -> flip -> Normalize -> Pad for a table of jobs in ONE launch.  ``jobs``: host numpy
+    records of PREPROCESS_JOB (preprocess_job_table checks them and fills in the scales); ``out``: a contiguous fp32 device tensor
+    of 4-float pixels."""
+    import numpy as np
+    if _check(out).numel() % 4:
+        raise _lib.CprHipError('cpr_preprocess_jobs_u8: invalid argument (out holds 4-float pixels)')
+    total = out.numel() // 4
+    jobs = preprocess_job_table(jobs, total)
+    n = len(jobs)
+    table = torch.from_numpy(jobs.view(np.uint8).reshape(-1)).to(out.device) if n else None
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean3])
+    s = (ctypes.c_float * 3)(*[float(v) for v in stdinv3])
+    _lib.call('cpr_preprocess_jobs_u8', _ptr(table), n, ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
+              int(bool(to_rgb)), _ptr(out), total, _stream())
+    return out
+
+
+def scale_clip_flip_boxes(boxes, img_of, flips, img_hw, scale4, clip=True):
+    """In place: boxes (n,4) * scale4[img] -> clip to the resized img_hw[img] -> mirror when flips[img] (Resize then RandomFlip)."""
+    n = boxes.shape[0]
+    if n:
+        _check(boxes), _check(img_of, torch.int32), _check(flips, torch.int32), _check(img_hw, torch.int32), _check(scale4)
+        k = flips.numel()
+        if boxes.shape[1] != 4 or img_of.numel() != n or img_hw.numel() != 2 * k or scale4.numel() != 4 * k:
+            raise _lib.CprHipError('scale_clip_flip_boxes: boxes (n,4), img_of (n), flips (N), img_hw (N,2), scale4 (N,4)')
+    _lib.call('cpr_scale_clip_flip_boxes', _ptr(boxes), _ptr(img_of), _ptr(flips), _ptr(img_hw), _ptr(scale4), n, int(bool(clip)),
+              _stream())
+    return boxes
