@@ -165,6 +165,21 @@ int cpr_nhwc_to_nchw(const float* in, float* out, int N, int C, int H, int W, vo
 int cpr_stem7x7s2_pool_f32(const float* in, const float* wgt, const float* scale, const float* bias, float* out, int N, int H,
                            int W, int layout, void* stream);
 int cpr_maxpool3x3s2(const float* in, float* out, int N, int H, int W, int C, void* stream);
+/* The deep stem of ResNetV1d in exact fp32 (resnet.py:564-596, 630-638; csrc/stem_deep.hip): conv 3x3 / 2, 3 -> 32; conv 3x3, 32 -> 32;
+ * conv 3x3, 32 -> 64, each + folded BatchNorm + ReLU, then max-pool 3x3 / 2 / pad 1 in the third conv's epilogue.  in: layout 0 =
+ * (N,H,W,4) fp32 (4th channel ignored), layout 1 = (N,3,H,W) fp32 planes (same bits either way).  w1 (32, 64), w2 (32, 288),
+ * w3 (64, 288): the fp32 packs of cpr_pack_weights ([cout][kh][kw][cin'], cin' = 4 / 32 / 32); s* / b* the folded BatchNorms.  mid1, mid2: caller-allocated (N, OH, OW, 32) fp32, OH = (H-1)/2+1.  out (N, PH, PW, 64), PH = (OH-1)/2+1: fp32, or
+ * bf16 (out_bf16 = 1: one rounding of the fp32 result). */
+int cpr_stem_deep_fwd(const float* in, const float* w1, const float* s1, const float* b1, const float* w2, const float* s2,
+                      const float* b2, const float* w3, const float* s3, const float* b3, float* mid1, float* mid2, void* out, int N,
+                      int H, int W, int layout, int out_bf16, void* stream);
+/* nn.AvgPool2d(s, s, ceil_mode=True, count_include_pad=False) on NHWC maps (the avg_down shortcut, res_layer.py:39-60): in (N,H,W,C) ->
+ * out (N,ceil(H/s),ceil(W/s),C); a last window of an odd map divides by its in-map elements.  bf16 = 0: fp32 maps (C % 4 == 0),
+ * 1: bf16 maps (C % 8 == 0); fp32 accumulation in a fixed order; s >= 2. */
+int cpr_avgpool_fwd(const void* in, void* out, int N, int H, int W, int C, int s, int bf16, void* stream);
+/* its backward in gather form (no atomics): dx[h, w] = g[h/s, w/s] / count + add[h, w] (add optional: another gradient of the same
+ * map, the shape and type of dx) */
+int cpr_avgpool_bwd(const void* g, const void* add, void* dx, int N, int H, int W, int C, int s, int bf16, void* stream);
 /* Recording instances (training with a trainable stem): the same pooled map, bit for bit, and next to it arg (N, PH, PW, 64) uint8 =
  * the window position 0..8 (row-major) of each maximum, the first of tied positions (torch's max_pool2d rule), 255 where the pooled
  * value is 0 (the ReLU passes no gradient there).  The bf16 instances take the argmax of their own bf16-rounded values. */

@@ -46,6 +46,9 @@ SIGNATURES = {
     'cpr_nhwc_to_nchw': [_p, _p, _i, _i, _i, _i, _p],
     'cpr_stem7x7s2_pool_f32': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     'cpr_maxpool3x3s2': [_p, _p, _i, _i, _i, _i, _p],
+    'cpr_stem_deep_fwd': [_p] * 13 + [_i] * 5 + [_p],
+    'cpr_avgpool_fwd': [_p, _p] + [_i] * 6 + [_p],
+    'cpr_avgpool_bwd': [_p, _p, _p] + [_i] * 6 + [_p],
     'cpr_maxpool3x3s2_rec': [_p, _p, _p, _i, _i, _i, _i, _p],
     'cpr_maxpool3x3s2_bf16_rec': [_p, _p, _p, _i, _i, _i, _i, _p],
     'cpr_stem7x7s2_pool_f32_rec': [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],

@@ -23,7 +23,7 @@ pinned to ``loss.backward()`` through the reference's own modules by tests/golde
 Both compute modes (round 5: the bf16 mode = mixed precision, the reference analogue being mmcv's ``Fp16OptimizerHook`` around an
 unmodified ``loss.backward()``, T/mmdet/apis/train.py:116-119 -- see ``Bridge.carrier`` for how bf16 maps cross the Function
 boundaries), every CPRHead option set that runs forward (``CPRHead.train_step_supported``) with one FPN output level, P2PHead with any number of
-FPN output levels (extra pyramid levels beyond the laterals included) and points per cell, a frozen stem or the standard trainable one (conv1 7x7/2, 3 -> 64).  Anything else keeps
+FPN output levels (extra pyramid levels beyond the laterals included) and points per cell, a frozen stem (standard or deep) or the standard trainable one (conv1 7x7/2, 3 -> 64; a trainable deep stem is refused).  Anything else keeps
 the forward-only path and warns once."""
 import os
 import warnings
@@ -103,7 +103,7 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
         return 'BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only, not with the bf16 compute mode'
     if bb.compute_dtype != torch.float32 and type(head).__name__ not in ('CPRHead', 'P2PHead'):
         return 'the mixed-precision step (bf16 compute mode) covers the CPR and P2P locators'
-    if any(p.requires_grad for m in (bb.conv1, bb.bn1) for p in m.parameters()) and bb.stem_train_reason() is not None:
+    if any(p.requires_grad for p in bb.stem_parameters()) and bb.stem_train_reason() is not None:
         return bb.stem_train_reason()
     if tuple(bb.out_indices) != tuple(range(len(bb.res_layers))):
         return 'out_indices must name every stage'
@@ -283,7 +283,8 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
         x = _StemFn.apply(bridge, img.detach(), *bridge.stem_params)
     else:
         with torch.no_grad():
-            x = bb.stem(img)
+            # (ResNet.run_stem: with deep_stem ``bb.stem`` is the reference's Sequential; any other backbone runs its ``stem``)
+            x = (getattr(bb, 'run_stem', None) or bb.stem)(img)
     feats = []
     for i in range(len(bb.res_layers)):
         params = bridge.stage_params[i]

@@ -22,13 +22,14 @@ def _bn_not_mixed():
 
 
 class _Block(nn.Module):
-    def __init__(self, kind, inplanes, planes, stride, downsample, norm=nn.BatchNorm2d):
+    def __init__(self, kind, inplanes, planes, stride, downsample, norm=nn.BatchNorm2d, style='pytorch'):
         super().__init__()
         self.kind = kind
-        if kind == 'bottleneck':  # style='pytorch': the stride sits on the 3x3 (resnet.py:153-158)
-            self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
+        if kind == 'bottleneck':  # style='pytorch': the stride sits on the 3x3, 'caffe': on the first 1x1 (resnet.py:153-158)
+            s1, s2 = (1, stride) if style == 'pytorch' else (stride, 1)
+            self.conv1 = nn.Conv2d(inplanes, planes, 1, s1, bias=False)
             self.bn1 = norm(planes)
-            self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
+            self.conv2 = nn.Conv2d(planes, planes, 3, s2, 1, bias=False)
             self.bn2 = norm(planes)
             self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
             self.bn3 = norm(planes * 4)
@@ -39,9 +40,33 @@ class _Block(nn.Module):
             self.bn2 = norm(planes)
         self.downsample = downsample
 
+    # the projection shortcut: Sequential(conv 1x1 / stride, BN), or with avg_down Sequential(AvgPool2d(stride, ceil_mode,
+    # count_include_pad=False), conv 1x1 / 1, BN) (res_layer.py:39-60) -- the pool module is there at stride 1 too (the identity)
+    @property
+    def ds_conv(self):
+        return self.downsample[-2]
+
+    @property
+    def ds_bn(self):
+        return self.downsample[-1]
+
+    @property
+    def ds_pool(self):
+        """The window (= stride) of the shortcut's average pool when it does anything: avg_down and stride > 1; else 0."""
+        if self.downsample is None or len(self.downsample) != 3:
+            return 0
+        k = self.downsample[0].kernel_size
+        k = k if isinstance(k, int) else k[0]
+        return k if k > 1 else 0
+
+    def shortcut_input(self, x):
+        """What the projection shortcut's conv reads: the block input, or with avg_down its average-pooled map (ops.avgpool)."""
+        k = self.ds_pool
+        return ops.avgpool(x, k) if k else x
+
     def _norms(self):
         return [self.bn1, self.bn2] + ([self.bn3] if self.kind == 'bottleneck' else []) + \
-            ([self.downsample[1]] if self.downsample is not None else [])
+            ([self.ds_bn] if self.downsample is not None else [])
 
     def batch_stats(self):
         """True when this block's BatchNorms normalise with batch statistics (training mode, norm_eval=False, stage not frozen)."""
@@ -60,9 +85,10 @@ class _Block(nn.Module):
         # forward-only fp32 bottleneck with a projection shortcut: the shortcut GEMM rides in conv3's launch (bit-identical,
         # ops.conv2d_dual); the training step keeps the two launches (its backward walks the recorded maps)
         fuse_shortcut = self.downsample is not None and save is None and self.kind == 'bottleneck' and dt == torch.float32
+        xp = self.shortcut_input(x) if self.downsample is not None else None      # avg_down: the pooled map (the record keeps it)
         if self.downsample is not None and not fuse_shortcut:
-            s, b = folded_bn(cache, self.downsample[1])
-            identity = ops.conv2d(x, packed_conv(cache, self.downsample[0], x.dtype), scale=s, bias=b)
+            s, b = folded_bn(cache, self.ds_bn)
+            identity = ops.conv2d(xp, packed_conv(cache, self.ds_conv, x.dtype), scale=s, bias=b)
         s1, b1 = folded_bn(cache, self.bn1)
         o1 = ops.conv2d(x, packed_conv(cache, self.conv1, dt), scale=s1, bias=b1, relu=True)
         s2, b2 = folded_bn(cache, self.bn2)
@@ -70,8 +96,8 @@ class _Block(nn.Module):
             o2 = ops.conv2d(o1, packed_conv(cache, self.conv2, dt), scale=s2, bias=b2, relu=True)
             s3, b3 = folded_bn(cache, self.bn3)
             if fuse_shortcut:
-                sd, bd = folded_bn(cache, self.downsample[1])
-                out = ops.conv2d_dual(o2, packed_conv(cache, self.conv3, dt), x, packed_conv(cache, self.downsample[0], dt),
+                sd, bd = folded_bn(cache, self.ds_bn)
+                out = ops.conv2d_dual(o2, packed_conv(cache, self.conv3, dt), xp, packed_conv(cache, self.ds_conv, dt),
                                       scale=s3, bias=b3, scale2=sd, bias2=bd, relu=True)
             else:
                 out = ops.conv2d(o2, packed_conv(cache, self.conv3, dt), scale=s3, bias=b3, residual=identity, relu=True)
@@ -79,7 +105,7 @@ class _Block(nn.Module):
             o2 = None
             out = ops.conv2d(o1, packed_conv(cache, self.conv2, dt), scale=s2, bias=b2, residual=identity, relu=True)
         if save is not None:
-            save.update(block=self, x=x, o1=o1, o2=o2, identity=identity, out=out)
+            save.update(block=self, x=x, xp=xp, o1=o1, o2=o2, identity=identity, out=out)
         return out
 
     def _run_batch_stats(self, cache, x, save):
@@ -99,9 +125,10 @@ class _Block(nn.Module):
         y1, t1 = conv_stats('bn1', self.conv1, self.bn1, x)
         o1 = ops.bn_apply(y1, t1.scale, t1.cshift, center=t1.center, relu=True)
         y2, t2 = conv_stats('bn2', self.conv2, self.bn2, o1)
-        yd = o2 = y3 = None
+        yd = o2 = y3 = xp = None
         if self.downsample is not None:
-            yd, td = conv_stats('bnd', self.downsample[0], self.downsample[1], x)
+            xp = self.shortcut_input(x)
+            yd, td = conv_stats('bnd', self.ds_conv, self.ds_bn, xp)
         if self.kind == 'bottleneck':
             o2 = ops.bn_apply(y2, t2.scale, t2.cshift, center=t2.center, relu=True)
             y3, tl = conv_stats('bn3', self.conv3, self.bn3, o2)
@@ -114,8 +141,19 @@ class _Block(nn.Module):
         else:
             out = ops.bn_apply(yl, tl.scale, tl.cshift, center=tl.center, residual=x, relu=True)
         if save is not None:
-            save.update(block=self, x=x, o1=o1, o2=o2, out=out, y1=y1, y2=y2, y3=y3, yd=yd, stats=stats, batch_stats=True)
+            save.update(block=self, x=x, xp=xp, o1=o1, o2=o2, out=out, y1=y1, y2=y2, y3=y3, yd=yd, stats=stats, batch_stats=True)
         return out
+
+
+class _StemAttr:
+    """``ResNet.stem``: with deep_stem the stem's Sequential, the reference's attribute and state-dict prefix (resnet.py:566); on the
+    standard net, which has no such module, the name stays what it was here -- the method that runs the stem (``run_stem``)."""
+
+    def __get__(self, obj, cls):
+        if obj is None:
+            return self
+        m = obj._modules.get('stem')
+        return m if m is not None else obj.run_stem
 
 
 F32_STEM = [True]         # False: stem conv on the implicit-GEMM kernel + separate max-pool (tests)
@@ -128,6 +166,8 @@ class ResNet(nn.Module):
     arch_settings = {18: ('basic', (2, 2, 2, 2)), 34: ('basic', (3, 4, 6, 3)), 50: ('bottleneck', (3, 4, 6, 3)),
                      101: ('bottleneck', (3, 4, 23, 3)), 152: ('bottleneck', (3, 8, 36, 3))}
 
+    stem = _StemAttr()
+
     def __init__(self, depth, in_channels=3, stem_channels=None, base_channels=64, num_stages=4,
                  strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1), out_indices=(0, 1, 2, 3), style='pytorch',
                  deep_stem=False, avg_down=False, frozen_stages=-1, conv_cfg=None,
@@ -136,20 +176,30 @@ class ResNet(nn.Module):
         super().__init__()
         if depth not in self.arch_settings:
             raise KeyError('invalid depth %s for resnet' % depth)
-        assert style == 'pytorch' and not deep_stem and not avg_down and dcn is None and plugins is None, \
-            'only the options used by the CPR/P2P configs are built (SURVEY.md §2a row 5)'
+        assert style in ('pytorch', 'caffe'), style
+        assert dcn is None and plugins is None and not with_cp, 'dcn, plugins and with_cp are not built (SURVEY.md §2a row 5)'
         assert tuple(dilations[:num_stages]) == (1,) * num_stages and norm_cfg.get('type') == 'BN'
+        if deep_stem and (stem_channels or base_channels) != 64:
+            raise NotImplementedError('deep_stem is built for stem_channels=64 (convs 3 -> 32 -> 32 -> 64, csrc/stem_deep.hip), not '
+                                      'stem_channels=%s' % (stem_channels or base_channels))
         bn_kw = {'momentum': norm_cfg['momentum']} if 'momentum' in norm_cfg else {}     # (mmcv build_norm_layer)
 
         def norm(c):
             return nn.BatchNorm2d(c, **bn_kw)
         self.depth, self.num_stages, self.out_indices = depth, num_stages, tuple(out_indices)
         self.frozen_stages, self.norm_eval = frozen_stages, norm_eval
+        self.style, self.deep_stem, self.avg_down = style, bool(deep_stem), bool(avg_down)
         kind, blocks = self.arch_settings[depth]
         exp = 4 if kind == 'bottleneck' else 1
         stem = stem_channels or base_channels
-        self.conv1 = nn.Conv2d(in_channels, stem, 7, 2, 3, bias=False)
-        self.bn1 = norm(stem)
+        if self.deep_stem:    # resnet.py:564-596: three 3x3 convs, BN + ReLU after each (the ReLU modules hold the indices 2, 5, 8)
+            self.stem = nn.Sequential(
+                nn.Conv2d(in_channels, stem // 2, 3, 2, 1, bias=False), norm(stem // 2), nn.ReLU(inplace=True),
+                nn.Conv2d(stem // 2, stem // 2, 3, 1, 1, bias=False), norm(stem // 2), nn.ReLU(inplace=True),
+                nn.Conv2d(stem // 2, stem, 3, 1, 1, bias=False), norm(stem), nn.ReLU(inplace=True))
+        else:
+            self.conv1 = nn.Conv2d(in_channels, stem, 7, 2, 3, bias=False)
+            self.bn1 = norm(stem)
         inplanes = stem
         self.res_layers = []
         for i in range(num_stages):
@@ -159,8 +209,12 @@ class ResNet(nn.Module):
                 stride = strides[i] if bi == 0 else 1
                 ds = None
                 if bi == 0 and (stride != 1 or inplanes != planes * exp):
-                    ds = nn.Sequential(nn.Conv2d(inplanes, planes * exp, 1, stride, bias=False), norm(planes * exp))
-                layer.append(_Block(kind, inplanes, planes, stride, ds, norm))
+                    if self.avg_down:     # res_layer.py:39-60 (the pool module is there at stride 1 as well: it shifts the keys)
+                        ds = nn.Sequential(nn.AvgPool2d(kernel_size=stride, stride=stride, ceil_mode=True, count_include_pad=False),
+                                           nn.Conv2d(inplanes, planes * exp, 1, 1, bias=False), norm(planes * exp))
+                    else:
+                        ds = nn.Sequential(nn.Conv2d(inplanes, planes * exp, 1, stride, bias=False), norm(planes * exp))
+                layer.append(_Block(kind, inplanes, planes, stride, ds, norm, style))
                 inplanes = planes * exp
             name = 'layer%d' % (i + 1)
             self.add_module(name, nn.Sequential(*layer))
@@ -174,10 +228,15 @@ class ResNet(nn.Module):
 
     def _freeze_stages(self):  # resnet.py:612-628
         if self.frozen_stages >= 0:
-            self.bn1.eval()
-            for m in (self.conv1, self.bn1):
-                for p in m.parameters():
+            if self.deep_stem:
+                self.stem.eval()
+                for p in self.stem.parameters():
                     p.requires_grad = False
+            else:
+                self.bn1.eval()
+                for m in (self.conv1, self.bn1):
+                    for p in m.parameters():
+                        p.requires_grad = False
         for i in range(1, self.frozen_stages + 1):
             m = getattr(self, 'layer%d' % i)
             m.eval()
@@ -195,8 +254,14 @@ class ResNet(nn.Module):
 
     def batch_stats_active(self):
         """True when some BatchNorm of this backbone normalises with batch statistics in the next forward."""
-        return (self.training and self.bn1.training) or any(blk.batch_stats() for name in self.res_layers
-                                                             for blk in getattr(self, name))
+        return (self.training and any(bn.training for bn in self.stem_norms())) or \
+            any(blk.batch_stats() for name in self.res_layers for blk in getattr(self, name))
+
+    def stem_norms(self):
+        return [self.stem[i] for i in (1, 4, 7)] if self.deep_stem else [self.bn1]
+
+    def stem_parameters(self):
+        return list(self.stem.parameters()) if self.deep_stem else list(self.conv1.parameters()) + list(self.bn1.parameters())
 
     def _check_mode(self):
         if self.compute_dtype != torch.float32 and self.batch_stats_active():
@@ -225,6 +290,8 @@ class ResNet(nn.Module):
     def stem_train_reason(self):
         """None when the stem has a backward rule (the standard stem: conv1 7x7 / stride 2 / pad 3, 3 -> 64, no bias, + bn1 + ReLU +
         the 3x3 / 2 max-pool, csrc/stem_bwd.hip), else why not, naming the shape."""
+        if self.deep_stem:
+            return 'a trainable deep stem (deep_stem=True with frozen_stages=-1) has no backward rule: freeze it (frozen_stages >= 0)'
         c1 = self.conv1
         if not all(p.requires_grad for p in getattr(self, self.res_layers[0]).parameters()):
             return 'a trainable stem needs a trainable %s (its backward starts from that stage\'s input gradient)' % self.res_layers[0]
@@ -234,12 +301,14 @@ class ResNet(nn.Module):
         return 'a trainable stem has a backward rule for conv1 7x7 / stride 2 / pad 3, 3 -> 64 only, not for weight %s stride %s ' \
             'padding %s' % (tuple(c1.weight.shape), c1.stride, c1.padding)
 
-    def stem(self, x, tape=None):
+    def run_stem(self, x, tape=None):
         """(N,3,H,W) image -> the NHWC map after conv1 + bn1 + ReLU + max-pool (resnet.py:630-637).
         tape (list): when conv1 or bn1 trains, the recording pool instances run and one record (``stem=True``) is appended: the input as the
         kernels read it, the argmax byte map of the pool (csrc/stem_bwd.hip reads both), and with batch statistics the raw conv map and
         its BnStats."""
         c = self._cache
+        if self.deep_stem:
+            return self._deep_stem(x, tape)
         c1 = self.conv1
         rec = None
         if tape is not None and any(p.requires_grad for p in (c1.weight, self.bn1.weight, self.bn1.bias)):
@@ -305,6 +374,25 @@ class ResNet(nn.Module):
             x = ops.conv2d(x, packed_conv(c, c1), scale=s, bias=b, relu=True, out_dtype=self.compute_dtype)
         return pool(x, x4, False)
 
+    def _deep_stem(self, x, tape=None):
+        """The deep stem (resnet.py:564-596): three conv3x3 + eval-BN + ReLU and the max-pool as csrc/stem_deep.hip runs them -- exact
+        fp32 in both compute modes, the bf16 mode rounds the pooled map once.  The fused 7x7 stems (F32_STEM / BF16_STEM) do not apply.
+        Forward only: a tape with trainable stem parameters raises stem_train_reason()."""
+        st = self.stem
+        if tape is not None and any(p.requires_grad for p in st.parameters()):
+            raise NotImplementedError(self.stem_train_reason())
+        if self.training and any(bn.training for bn in self.stem_norms()):
+            raise NotImplementedError('deep_stem with BatchNorm batch statistics in the stem (norm_eval=False and frozen_stages=-1): '
+                                      'the deep stem runs with eval-mode BatchNorm only')
+        c = self._cache
+        planar = x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] == 3 and x.is_contiguous()
+        if not planar:
+            # (N,3,H,W) float image -> NHWC4; a 4-channel channels-last view (datasets.GpuImagePipeline output) is taken as is
+            x = ops.from_nchw(x) if (x.shape[1] == 4 and x.stride(1) == 1) else ops.nchw_to_nhwc(x)
+        packs = [packed_conv(c, st[i]) for i in (0, 3, 6)]
+        folds = [folded_bn(c, st[i]) for i in (1, 4, 7)]
+        return ops.stem_deep(x, packs, folds, planar=planar, out_dtype=self.compute_dtype)
+
     def run_stage(self, i, x, tape=None):
         """Stage ``i`` (``layer{i+1}``) on an NHWC map.  tape (list): one record per block with trainable parameters."""
         self._check_mode()
@@ -320,10 +408,19 @@ class ResNet(nn.Module):
         """x: (N,3,H,W) -> tuple of NCHW-shaped (channels_last) stage outputs.
         tape (list): training mode -- one record per block with trainable parameters, in forward order."""
         self._check_mode()
-        x = self.stem(x, tape)
+        x = self.run_stem(x, tape)
         outs = []
         for i in range(len(self.res_layers)):
             x = self.run_stage(i, x, tape)
             if i in self.out_indices:
                 outs.append(ops.as_nchw(x))
         return tuple(outs)
+
+
+@BACKBONES.register_module()
+class ResNetV1d(ResNet):
+    """ResNetV1d (resnet.py:659-671): the 7x7 stem conv replaced by three 3x3 convs, and a 2x2 average pool before the (then
+    stride-1) 1x1 conv of every downsampling shortcut."""
+
+    def __init__(self, **kwargs):
+        super().__init__(deep_stem=True, avg_down=True, **kwargs)

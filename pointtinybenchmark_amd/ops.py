@@ -691,6 +691,52 @@ def maxpool3x3s2(x, record=False):
     return out
 
 
+def stem_deep(x, packs, folds, planar=None, out_dtype=torch.float32):
+    """The deep stem (ResNetV1d) in exact fp32 on the matrix cores (csrc/stem_deep.hip): x (N,H,W,4) NHWC4 or the (N,3,H,W) network
+    input -> (N,PH,PW,64) = maxpool3x3s2(the three conv3x3 + folded BN + ReLU layers).  packs: the fp32 PackedConv of the 3 -> 32 / 2,
+    32 -> 32 and 32 -> 64 convs; folds: their (scale, shift).  out_dtype bf16 (the bf16 compute mode): the same fp32 chain, the pooled
+    map rounded once.  Both input forms give the same bits."""
+    N, H, W, layout = _stem_input(_check(x), planar)
+    p1, p2, p3 = packs
+    for pc, shape in zip(packs, ((32, 4, 64, 2), (32, 32, 288, 1), (64, 32, 288, 1))):
+        assert pc.dtype == torch.float32 and (pc.Cout, pc.Cin, pc.Kpad, pc.stride) == shape and (pc.KH, pc.KW, pc.padding) == (3, 3, 1), \
+            'deep stem: conv3x3 3 -> 32 / 2, 32 -> 32, 32 -> 64, padding 1'
+        pack_ready(pc)
+    assert out_dtype in ACT
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    mid1 = torch.empty((N, OH, OW, 32), device=x.device, dtype=torch.float32)
+    mid2 = torch.empty_like(mid1)
+    out = torch.empty((N, (OH - 1) // 2 + 1, (OW - 1) // 2 + 1, 64), device=x.device, dtype=out_dtype)
+    (s1, b1), (s2, b2), (s3, b3) = folds
+    _lib.call('cpr_stem_deep_fwd', _ptr(x), _ptr(p1.w), _ptr(_check(s1)), _ptr(_check(b1)), _ptr(p2.w), _ptr(_check(s2)), _ptr(_check(b2)),
+              _ptr(p3.w), _ptr(_check(s3)), _ptr(_check(b3)), _ptr(mid1), _ptr(mid2), _ptr(out), N, H, W, layout,
+              int(out_dtype == torch.bfloat16), _stream())
+    return out
+
+
+def avgpool(x, s):
+    """nn.AvgPool2d(s, s, ceil_mode=True, count_include_pad=False) on an NHWC fp32 / bf16 map (the avg_down shortcut): a last window
+    of an odd map divides by its in-map elements; fp32 accumulation in a fixed order."""
+    N, H, W, C = _check(x, ACT).shape
+    assert s >= 2 and C % (8 if x.dtype == torch.bfloat16 else 4) == 0, (s, C)
+    out = torch.empty((N, -(-H // s), -(-W // s), C), device=x.device, dtype=x.dtype)
+    _lib.call('cpr_avgpool_fwd', _ptr(x), _ptr(out), N, H, W, C, s, int(x.dtype == torch.bfloat16), _stream())
+    return out
+
+
+def avgpool_bwd(g, in_hw, s, add=None):
+    """Backward of avgpool in gather form: g (N,ceil(H/s),ceil(W/s),C) -> dx (N,H,W,C) = g[h/s, w/s] / count (+ add: another gradient
+    of the pooled map's input, summed in the same pass -- the same bits as avgpool_bwd followed by axpby)."""
+    N, OH, OW, C = _check(g, ACT).shape
+    H, W = in_hw
+    assert s >= 2 and (OH, OW) == (-(-H // s), -(-W // s)) and C % (8 if g.dtype == torch.bfloat16 else 4) == 0, (tuple(g.shape), in_hw, s)
+    dx = torch.empty((N, H, W, C), device=g.device, dtype=g.dtype)
+    if add is not None:
+        assert _check(add, g.dtype).shape == dx.shape, (tuple(add.shape), tuple(dx.shape))
+    _lib.call('cpr_avgpool_bwd', _ptr(g), _ptr(add), _ptr(dx), N, H, W, C, s, int(g.dtype == torch.bfloat16), _stream())
+    return dx
+
+
 def stem_pool_bwd(dp, arg, conv_hw):
     """Backward of the stem's max-pool 3x3/2/1 and the ReLU before it: dp (N,PH,PW,64) fp32 (the pooled map's gradient) and the
     recorded arg map (uint8, same shape) -> (dy (N,OH,OW,64) fp32 = the gradient at the BatchNorm output, TilePartials of its column

@@ -52,12 +52,21 @@ def _gn(sd, prefix, c, g):
     sd[prefix + '.bias'] = torch.randn(c, generator=g) * 0.1
 
 
-def resnet_state_dict(depth=50, seed=0, prefix='backbone.'):
+def resnet_state_dict(depth=50, seed=0, prefix='backbone.', deep_stem=False, avg_down=False):
+    """deep_stem: the keys of the three-conv stem (``stem.0 / .3 / .6`` convs, ``stem.1 / .4 / .7`` norms) in place of conv1 / bn1;
+    avg_down: the projection shortcuts as ``downsample.1`` (conv) / ``downsample.2`` (norm) behind the parameter-free pool at index
+    0.  (style='caffe' moves a stride, no key.)  The defaults draw the tensors they always drew."""
     g = torch.Generator().manual_seed(seed)
     kind, blocks = ARCH[depth]
     sd = {}
-    sd[prefix + 'conv1.weight'] = _kaiming((64, 3, 7, 7), g)
-    _bn(sd, prefix + 'bn1', 64, g)
+    if deep_stem:
+        for i, (co, ci) in zip((0, 3, 6), ((32, 3), (32, 32), (64, 32))):
+            sd['%sstem.%d.weight' % (prefix, i)] = _kaiming((co, ci, 3, 3), g)
+            _bn(sd, '%sstem.%d' % (prefix, i + 1), co, g)
+    else:
+        sd[prefix + 'conv1.weight'] = _kaiming((64, 3, 7, 7), g)
+        _bn(sd, prefix + 'bn1', 64, g)
+    ds = (1, 2) if avg_down else (0, 1)
     inplanes = 64
     for li, nb in enumerate(blocks):
         planes = 64 * 2 ** li
@@ -78,8 +87,8 @@ def resnet_state_dict(depth=50, seed=0, prefix='backbone.'):
                 sd[p + 'conv2.weight'] = _kaiming((planes, planes, 3, 3), g)
                 _bn(sd, p + 'bn2', planes, g)
             if bi == 0 and (stride != 1 or inplanes != planes * exp):
-                sd[p + 'downsample.0.weight'] = _kaiming((planes * exp, inplanes, 1, 1), g)
-                _bn(sd, p + 'downsample.1', planes * exp, g)
+                sd[p + 'downsample.%d.weight' % ds[0]] = _kaiming((planes * exp, inplanes, 1, 1), g)
+                _bn(sd, p + 'downsample.%d' % ds[1], planes * exp, g)
             inplanes = planes * exp
     return sd
 
@@ -164,8 +173,9 @@ def p2p_head_state_dict(num_classes=1, num_points=1, in_channels=256, feat_chann
 
 
 def locator_state_dict(depth=50, num_classes=1, start_level=0, head='cpr', seed=0, head_std=0.01, num_points=1,
-                       num_cls_fcs=0, fc_out_channels=1024, binary_ins=False, ins_tower=False, out_bg_cls=False):
-    sd = resnet_state_dict(depth, seed)
+                       num_cls_fcs=0, fc_out_channels=1024, binary_ins=False, ins_tower=False, out_bg_cls=False, deep_stem=False,
+                       avg_down=False):
+    sd = resnet_state_dict(depth, seed, deep_stem=deep_stem, avg_down=avg_down)
     sd.update(fpn_state_dict(backbone_out_channels(depth), 256, start_level, 1, seed + 1))
     if head == 'cpr':
         sd.update(cpr_head_state_dict(num_classes, seed=seed + 2, std=head_std, num_cls_fcs=num_cls_fcs,

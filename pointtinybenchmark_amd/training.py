@@ -343,7 +343,7 @@ class BackwardEngine:
     def forward_stem(self, img):
         """-> (the pooled stem map, its record) for a trainable stem."""
         tape = []
-        out = self.model.backbone.stem(img, tape)
+        out = (getattr(self.model.backbone, 'run_stem', None) or self.model.backbone.stem)(img, tape)
         assert tape and tape[0].get('stem'), 'a stem segment is only built for a trainable stem'
         return out, tape[0]
 
@@ -1003,8 +1003,17 @@ class BackwardEngine:
         self._done(last.bias if last.bias.requires_grad else blk.conv2.weight)
         if blk.downsample is not None:     # the shortcut conv sees the same g3 (no activation on that branch)
             dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, g16=g1h)
-            dx = self._conv_bn_backward(cache, blk.downsample[0], blk.downsample[1], g3, cs3, x, need_dx, add=dx, g16=g3h)
-            tail = blk.downsample[1].bias if blk.downsample[1].bias.requires_grad else blk.downsample[0].weight
+            pool = blk.ds_pool
+            if pool:
+                # avg_down: the shortcut conv read the pooled map xp (its weight gradient does too); its data gradient is a plain
+                # stride-1 1x1 (the bf16 pipe's plain case in the mixed step), spread back over the windows by avgpool_bwd with
+                # the conv1-branch gradient summed in the same pass
+                dxp = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, rec['xp'], need_dx, g16=g3h)
+                if need_dx:
+                    dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
+            else:
+                dx = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx, g16=g3h)
+            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
         elif mask_in and need_dx:
             dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, True, mask=x, add=g3, want_colsum=True, g16=g1h, want16=mixed)
             dx = dx if mixed else (dx[0], dx[1], None)
@@ -1059,9 +1068,14 @@ class BackwardEngine:
         self._done(last.bias if last.bias.requires_grad else blk.conv2.weight)
         dx = self._conv_bn_backward_batch_stats(cache, blk.conv1, blk.bn1, rec, 'bn1', d1, o1, x, need_dx, add=ident)
         if blk.downsample is not None:
-            dx = self._conv_bn_backward_batch_stats(cache, blk.downsample[0], blk.downsample[1], rec, 'bnd', g3, m3, x, need_dx,
-                                                    add=dx)
-            tail = blk.downsample[1].bias if blk.downsample[1].bias.requires_grad else blk.downsample[0].weight
+            pool = blk.ds_pool
+            if pool:      # avg_down: the shortcut conv read the pooled map (see _block_backward)
+                dxp = self._conv_bn_backward_batch_stats(cache, blk.ds_conv, blk.ds_bn, rec, 'bnd', g3, m3, rec['xp'], need_dx)
+                if need_dx:
+                    dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
+            else:
+                dx = self._conv_bn_backward_batch_stats(cache, blk.ds_conv, blk.ds_bn, rec, 'bnd', g3, m3, x, need_dx, add=dx)
+            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
         else:
             tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
         self._done(tail)
@@ -1093,7 +1107,7 @@ class CprTrainer(BackwardEngine):
         missing = [n for n, p in model.named_parameters() if p.requires_grad and id(p) not in seen]
         assert not missing, 'trainable parameters without a backward rule: %s%s' % (
             missing[:8], ''.join(' (%s)' % model.backbone.stem_train_reason() for n in missing[:1] if n.startswith('backbone.conv1.') or
-                                 n.startswith('backbone.bn1.')))
+                                 n.startswith('backbone.bn1.') or n.startswith('backbone.stem.')))
         self.params = order
         dev = order[0].device
         n = sum(p.numel() for p in order)
@@ -1311,9 +1325,9 @@ class CprTrainer(BackwardEngine):
                     add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
                 add(blk.conv2.weight, blk.bn2.weight, blk.bn2.bias, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
                 if blk.downsample is not None:
-                    add(blk.downsample[0].weight, blk.downsample[1].weight, blk.downsample[1].bias)
+                    add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
         if bb.stem_train_reason() is None:          # frozen_stages < 0: the stem's gradients complete last
-            add(bb.conv1.weight, bb.bn1.weight, bb.bn1.bias)
+            add(bb.conv1.weight, bb.bn1.weight, bb.bn1.bias)     # (a deep stem always has a reason: it does not train)
         return out      # (a trainable non-standard stem has no backward rule and trips the constructor's check)
 
     @staticmethod
