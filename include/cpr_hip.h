@@ -538,6 +538,34 @@ int cpr_bn_apply(const float* y, const float* center, const float* scale, const 
                  const float* center2, const float* scale2, const float* shift2, float* out, long long M, int C, int relu, void* stream);
 int cpr_bn_train_bwd(const float* dout, const float* z, const float* y, const float* center, const float* mean, const float* rstd,
                      const float* gamma, float* dy, float* dgamma, float* dbeta, float* ws, long long M, int C, void* stream);
+/* SyncBN: the batch statistics of training-mode BatchNorm over the rows of ALL ranks (norm_cfg=dict(type='SyncBN'): mmcv's
+ * build_norm_layer -> torch.nn.SyncBatchNorm at T/mmdet/models/backbones/resnet.py:33-34, :160-162, :606; the collective
+ * between the two halves is the caller's, torch.distributed.all_gather_into_tensor).  The finalize step of cpr_bn_batch_stats and of
+ * cpr_bn_train_bwd in split form; a rank's map may hold a single row (M >= 1).  ws: cpr_bn_sync_ws(M, C) floats, shared by a local call
+ * and the merge call that follows it.  Exchange records are fp64, gathered rank-major:
+ *   statistics (2C + 1): [0, C) the absolute mean of this rank's rows, [C, 2C) their M2, [2C] the row count (an integer value);
+ *   backward   (2C):     [0, C) sum g, [C, 2C) sum g*(y - mean) over this rank's rows.
+ * cpr_bn_sync_stats_local: y -> record.
+ * cpr_bn_sync_stats_merge: records (R, 2C + 1) merged in rank order by Chan's k-group form in fp64 -> the vectors of cpr_bn_batch_stats
+ *   (biased variance over the global count), the running buffers (unbiased variance over the global count - 1) and num_batches_tracked
+ *   (+ 1) updated as there, count (1 double, may be NULL) = the global row count.  y: THIS rank's map -- center = its first row, so
+ *   center / cmean / cshift are rank-local; mean, rstd, scale, shift and the running buffers are functions of the records alone
+ *   (bit-identical on every rank).
+ * cpr_bn_sync_bwd_local: record, and this rank's dbeta = sum g, dgamma = rstd * sum g*(y - mean) over its OWN rows (either may be
+ *   NULL) -- torch's SyncBatchNorm hands each rank its local parameter-gradient sums, the gradient reducer averages them.  mean / center
+ *   as cpr_bn_train_bwd (the centred statistics: center, cmean).
+ * cpr_bn_sync_bwd_merge: records (R, 2C) summed in rank order in fp64, count = the global row count (device, from the statistics
+ *   merge) -> dy = gamma*rstd*(g - sum g / count - xhat * sum g*xhat / count), sums over all ranks. */
+int cpr_bn_sync_ws(long long M, int C);
+int cpr_bn_sync_stats_local(const float* y, double* record, float* ws, long long M, int C, void* stream);
+int cpr_bn_sync_stats_merge(const double* records, int R, const float* y, const float* gamma, const float* beta, float* running_mean,
+                            float* running_var, long long* num_batches_tracked, float momentum, float eps, float* mean, float* rstd,
+                            float* scale, float* shift, float* center, float* cmean, float* cshift, double* count, int C, void* stream);
+int cpr_bn_sync_bwd_local(const float* dout, const float* z, const float* y, const float* center, const float* mean, const float* rstd,
+                          float* dgamma, float* dbeta, double* record, float* ws, long long M, int C, void* stream);
+int cpr_bn_sync_bwd_merge(const double* records, int R, const double* count, const float* dout, const float* z, const float* y,
+                          const float* center, const float* mean, const float* rstd, const float* gamma, float* dy, float* ws, long long M,
+                          int C, void* stream);
 /* P2PHead's output convolutions in the bf16 compute mode (csrc/p2p_out_bf16.hip): a 3x3 / pad 1 / stride 1 conv with bias from the
  * RAW bf16 NHWC map x (N,H,W,Cin) of the last tower layer -- read as relu(a*x + b) with its per-(image, channel) GroupNorm affine
  * a, b (N,Cin) fp32, the activation never written -- to J output channels.  w (J,Cin,3,3) and bias (J) fp32 (the nn.Conv2d
@@ -666,6 +694,7 @@ int cpr_bf16_set_wfrag(int on);          /* bf16 mode: 0 = ignore wgt_frag (A/B 
 int cpr_wino_set_staging(int var, int tpx);      /* Winograd: staging variant (kernel template VAR) and cout tiles per XCD; -1 = the product's choice */
 int cpr_wino32_set_debug(int ablate, int wg_per_cu, int stagger_pct); /* conv_wino32.hip: loop ablations, workgroups per CU (1 / 2), stagger of the second wave of workgroups */
 int cpr_lsa_phase_clocks(long long* host_out, int reset);            /* assign.hip: shader clocks workgroup 0 of lsa_topk_reg_kernel spent per phase (8 values) */
+int cpr_bn_set_finalize_only(int on);    /* bn_train.hip: 1 = every entry skips its streaming passes (part / apply), so the finalize / local / merge launches can be timed alone; results are WRONG */
 #endif
 
 #ifdef __cplusplus

@@ -118,6 +118,11 @@ SIGNATURES = {
     'cpr_bn_batch_stats': [_p] * 6 + [_f, _f] + [_p] * 8 + [_l, _i, _p],
     'cpr_bn_apply': [_p] * 10 + [_l, _i, _i, _p],
     'cpr_bn_train_bwd': [_p] * 11 + [_l, _i, _p],
+    'cpr_bn_sync_ws': [_l, _i],
+    'cpr_bn_sync_stats_local': [_p, _p, _p, _l, _i, _p],
+    'cpr_bn_sync_stats_merge': [_p, _i] + [_p] * 6 + [_f, _f] + [_p] * 8 + [_i, _p],
+    'cpr_bn_sync_bwd_local': [_p] * 10 + [_l, _i, _p],
+    'cpr_bn_sync_bwd_merge': [_p, _i] + [_p] * 10 + [_l, _i, _p],
     'cpr_p2p_out_bf16_fwd': [_p] * 7 + [_i] * 5 + [_p],
     'cpr_p2p_out_bf16_dgrad': [_p, _i, _p, _p] + [_i] * 6 + [_p],
     'cpr_p2p_out_bf16_wgrad_ws': [_i] * 5,
@@ -143,6 +148,7 @@ BENCH_SIGNATURES = {
     'cpr_conv_set_extra_lds': [_i],
     'cpr_bf16_set_dma': [_i],
     'cpr_bf16_set_wfrag': [_i],
+    'cpr_bn_set_finalize_only': [_i],
 }
 BENCH_LIB_PATH = os.path.join(_HERE, 'csrc', 'libcprhip_bench.so')
 

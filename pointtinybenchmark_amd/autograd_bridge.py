@@ -24,7 +24,9 @@ Both compute modes (round 5: the bf16 mode = mixed precision, the reference anal
 unmodified ``loss.backward()``, T/mmdet/apis/train.py:116-119 -- see ``Bridge.carrier`` for how bf16 maps cross the Function
 boundaries), every CPRHead option set that runs forward (``CPRHead.train_step_supported``) with one FPN output level, P2PHead with any number of
 FPN output levels (extra pyramid levels beyond the laterals included) and points per cell, a frozen stem (standard or deep) or the standard trainable one (conv1 7x7/2, 3 -> 64; a trainable deep stem is refused).  Anything else keeps
-the forward-only path and warns once."""
+the forward-only path and warns once.  SyncBN (nn.SyncBatchNorm in the backbone, a process group of more than one rank): the recorded
+tapes carry each BatchNorm's group, so _StemFn / _StageFn synchronise their batch-statistics backward as the native trainer does -- every
+rank issues the exchanges in program order on its main stream; dgamma / dbeta stay rank-local sums for DDP's reducer to average."""
 import os
 import warnings
 

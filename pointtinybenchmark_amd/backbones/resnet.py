@@ -5,7 +5,9 @@ Interface of T/mmdet/models/backbones/resnet.py:305-657 (ctor kwargs, ``forward(
 BatchNorm in eval mode (norm_eval=True, every CPR/P2P config; or model.eval()) uses running statistics and is folded into the
 conv epilogue; the bottleneck shortcut add + ReLU are fused into conv3's epilogue.  With norm_eval=False the BatchNorm modules of the
 non-frozen stages are in training mode (the reference's ``train()``) and normalise with batch statistics: raw conv, statistics pass,
-normalise / residual / ReLU pass (csrc/bn_train.hip), running statistics updated on the device.
+normalise / residual / ReLU pass (csrc/bn_train.hip), running statistics updated on the device.  norm_cfg type 'SyncBN' (or
+torch.nn.SyncBatchNorm.convert_sync_batchnorm) builds nn.SyncBatchNorm modules -- same names and state-dict keys -- whose batch statistics
+run over the rows of every rank of their process group (``sync_group``); on one rank they are BatchNorm bit for bit.
 The backward of the trainable stages -- and of a trainable stem (frozen_stages=-1) -- is driven by training.CprTrainer from the records
 of ``forward(tape=)``."""
 import torch
@@ -14,6 +16,22 @@ import torch.nn as nn
 from .. import ops
 from ..layers import _PackCache, folded_bn, packed_conv
 from ..registry import BACKBONES
+
+
+_BatchNorm = nn.modules.batchnorm._BatchNorm      # BatchNorm2d and SyncBatchNorm (T/mmdet/models/backbones/resnet.py:7, :655)
+
+
+def sync_group(bn):
+    """The process group a BatchNorm module synchronises its batch statistics over in the next forward, or None: an nn.SyncBatchNorm in
+    training mode, torch.distributed initialised, and more than one rank in ``bn.process_group`` (None: the world group) -- torch's
+    ``need_sync`` rule."""
+    if not (isinstance(bn, nn.SyncBatchNorm) and bn.training):
+        return None
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return None
+    group = bn.process_group if bn.process_group is not None else dist.group.WORLD
+    return group if dist.get_world_size(group) > 1 else None
 
 
 def _bn_not_mixed():
@@ -111,15 +129,17 @@ class _Block(nn.Module):
     def _run_batch_stats(self, cache, x, save):
         """Training-mode BatchNorm: raw conv (unscaled pack, no epilogue affine) -> batch statistics (running buffers updated) ->
         normalise (+ shortcut) (+ ReLU).  The projection shortcut of a bottleneck joins in conv3's apply pass (two-input form);
-        nothing here takes the fused-shortcut conv2d_dual path.  save: the pre-BN maps y* and each BN's statistics (ops.BnStats) as well."""
+        nothing here takes the fused-shortcut conv2d_dual path.  save: the pre-BN maps y* and each BN's statistics (ops.BnStats) as well, and
+        beside them the process group each one was synchronised over (``groups``; None: per rank)."""
         if x.dtype != torch.float32:
             raise _bn_not_mixed()
-        stats = {}
+        stats, groups = {}, {}
 
         def conv_stats(name, conv, bn, inp):
             y = ops.conv2d(inp, packed_conv(cache, conv, torch.float32))
+            groups[name] = sync_group(bn)
             stats[name] = ops.bn_batch_stats(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                             bn.momentum, bn.eps)
+                                             bn.momentum, bn.eps, group=groups[name])
             return y, stats[name]
 
         y1, t1 = conv_stats('bn1', self.conv1, self.bn1, x)
@@ -141,7 +161,8 @@ class _Block(nn.Module):
         else:
             out = ops.bn_apply(yl, tl.scale, tl.cshift, center=tl.center, residual=x, relu=True)
         if save is not None:
-            save.update(block=self, x=x, xp=xp, o1=o1, o2=o2, out=out, y1=y1, y2=y2, y3=y3, yd=yd, stats=stats, batch_stats=True)
+            save.update(block=self, x=x, xp=xp, o1=o1, o2=o2, out=out, y1=y1, y2=y2, y3=y3, yd=yd, stats=stats, groups=groups,
+                        batch_stats=True)
         return out
 
 
@@ -178,14 +199,19 @@ class ResNet(nn.Module):
             raise KeyError('invalid depth %s for resnet' % depth)
         assert style in ('pytorch', 'caffe'), style
         assert dcn is None and plugins is None and not with_cp, 'dcn, plugins and with_cp are not built (SURVEY.md §2a row 5)'
-        assert tuple(dilations[:num_stages]) == (1,) * num_stages and norm_cfg.get('type') == 'BN'
+        assert tuple(dilations[:num_stages]) == (1,) * num_stages
+        if norm_cfg.get('type') not in ('BN', 'SyncBN'):
+            raise NotImplementedError("norm_cfg type %r is not built: the backbone norms are 'BN' (nn.BatchNorm2d) or 'SyncBN' "
+                                      "(nn.SyncBatchNorm)" % (norm_cfg.get('type'),))
         if deep_stem and (stem_channels or base_channels) != 64:
             raise NotImplementedError('deep_stem is built for stem_channels=64 (convs 3 -> 32 -> 32 -> 64, csrc/stem_deep.hip), not '
                                       'stem_channels=%s' % (stem_channels or base_channels))
         bn_kw = {'momentum': norm_cfg['momentum']} if 'momentum' in norm_cfg else {}     # (mmcv build_norm_layer)
 
+        norm_cls = nn.SyncBatchNorm if norm_cfg['type'] == 'SyncBN' else nn.BatchNorm2d
+
         def norm(c):
-            return nn.BatchNorm2d(c, **bn_kw)
+            return norm_cls(c, **bn_kw)
         self.depth, self.num_stages, self.out_indices = depth, num_stages, tuple(out_indices)
         self.frozen_stages, self.norm_eval = frozen_stages, norm_eval
         self.style, self.deep_stem, self.avg_down = style, bool(deep_stem), bool(avg_down)
@@ -248,7 +274,7 @@ class ResNet(nn.Module):
         self._freeze_stages()
         if mode and self.norm_eval:
             for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
+                if isinstance(m, _BatchNorm):
                     m.eval()
         return self
 
@@ -278,7 +304,7 @@ class ResNet(nn.Module):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
                 if m.bias is not None:
                     nn.init.constant_(m.bias, 0)
-            elif isinstance(m, nn.BatchNorm2d):
+            elif isinstance(m, _BatchNorm):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
         if self.zero_init_residual:
@@ -331,9 +357,11 @@ class ResNet(nn.Module):
             x = ops.from_nchw(x) if (x.shape[1] > 4 or (x.shape[1] == 4 and x.stride(1) == 1)) else ops.nchw_to_nhwc(x)
             y = ops.conv2d(x, packed_conv(c, c1))
             bn = self.bn1
-            t = ops.bn_batch_stats(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps)
+            group = sync_group(bn)
+            t = ops.bn_batch_stats(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
+                                   group=group)
             if rec is not None:
-                rec.update(y=y, stats=t, batch_stats=True)
+                rec.update(y=y, stats=t, group=group, batch_stats=True)
             return pool(ops.bn_apply(y, t.scale, t.cshift, center=t.center, relu=True), x, False)
         s, b = folded_bn(c, self.bn1)
         std7 = tuple(c1.weight.shape) == (64, 3, 7, 7) and c1.stride == (2, 2) and c1.padding == (3, 3)

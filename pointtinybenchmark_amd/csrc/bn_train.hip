@@ -339,9 +339,158 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_kernel(const float* __r
     }
 }
 
+// ---- SyncBN (torch.nn.SyncBatchNorm; mmcv build_norm_layer 'SyncBN'): the two finalize steps in split form, so that a collective can
+// sit between "what this rank saw" and "what every rank uses".  The exchange records are fp64:
+//   statistics  (2C + 1): [0, C) the ABSOLUTE mean of this rank's rows, [C, 2C) their M2, [2C] the row count (an exact integer value)
+//   backward    (2C):     [0, C) sum g, [C, 2C) sum g * (y - mean) over this rank's rows, mean = the merged mean
+// The local kernels keep the finalize kernels' shape (16 channels x 16 row-block slices per workgroup, fixed order); the merge kernels
+// run one thread per channel over the R gathered records in rank order.  No atomics.
+__global__ void __launch_bounds__(kThreads) bn_stats_local_kernel(const float* __restrict__ y, const float* __restrict__ part, int blocks,
+                                                                  long long M, int C, int rows_per_block, double* __restrict__ record) {
+    __shared__ double red[16][17];
+    const int cl = threadIdx.x & 15, s = threadIdx.x >> 4;
+    const int c = blockIdx.x * 16 + cl;
+    const bool live = c < C;
+    double s1 = 0;
+    if (live)
+        for (int b = s; b < blocks; b += 16) {
+            const long long nb = min((long long)rows_per_block, M - (long long)b * rows_per_block);
+            s1 += (double)nb * (double)part[((size_t)b * C + c) * 2];
+        }
+    red[s][cl] = s1;
+    __syncthreads();
+    double msh = 0;                                        // mean relative to the shift (this rank's first row)
+    for (int k = 0; k < 16; ++k) msh += red[k][cl];
+    msh /= (double)M;
+    __syncthreads();
+    double s2 = 0;
+    if (live)
+        for (int b = s; b < blocks; b += 16) {
+            const long long nb = min((long long)rows_per_block, M - (long long)b * rows_per_block);
+            const double d = (double)part[((size_t)b * C + c) * 2] - msh;
+            s2 += (double)part[((size_t)b * C + c) * 2 + 1] + (double)nb * d * d;
+        }
+    red[s][cl] = s2;
+    __syncthreads();
+    if (s != 0 || !live) return;
+    double m2 = 0;
+    for (int k = 0; k < 16; ++k) m2 += red[k][cl];
+    record[c] = (double)y[c] + msh;
+    record[(size_t)C + c] = m2;
+    if (c == 0) record[(size_t)2 * C] = (double)M;
+}
+
+// One workgroup: every thread reads num_batches_tracked before thread 0 writes it back incremented (momentum None divides by the new
+// count); each thread then owns channels c, c + 1024, ...
+constexpr int kMergeThreads = 1024;
+__global__ void __launch_bounds__(kMergeThreads) bn_stats_merge_kernel(
+    const double* __restrict__ records, int R, const float* __restrict__ y, int C, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ running_mean, float* __restrict__ running_var, long long* nbt, float momentum,
+    float eps, float* __restrict__ mean_out, float* __restrict__ rstd_out, float* __restrict__ scale_out, float* __restrict__ shift_out,
+    float* __restrict__ center_out, float* __restrict__ cmean_out, float* __restrict__ cshift_out, double* __restrict__ count_out) {
+    const long long seen = nbt ? *nbt + 1 : 0;
+    __syncthreads();
+    if (nbt && threadIdx.x == 0) *nbt = seen;
+    const size_t ld = (size_t)2 * C + 1;
+    double M = 0;
+    for (int r = 0; r < R; ++r) M += records[r * ld + 2 * (size_t)C];
+    if (threadIdx.x == 0 && count_out) *count_out = M;
+    for (int c = threadIdx.x; c < C; c += kMergeThreads) {
+        double s1 = 0;
+        for (int r = 0; r < R; ++r) s1 += records[r * ld + 2 * (size_t)C] * records[r * ld + c];
+        const double mu = s1 / M;
+        double m2 = 0;
+        for (int r = 0; r < R; ++r) {
+            const double d = records[r * ld + c] - mu;
+            m2 += records[r * ld + C + c] + records[r * ld + 2 * (size_t)C] * d * d;
+        }
+        const double var = m2 / M;                          // biased, over the global count: what the normalisation uses
+        const double rstd = 1.0 / sqrt(var + (double)eps);
+        const double sc = (double)gamma[c] * rstd;
+        mean_out[c] = (float)mu;
+        rstd_out[c] = (float)rstd;
+        if (scale_out) scale_out[c] = (float)sc;
+        if (shift_out) shift_out[c] = (float)((double)beta[c] - mu * sc);
+        if (center_out) {                                   // rank-local: this rank's own first row
+            const double msh = mu - (double)y[c];
+            center_out[c] = y[c];
+            cmean_out[c] = (float)msh;
+            cshift_out[c] = (float)((double)beta[c] - msh * sc);
+        }
+        if (running_mean) {
+            const double m = momentum >= 0.f ? (double)momentum : 1.0 / (double)seen;     // momentum None: cumulative average
+            running_mean[c] = (float)((1.0 - m) * (double)running_mean[c] + m * mu);
+            running_var[c] = (float)((1.0 - m) * (double)running_var[c] + m * (m2 / (M - 1.0)));   // unbiased, global M - 1
+        }
+    }
+}
+
+// this rank's dbeta = sum g and dgamma = rstd * sum g (y - mean) over its own rows (torch's SyncBatchNorm hands each rank its local
+// parameter-gradient sums; the gradient reducer averages them), and the record
+__global__ void __launch_bounds__(kThreads) bn_bwd_local_kernel(const float* __restrict__ part, int blocks, int C,
+                                                                const float* __restrict__ rstd, float* __restrict__ dgamma,
+                                                                float* __restrict__ dbeta, double* __restrict__ record) {
+    __shared__ double ra[16][17], rb[16][17];
+    const int cl = threadIdx.x & 15, s = threadIdx.x >> 4;
+    const int c = blockIdx.x * 16 + cl;
+    double a = 0, b = 0;
+    if (c < C)
+        for (int k = s; k < blocks; k += 16) {
+            a += (double)part[((size_t)k * C + c) * 2];
+            b += (double)part[((size_t)k * C + c) * 2 + 1];
+        }
+    ra[s][cl] = a;
+    rb[s][cl] = b;
+    __syncthreads();
+    if (s != 0 || c >= C) return;
+    double sa = 0, sb = 0;
+    for (int k = 0; k < 16; ++k) {
+        sa += ra[k][cl];
+        sb += rb[k][cl];
+    }
+    if (dgamma) dgamma[c] = (float)((double)rstd[c] * sb);
+    if (dbeta) dbeta[c] = (float)sa;
+    record[c] = sa;
+    record[(size_t)C + c] = sb;
+}
+
+// coef for bn_bwd_apply_kernel from the sums over ALL ranks (rank order) and the global count
+__global__ void __launch_bounds__(kThreads) bn_bwd_merge_kernel(const double* __restrict__ records, int R, int C,
+                                                                const double* __restrict__ count, const float* __restrict__ mean,
+                                                                const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                                float* __restrict__ coef) {
+    const int c = blockIdx.x * kThreads + threadIdx.x;
+    if (c >= C) return;
+    double sa = 0, sb = 0;
+    for (int r = 0; r < R; ++r) {
+        sa += records[(size_t)r * 2 * C + c];
+        sb += records[(size_t)r * 2 * C + C + c];
+    }
+    const double M = *count, rs = (double)rstd[c];
+    coef[(size_t)c * 4 + 0] = (float)((double)gamma[c] * rs);
+    coef[(size_t)c * 4 + 1] = (float)(sa / M);
+    coef[(size_t)c * 4 + 2] = (float)(rs * (rs * sb) / M);
+    coef[(size_t)c * 4 + 3] = mean[c];
+}
+
 bool bn_shape_ok(long long M, int C) { return M > 1 && C > 0 && C % 64 == 0; }
+bool bn_sync_shape_ok(long long M, int C) { return M > 0 && C > 0 && C % 64 == 0; }      // a rank may hold a single row
+
+#ifdef CPR_BENCH_HOOKS   // measurement build only (libcprhip_bench.so): the finalize / local / merge launches on their own
+int bn_finalize_only = 0;
+#define BN_STREAMING (!bn_finalize_only)
+#else
+#define BN_STREAMING true
+#endif
 
 }  // namespace
+
+#ifdef CPR_BENCH_HOOKS
+extern "C" int cpr_bn_set_finalize_only(int on) {   // 1: every bn_train.hip entry skips its streaming passes (part / apply): results WRONG
+    bn_finalize_only = on != 0;
+    return CPR_OK;
+}
+#endif
 
 // floats of workspace the statistics / backward entries need for an (M, C) map
 extern "C" int cpr_bn_train_ws(long long M, int C) {
@@ -360,8 +509,9 @@ extern "C" int cpr_bn_batch_stats(const float* y, const float* gamma, const floa
     CPR_CHECK_ARG(momentum >= 0.f || num_batches_tracked);
     const int rpb = (int)bn_rows_per_block(M, C);
     const int blocks = (int)cdivll(M, rpb);
-    hipLaunchKernelGGL(bn_stats_part_kernel, dim3(blocks, cdiv(C, 1024)), dim3(kThreads), 0, stream, y, ws, num_batches_tracked, M, C,
-                       rpb);
+    if (BN_STREAMING)
+        hipLaunchKernelGGL(bn_stats_part_kernel, dim3(blocks, cdiv(C, 1024)), dim3(kThreads), 0, stream, y, ws, num_batches_tracked, M, C,
+                           rpb);
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(cdiv(C, 16)), dim3(kThreads), 0, stream, y, ws, blocks, M, C, rpb, gamma, beta,
                        running_mean, running_var, num_batches_tracked, momentum, eps, mean, rstd, scale, shift, center, cmean, cshift);
     CPR_LAUNCH_STATUS();
@@ -385,9 +535,67 @@ extern "C" int cpr_bn_train_bwd(const float* dout, const float* z, const float* 
     const int rpb = (int)bn_rows_per_block(M, C);
     const int blocks = (int)cdivll(M, rpb);
     float* coef = ws + (size_t)blocks * C * 2;
-    hipLaunchKernelGGL(bn_bwd_part_kernel, dim3(blocks, cdiv(C, 1024)), dim3(kThreads), 0, stream, dout, z, y, center, mean, ws, M, C, rpb);
+    if (BN_STREAMING)
+        hipLaunchKernelGGL(bn_bwd_part_kernel, dim3(blocks, cdiv(C, 1024)), dim3(kThreads), 0, stream, dout, z, y, center, mean, ws, M, C, rpb);
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, 16)), dim3(kThreads), 0, stream, ws, blocks, M, C, mean, rstd, gamma,
                        dgamma, dbeta, coef);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks, cdiv(C, 1024)), dim3(kThreads), 0, stream, dout, z, y, coef, center, dy, M, C, rpb);
+    if (BN_STREAMING)
+        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks, cdiv(C, 1024)), dim3(kThreads), 0, stream, dout, z, y, coef, center, dy, M, C, rpb);
+    CPR_LAUNCH_STATUS();
+}
+
+// ---- SyncBN entries (see the kernels).  ws: cpr_bn_sync_ws(M, C) floats; records: (R, 2C + 1) / (R, 2C) doubles, rank-major
+extern "C" int cpr_bn_sync_ws(long long M, int C) {
+    if (!bn_sync_shape_ok(M, C)) return CPR_ERR_ARG;
+    const long long n = cdivll(M, bn_rows_per_block(M, C)) * C * 2 + (long long)C * 4;
+    return n < (1ll << 31) ? (int)n : CPR_ERR_UNSUPPORTED;
+}
+
+extern "C" int cpr_bn_sync_stats_local(const float* y, double* record, float* ws, long long M, int C, hipStream_t stream) {
+    CPR_CHECK_ARG(y && record && ws && bn_sync_shape_ok(M, C));
+    const int rpb = (int)bn_rows_per_block(M, C);
+    const int blocks = (int)cdivll(M, rpb);
+    if (BN_STREAMING)
+        hipLaunchKernelGGL(bn_stats_part_kernel, dim3(blocks, cdiv(C, 1024)), dim3(kThreads), 0, stream, y, ws, (long long*)nullptr, M, C,
+                           rpb);
+    hipLaunchKernelGGL(bn_stats_local_kernel, dim3(cdiv(C, 16)), dim3(kThreads), 0, stream, y, ws, blocks, M, C, rpb, record);
+    CPR_LAUNCH_STATUS();
+}
+
+extern "C" int cpr_bn_sync_stats_merge(const double* records, int R, const float* y, const float* gamma, const float* beta,
+                                       float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps,
+                                       float* mean, float* rstd, float* scale, float* shift, float* center, float* cmean, float* cshift,
+                                       double* count, int C, hipStream_t stream) {
+    CPR_CHECK_ARG(records && R > 0 && y && gamma && beta && mean && rstd && C > 0 && C % 64 == 0);
+    CPR_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
+    CPR_CHECK_ARG((center == nullptr) == (cmean == nullptr) && (center == nullptr) == (cshift == nullptr));
+    CPR_CHECK_ARG(momentum >= 0.f || num_batches_tracked);
+    hipLaunchKernelGGL(bn_stats_merge_kernel, dim3(1), dim3(kMergeThreads), 0, stream, records, R, y, C, gamma, beta, running_mean,
+                       running_var, num_batches_tracked, momentum, eps, mean, rstd, scale, shift, center, cmean, cshift, count);
+    CPR_LAUNCH_STATUS();
+}
+
+extern "C" int cpr_bn_sync_bwd_local(const float* dout, const float* z, const float* y, const float* center, const float* mean,
+                                     const float* rstd, float* dgamma, float* dbeta, double* record, float* ws, long long M, int C,
+                                     hipStream_t stream) {
+    CPR_CHECK_ARG(dout && y && mean && rstd && record && ws && bn_sync_shape_ok(M, C));
+    const int rpb = (int)bn_rows_per_block(M, C);
+    const int blocks = (int)cdivll(M, rpb);
+    if (BN_STREAMING)
+        hipLaunchKernelGGL(bn_bwd_part_kernel, dim3(blocks, cdiv(C, 1024)), dim3(kThreads), 0, stream, dout, z, y, center, mean, ws, M, C, rpb);
+    hipLaunchKernelGGL(bn_bwd_local_kernel, dim3(cdiv(C, 16)), dim3(kThreads), 0, stream, ws, blocks, C, rstd, dgamma, dbeta, record);
+    CPR_LAUNCH_STATUS();
+}
+
+extern "C" int cpr_bn_sync_bwd_merge(const double* records, int R, const double* count, const float* dout, const float* z, const float* y,
+                                     const float* center, const float* mean, const float* rstd, const float* gamma, float* dy, float* ws,
+                                     long long M, int C, hipStream_t stream) {
+    CPR_CHECK_ARG(records && R > 0 && count && dout && y && mean && rstd && gamma && dy && ws && bn_sync_shape_ok(M, C));
+    const int rpb = (int)bn_rows_per_block(M, C);
+    const int blocks = (int)cdivll(M, rpb);
+    float* coef = ws + (size_t)blocks * C * 2;
+    hipLaunchKernelGGL(bn_bwd_merge_kernel, dim3(cdiv(C, kThreads)), dim3(kThreads), 0, stream, records, R, C, count, mean, rstd, gamma, coef);
+    if (BN_STREAMING)
+        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks, cdiv(C, 1024)), dim3(kThreads), 0, stream, dout, z, y, coef, center, dy, M, C, rpb);
     CPR_LAUNCH_STATUS();
 }

@@ -535,14 +535,20 @@ def _bn_vec(t, C):
 BnStats = collections.namedtuple('BnStats', 'mean rstd scale shift center cmean cshift')
 
 
-def bn_batch_stats(y, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1, eps=1e-5):
+def bn_batch_stats(y, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1, eps=1e-5, group=None):
     """Batch statistics of an NHWC fp32 map y (..., C) -> BnStats of (C,) vectors: mean, rstd = 1/sqrt(biased var + eps),
     scale = gamma*rstd, shift = beta - mean*scale, and the centred form the product path applies and differentiates with --
     center = the map's first row, cmean = mean - center, cshift = beta - cmean*scale: (y - center)*scale + cshift has an exact first
     difference, so a map whose mean is far above its spread normalises to the precision of its spread.  running_mean / running_var are updated in place as torch's training-mode
     BatchNorm does (unbiased variance; momentum None: 1 / num_batches_tracked), num_batches_tracked incremented -- on the device.
     The kernel writes the buffers through raw pointers: their version counters are bumped here so that anything keyed on them
-    (layers._PackCache: the folded eval-mode BatchNorm) sees the change."""
+    (layers._PackCache: the folded eval-mode BatchNorm) sees the change.
+    group (SyncBN): a torch.distributed process group of more than one rank -> the statistics of the rows of ALL its ranks
+    (bn_sync_local_stats -> all_gather_into_tensor of the fp64 record on the current stream -> bn_sync_merge_stats; a BnSyncStats).
+    None, torch.distributed not initialised or a one-rank group: the single-rank launch below, untouched (torch's ``need_sync`` rule)."""
+    if sync_world_size(group) > 1:
+        rec, _ = bn_sync_local_stats(y)
+        return bn_sync_merge_stats(_sync_gather(rec, group), y, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps)
     M, C = _bn_rows(_check(y))
     dev = y.device
     st = torch.empty((7, C), device=dev, dtype=torch.float32)
@@ -583,10 +589,16 @@ def bn_apply(y, scale, shift, residual=None, relu=False, center=None, y2=None, s
     return out
 
 
-def bn_train_bwd(dout, y, mean, rstd, gamma, mask=None, out_dgamma=None, out_dbeta=None, center=None):
+def bn_train_bwd(dout, y, mean, rstd, gamma, mask=None, out_dgamma=None, out_dbeta=None, center=None, group=None, count=None):
     """Backward of training-mode BatchNorm (xhat = ((y - center) - mean)*rstd: pass BnStats' center and cmean for the centred form) (+ the ReLU whose output is ``mask``, when given: g = dout*(mask > 0), applied on the fly,
     never written) -> (dy, dgamma, dbeta): dbeta = sum g, dgamma = sum g*xhat, dy = gamma*rstd*(g - dbeta/M - xhat*dgamma/M).
-    out_dgamma / out_dbeta: where the parameter gradients go (e.g. the trainer's gradient views); default fresh tensors."""
+    out_dgamma / out_dbeta: where the parameter gradients go (e.g. the trainer's gradient views); default fresh tensors.
+    group (SyncBN, a group of more than one rank; ``count``: the forward's BnSyncStats.count): the sums behind dy run over the rows of
+    all ranks (bn_sync_local_bwd -> all_gather_into_tensor -> bn_sync_merge_bwd); dgamma / dbeta stay THIS rank's local sums."""
+    if sync_world_size(group) > 1:
+        assert count is not None, 'the synchronised backward divides by the global row count of the forward (BnSyncStats.count)'
+        rec, ws, dg, db = bn_sync_local_bwd(dout, y, mean, rstd, mask=mask, out_dgamma=out_dgamma, out_dbeta=out_dbeta, center=center)
+        return bn_sync_merge_bwd(_sync_gather(rec, group), ws, count, dout, y, mean, rstd, gamma, mask=mask, center=center), dg, db
     M, C = _bn_rows(_check(y))
     assert _check(dout).shape == y.shape and (mask is None or _check(mask).shape == y.shape)
     dev = y.device
@@ -597,6 +609,120 @@ def bn_train_bwd(dout, y, mean, rstd, gamma, mask=None, out_dgamma=None, out_dbe
     _lib.call('cpr_bn_train_bwd', _ptr(dout), _ptr(mask), _ptr(y), _ptr(_bn_vec(center, C)), _ptr(_bn_vec(mean, C)), _ptr(_bn_vec(rstd, C)),
               _ptr(_bn_vec(gamma, C)), _ptr(dy), _ptr(_bn_vec(dg, C)), _ptr(_bn_vec(db, C)), _ptr(ws), M, C, _stream())
     return dy, dg, db
+
+
+# ---- SyncBN: batch statistics over the rows of every rank of a process group (torch.nn.SyncBatchNorm).  The local / merge halves are
+# public: one process can play R ranks by calling the local half on R chunks and stacking the records (tests/test_gpu_syncbn.py).
+class BnSyncStats(BnStats):
+    """BnStats of a synchronised BatchNorm.  mean, rstd, scale, shift are the same bits on every rank; center, cmean, cshift are
+    rank-local (center = this rank's first row).  ``count``: (1,) fp64 device tensor, the global row count (the backward divides by it)."""
+    count = None
+
+
+def sync_world_size(group=None):
+    """Ranks a BatchNorm synchronises over: 1 without a group or without an initialised torch.distributed (no synchronisation)."""
+    if group is None:
+        return 1
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return 1
+    return dist.get_world_size(group)
+
+
+def _sync_gather(record, group):
+    """(n,) fp64 record -> (R, n): every rank's record in rank order; issued in program order on the current stream."""
+    import torch.distributed as dist
+    R = dist.get_world_size(group)
+    out = torch.empty((R * record.numel(),), device=record.device, dtype=record.dtype)
+    dist.all_gather_into_tensor(out, record, group=group)
+    return out.view(R, record.numel())
+
+
+def _bn_sync_rows(y):
+    C = y.shape[-1]
+    M = y.numel() // C if C else 0
+    if M < 1:
+        raise ValueError('SyncBN: this rank holds no rows (input size %s): every rank of the group brings at least one value per channel'
+                         % (tuple(y.shape),))
+    assert C % 64 == 0, 'training-mode BatchNorm needs C % 64 == 0, got %d' % C
+    return M, C
+
+
+def _bn_sync_records(records, n, y):
+    assert _check(records, torch.float64).dim() == 2 and records.shape[1] == n, (tuple(records.shape), n)
+    assert records.device == y.device
+    return int(records.shape[0])
+
+
+def bn_sync_local_stats(y):
+    """This rank's half of the synchronised statistics: NHWC fp32 map y (..., C), one row or more -> (record, workspace).  record:
+    (2C + 1,) fp64 = [absolute per-channel mean | M2 | row count], what the ranks exchange; workspace: the row-block partials."""
+    M, C = _bn_sync_rows(_check(y))
+    rec = torch.empty((2 * C + 1,), device=y.device, dtype=torch.float64)
+    ws = torch.empty((_lib.call('cpr_bn_sync_ws', M, C, positive=True),), device=y.device, dtype=torch.float32)
+    _lib.call('cpr_bn_sync_stats_local', _ptr(y), _ptr(rec), _ptr(ws), M, C, _stream())
+    return rec, ws
+
+
+def bn_sync_merge_stats(records, y, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1, eps=1e-5):
+    """records (R, 2C + 1): the gathered bn_sync_local_stats records, rank order; y: THIS rank's map -> BnSyncStats over the rows of all
+    ranks, running buffers / num_batches_tracked updated as bn_batch_stats does (unbiased variance over the global count - 1).  More than
+    one value per channel is needed over the whole group (torch's refusal), not per rank."""
+    M, C = _bn_sync_rows(_check(y))
+    R = _bn_sync_records(records, 2 * C + 1, y)
+    if R == 1 and M <= 1:      # every rank brings >= 1 row (bn_sync_local_stats), so only a lone one-row rank can fall short
+        raise ValueError('Expected more than 1 value per channel when training, got input size %s' % (tuple(y.shape),))
+    dev = y.device
+    st = torch.empty((7, C), device=dev, dtype=torch.float32)
+    count = torch.empty((1,), device=dev, dtype=torch.float64)
+    if momentum is None:
+        assert num_batches_tracked is not None, 'momentum None averages over num_batches_tracked'
+    assert (running_mean is None) == (running_var is None), 'running_mean and running_var go together'
+    bufs = [t for t in (running_mean, running_var) if t is not None]
+    for t in bufs:
+        _bn_vec(t, C)
+    if num_batches_tracked is not None:
+        assert _check(num_batches_tracked, torch.int64).numel() == 1
+    _lib.call('cpr_bn_sync_stats_merge', _ptr(records), R, _ptr(y), _ptr(_bn_vec(gamma, C)), _ptr(_bn_vec(beta, C)), _ptr(running_mean),
+              _ptr(running_var), _ptr(num_batches_tracked), -1.0 if momentum is None else float(momentum), float(eps),
+              _ptr(st[0]), _ptr(st[1]), _ptr(st[2]), _ptr(st[3]), _ptr(st[4]), _ptr(st[5]), _ptr(st[6]), _ptr(count), C, _stream())
+    from torch.autograd.graph import increment_version
+    for t in bufs + ([num_batches_tracked] if num_batches_tracked is not None else []):
+        increment_version(t)
+    out = BnSyncStats(*st.unbind(0))
+    out.count = count
+    return out
+
+
+def bn_sync_local_bwd(dout, y, mean, rstd, mask=None, out_dgamma=None, out_dbeta=None, center=None):
+    """This rank's half of the synchronised backward (mean / center as bn_train_bwd: BnSyncStats' cmean and center) ->
+    (record, workspace, dgamma, dbeta): record (2C,) fp64 = [sum g | sum g*(y - mean)] over this rank's rows; dgamma / dbeta are this
+    rank's LOCAL sums, as torch's SyncBatchNorm gives them (the gradient reducer averages them over the ranks)."""
+    M, C = _bn_sync_rows(_check(y))
+    assert _check(dout).shape == y.shape and (mask is None or _check(mask).shape == y.shape)
+    dev = y.device
+    dg = out_dgamma if out_dgamma is not None else torch.empty((C,), device=dev, dtype=torch.float32)
+    db = out_dbeta if out_dbeta is not None else torch.empty((C,), device=dev, dtype=torch.float32)
+    rec = torch.empty((2 * C,), device=dev, dtype=torch.float64)
+    ws = torch.empty((_lib.call('cpr_bn_sync_ws', M, C, positive=True),), device=dev, dtype=torch.float32)
+    _lib.call('cpr_bn_sync_bwd_local', _ptr(dout), _ptr(mask), _ptr(y), _ptr(_bn_vec(center, C)), _ptr(_bn_vec(mean, C)),
+              _ptr(_bn_vec(rstd, C)), _ptr(_bn_vec(dg, C)), _ptr(_bn_vec(db, C)), _ptr(rec), _ptr(ws), M, C, _stream())
+    return rec, ws, dg, db
+
+
+def bn_sync_merge_bwd(records, workspace, count, dout, y, mean, rstd, gamma, mask=None, center=None):
+    """records (R, 2C): the gathered bn_sync_local_bwd records, rank order; workspace: this rank's, from bn_sync_local_bwd; count: the
+    forward's BnSyncStats.count -> dy of THIS rank's rows, dy = gamma*rstd*(g - sum g / count - xhat * sum g*xhat / count) with the
+    sums over all ranks."""
+    M, C = _bn_sync_rows(_check(y))
+    R = _bn_sync_records(records, 2 * C, y)
+    assert _check(dout).shape == y.shape and (mask is None or _check(mask).shape == y.shape)
+    assert _check(count, torch.float64).numel() == 1
+    assert _check(workspace).numel() == _lib.call('cpr_bn_sync_ws', M, C, positive=True), 'the workspace of bn_sync_local_bwd on this map'
+    dy = torch.empty_like(y)
+    _lib.call('cpr_bn_sync_bwd_merge', _ptr(records), R, _ptr(count), _ptr(dout), _ptr(mask), _ptr(y), _ptr(_bn_vec(center, C)),
+              _ptr(_bn_vec(mean, C)), _ptr(_bn_vec(rstd, C)), _ptr(_bn_vec(gamma, C)), _ptr(dy), _ptr(workspace), M, C, _stream())
+    return dy
 
 
 def stem_weight_f32(weight):

@@ -845,7 +845,7 @@ class BackwardEngine:
         if rec.get('batch_stats'):
             st = rec['stats']
             dconv, _, _ = ops.bn_train_bwd(dy, rec['y'], st.cmean, st.rstd, bn.weight, center=st.center, out_dgamma=dg_out,
-                                           out_dbeta=db_out)
+                                           out_dbeta=db_out, group=rec.get('group'), count=getattr(st, 'count', None))
             if w.requires_grad:
                 self._param_side(lambda: ops.stem_wgrad_f32(dconv, x, planar=planar, out=self._g(w)), dconv, x)
         else:
@@ -1031,8 +1031,11 @@ class BackwardEngine:
         data gradient wrt x (+ ``add``), through the UNSCALED weights."""
         st = rec['stats'][key]
         aff = bn.weight.requires_grad
+        # SyncBN: the group recorded beside the statistics -- dy from the sums over all its ranks, dgamma / dbeta this rank's own (the
+        # gradient reducer averages them); the exchange is issued here, in program order on the main stream
         dy, _, _ = ops.bn_train_bwd(g, rec['y' + key[2:]], st.cmean, st.rstd, bn.weight, mask=mask, center=st.center,
-                                    out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
+                                    out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None,
+                                    group=rec.get('groups', {}).get(key), count=getattr(st, 'count', None))
         w = conv.weight
         if w.requires_grad:
             def param_grads():
