@@ -448,6 +448,26 @@ int cpr_phase_scatter_add(const float* src, float* dst, int N, int Hs, int Ws, i
 /* out (N,H,W,C) = dy (N,OH,OW,C) with s-1 zeros inserted between pixels (data gradient of a stride-s conv as a
  * stride-1 conv over the dilated gradient) */
 int cpr_zero_insert(const float* dy, float* out, int N, int OH, int OW, int C, int H, int W, int s, void* stream);
+/* ---- grouped 3x3 convolution (ResNeXt conv2; csrc/conv_group.hip), NHWC fp32, plain fp32 FMA -------------------------------
+ * C input and output channels in C / cg groups, cg in {4, 8, 16, 32}, padding 1, stride 1 or 2; the parameter is (C, cg, 3, 3).
+ * An output channel is multiplied against the cg input channels of its own group and nothing else (9 * cg FMAs per output, tap-major,
+ * input channel ascending): bit-repeatable, and an image of a batch equals its single-image run.
+ * cpr_pack_weights_grouped: the parameter -> the kernel's image (9 * cg * C floats): transpose 0 the forward pack, 1 the data-gradient
+ * pack (per group in / out channels swapped, taps flipped, scale[C] -- the forward conv's folded BatchNorm, or NULL -- multiplied in).
+ * _multi: a device table of jobs { const float* w; const float* scale; float* out; int C, cg, transpose, block0, nblocks, pad; }
+ * (48 bytes, ascending block0), one launch of total_blocks workgroups -- the same bits as the single launches. */
+int cpr_pack_weights_grouped(const float* w, const float* scale, float* out, int C, int cg, int transpose, void* stream);
+int cpr_pack_weights_grouped_multi(const void* jobs_dev, int n, int total_blocks, void* stream);
+/* out (N,OH,OW,C) = relu?(conv(x (N,H,W,C), wp) * scale[c] + bias[c]); scale / bias may be NULL (the raw form); flags: CPR_CONV_RELU
+ * only (no residual, no GroupNorm statistics, no fused input affine: anything else is CPR_ERR_ARG).  The data gradient of a grouped
+ * conv is this call over dy (zero-inserted for stride 2) with the data-gradient pack and stride 1. */
+int cpr_conv_group_fwd(const float* x, const float* wp, float* out, const float* scale, const float* bias, int N, int H, int W, int C,
+                       int cg, int stride, int flags, void* stream);
+/* grad_w (C, cg, 3, 3) (+)= dy (N,OH,OW,C) against x (N,H,W,C) within each group.  The pixels are split into slices whose partials (ws:
+ * cpr_conv_group_wgrad_workspace(...) floats) are added in ascending order by a second kernel -- no atomics. */
+int cpr_conv_group_wgrad_workspace(int N, int OH, int OW, int C, int cg);
+int cpr_conv_group_wgrad(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int cg, int stride,
+                         int accumulate, void* stream);
 /* FPN extra pyramid levels (fpn.py:195-217; csrc/fpn_extra.hip), NHWC, 16 bytes of channels per lane.
  * cpr_subsample2: out (N,(H+1)/2,(W+1)/2,C) = y[:, ::2, ::2, :] with y = x, or x*a[n,c] + b[n,c] when a/b (N,C) are given (the producer's
  * pending GroupNorm affine, cpr_gn_apply's arithmetic) -- F.max_pool2d(y, 1, stride=2) bit for bit.  x/out fp32 (C%4==0) or bf16

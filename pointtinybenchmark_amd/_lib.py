@@ -112,6 +112,11 @@ SIGNATURES = {
     'cpr_scale_clip_flip_boxes': [_p, _p, _p, _p, _p, _i, _i, _p],
     'cpr_pack_weights': [_p, _p, _p] + [_i] * 7 + [_p],
     'cpr_pack_weights_bf16': [_p, _p, _p, _p] + [_i] * 5 + [_p],
+    'cpr_pack_weights_grouped': [_p, _p, _p, _i, _i, _i, _p],
+    'cpr_pack_weights_grouped_multi': [_p, _i, _i, _p],
+    'cpr_conv_group_fwd': [_p] * 5 + [_i] * 7 + [_p],
+    'cpr_conv_group_wgrad_workspace': [_i] * 5,
+    'cpr_conv_group_wgrad': [_p] * 4 + [_i] * 7 + [_p],
     'cpr_spin': [ctypes.c_longlong, _p],
     'cpr_bn_fold': [_p, _p, _p, _p, _f, _p, _p, _p, _i, _p],
     'cpr_bn_train_ws': [_l, _i],

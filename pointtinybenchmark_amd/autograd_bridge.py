@@ -101,6 +101,8 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     n_outs = min(len(neck.lateral_convs), neck.num_outs) + getattr(neck, 'extra_levels', 0)    # outputs, not fpn_convs: max-pool extras
     if n_outs != 1 and type(head).__name__ != 'P2PHead':
         return 'needs an FPN neck with num_outs == 1 (every shipped CPR config; CPRHead asserts one level, cpr_head.py:487)'
+    if bb.compute_dtype != torch.float32 and getattr(bb, 'groups', 1) > 1:
+        return 'a grouped backbone (ResNeXt groups=%d) runs in the fp32 compute mode only, not with the bf16 compute mode' % bb.groups
     if bb.compute_dtype != torch.float32 and bb.batch_stats_active():
         return 'BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only, not with the bf16 compute mode'
     if bb.compute_dtype != torch.float32 and type(head).__name__ not in ('CPRHead', 'P2PHead'):

@@ -1,1 +1,1 @@
-from .resnet import ResNet  # noqa: F401
+from .resnet import ResNet, ResNeXt  # noqa: F401

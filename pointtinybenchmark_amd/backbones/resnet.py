@@ -10,6 +10,8 @@ torch.nn.SyncBatchNorm.convert_sync_batchnorm) builds nn.SyncBatchNorm modules -
 run over the rows of every rank of their process group (``sync_group``); on one rank they are BatchNorm bit for bit.
 The backward of the trainable stages -- and of a trainable stem (frozen_stages=-1) -- is driven by training.CprTrainer from the records
 of ``forward(tape=)``."""
+import math
+
 import torch
 import torch.nn as nn
 
@@ -34,22 +36,40 @@ def sync_group(bn):
     return group if dist.get_world_size(group) > 1 else None
 
 
+def _grouped_not_mixed(groups):
+    return NotImplementedError('a grouped backbone (ResNeXt groups=%d) runs in the fp32 compute mode only: the bf16 compute mode (mixed '
+                               'precision) has no grouped convolution' % groups)
+
+
+def block_width(planes, groups=1, base_width=4, base_channels=64):
+    """Channels of a bottleneck's conv1 output / conv2 (T/mmdet/models/backbones/resnext.py:28-32): ``planes`` for a ResNet,
+    floor(planes * base_width / base_channels) * groups for a ResNeXt."""
+    if groups == 1:
+        return planes
+    return math.floor(planes * (base_width / base_channels)) * groups
+
+
 def _bn_not_mixed():
     return NotImplementedError('BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only: the bf16 compute '
                                'mode (mixed precision) keeps norm_eval=True')
 
 
 class _Block(nn.Module):
-    def __init__(self, kind, inplanes, planes, stride, downsample, norm=nn.BatchNorm2d, style='pytorch'):
+    def __init__(self, kind, inplanes, planes, stride, downsample, norm=nn.BatchNorm2d, style='pytorch', groups=1, base_width=4,
+                 base_channels=64):
         super().__init__()
         self.kind = kind
+        assert groups == 1 or kind == 'bottleneck', 'grouped blocks are bottlenecks (resnext.py:11)'
         if kind == 'bottleneck':  # style='pytorch': the stride sits on the 3x3, 'caffe': on the first 1x1 (resnet.py:153-158)
             s1, s2 = (1, stride) if style == 'pytorch' else (stride, 1)
-            self.conv1 = nn.Conv2d(inplanes, planes, 1, s1, bias=False)
-            self.bn1 = norm(planes)
-            self.conv2 = nn.Conv2d(planes, planes, 3, s2, 1, bias=False)
-            self.bn2 = norm(planes)
-            self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
+            # ResNeXt (resnext.py:28-84): conv1 inplanes -> width, conv2 width -> width in ``groups`` groups (csrc/conv_group.hip),
+            # conv3 width -> 4 * planes; groups == 1: width = planes, the ResNet block
+            width = block_width(planes, groups, base_width, base_channels)
+            self.conv1 = nn.Conv2d(inplanes, width, 1, s1, bias=False)
+            self.bn1 = norm(width)
+            self.conv2 = nn.Conv2d(width, width, 3, s2, 1, groups=groups, bias=False)
+            self.bn2 = norm(width)
+            self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
             self.bn3 = norm(planes * 4)
         else:
             self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
@@ -188,6 +208,7 @@ class ResNet(nn.Module):
                      101: ('bottleneck', (3, 4, 23, 3)), 152: ('bottleneck', (3, 8, 36, 3))}
 
     stem = _StemAttr()
+    groups, base_width = 1, 4      # ResNeXt sets them before this constructor runs (resnext.py:142-145)
 
     def __init__(self, depth, in_channels=3, stem_channels=None, base_channels=64, num_stages=4,
                  strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1), out_indices=(0, 1, 2, 3), style='pytorch',
@@ -206,6 +227,13 @@ class ResNet(nn.Module):
         if deep_stem and (stem_channels or base_channels) != 64:
             raise NotImplementedError('deep_stem is built for stem_channels=64 (convs 3 -> 32 -> 32 -> 64, csrc/stem_deep.hip), not '
                                       'stem_channels=%s' % (stem_channels or base_channels))
+        if self.groups > 1:
+            for i in range(num_stages):
+                cg = block_width(base_channels * 2 ** i, self.groups, self.base_width, base_channels) // self.groups
+                if cg not in ops.GROUP_WIDTHS:
+                    raise NotImplementedError('groups=%d with base_width=%d gives a group width of %d channels at stage %d: the grouped 3x3 '
+                                              'kernels (csrc/conv_group.hip) are built for widths %s'
+                                              % (self.groups, self.base_width, cg, i + 1, list(ops.GROUP_WIDTHS)))
         bn_kw = {'momentum': norm_cfg['momentum']} if 'momentum' in norm_cfg else {}     # (mmcv build_norm_layer)
 
         norm_cls = nn.SyncBatchNorm if norm_cfg['type'] == 'SyncBN' else nn.BatchNorm2d
@@ -240,7 +268,7 @@ class ResNet(nn.Module):
                                            nn.Conv2d(inplanes, planes * exp, 1, 1, bias=False), norm(planes * exp))
                     else:
                         ds = nn.Sequential(nn.Conv2d(inplanes, planes * exp, 1, stride, bias=False), norm(planes * exp))
-                layer.append(_Block(kind, inplanes, planes, stride, ds, norm, style))
+                layer.append(_Block(kind, inplanes, planes, stride, ds, norm, style, self.groups, self.base_width, base_channels))
                 inplanes = planes * exp
             name = 'layer%d' % (i + 1)
             self.add_module(name, nn.Sequential(*layer))
@@ -290,6 +318,8 @@ class ResNet(nn.Module):
         return list(self.stem.parameters()) if self.deep_stem else list(self.conv1.parameters()) + list(self.bn1.parameters())
 
     def _check_mode(self):
+        if self.compute_dtype != torch.float32 and self.groups > 1:
+            raise _grouped_not_mixed(self.groups)
         if self.compute_dtype != torch.float32 and self.batch_stats_active():
             raise _bn_not_mixed()
 
@@ -452,3 +482,17 @@ class ResNetV1d(ResNet):
 
     def __init__(self, **kwargs):
         super().__init__(deep_stem=True, avg_down=True, **kwargs)
+
+
+@BACKBONES.register_module()
+class ResNeXt(ResNet):
+    """ResNeXt (T/mmdet/models/backbones/resnext.py:108-153): the bottleneck ResNet whose 3x3 conv runs in ``groups`` groups of
+    floor(planes * base_width / base_channels) channels (32x4d: 128 / 256 / 512 / 1024 wide, 64x4d: 256 .. 2048; the stage outputs keep
+    ResNet's 256 .. 2048).  Same module names and state-dict keys as ResNet, other shapes.  The grouped layer is csrc/conv_group.hip
+    (fp32 compute mode only; group widths 4 / 8 / 16 / 32); ``groups=1`` is the ResNet of that depth on the dense kernels."""
+    arch_settings = {50: ('bottleneck', (3, 4, 6, 3)), 101: ('bottleneck', (3, 4, 23, 3)), 152: ('bottleneck', (3, 8, 36, 3))}
+
+    def __init__(self, groups=1, base_width=4, **kwargs):
+        self.groups = groups
+        self.base_width = base_width
+        super().__init__(**kwargs)

@@ -33,6 +33,10 @@ class BasicLocator(nn.Module):
         weights from the stem output on, fp32 accumulate / statistics / losses).  Parameters stay fp32 masters."""
         dt = {'fp32': torch.float32, 'bf16': torch.bfloat16, torch.float32: torch.float32,
               torch.bfloat16: torch.bfloat16}[dtype]
+        groups = getattr(self.backbone, 'groups', 1)
+        if dt != torch.float32 and groups > 1:
+            raise NotImplementedError('a grouped backbone (ResNeXt groups=%d) runs in the fp32 compute mode only: the bf16 compute mode '
+                                      'has no grouped convolution' % groups)
         self.backbone.compute_dtype = dt
         return self
 

@@ -24,6 +24,7 @@ def bump_weight_epoch():
 REFRESH_IN_PLACE = [True]
 
 _FOLDS, _PACKS16, _PACKS32 = 'cpr_bn_fold_multi', 'cpr_pack_weights_bf16_multi', 'cpr_pack_weights_multi'
+_PACKSG = 'cpr_pack_weights_grouped_multi'
 
 
 class FoldJob:
@@ -81,11 +82,31 @@ class PackJob:
                 _lib.call(fn, pc.w.data_ptr(), img.data_ptr(), pc.Cin, pc.Cout, pc.Kpad, stream)
 
 
+class GroupPackJob(PackJob):
+    """The same for a grouped pack (ops.PackedConv with groups > 1): one 48-byte row of cpr_pack_weights_grouped_multi
+    (csrc/conv_group.hip GroupPackJob).  It has no Winograd or fragment image."""
+    multi = _PACKSG
+    _ROWG = struct.Struct('<3Q6i')
+
+    def __init__(self, weight, value, transpose, fold):
+        self.weight, self.value, self.transpose, self.fold = weight, value, transpose, fold
+        self.shape = tuple(weight.shape)
+        self.nblocks = max(1, min(64, (value.w.numel() + 255) // 256))
+
+    def ptrs(self):
+        """The device pointers of this job's row: weight, scale, pack."""
+        return (self.weight.data_ptr(), 0 if self.fold is None else self.fold.value[0].data_ptr(), self.value.w.data_ptr())
+
+    def row(self, ptrs, block0):
+        pc, nb = self.value, self.nblocks
+        return self._ROWG.pack(*ptrs, pc.Cout, pc.cg, self.transpose, block0, nb, 0), block0 + nb
+
+
 def _pack_job(pc, weight, transpose=0, fold=None):
     """The PackJob of a pack that a pack kernel built from an fp32 contiguous device weight; None for anything else (the strided
     layers' PhasedDgrad): that entry lapses with the weight epoch."""
     if isinstance(pc, ops.PackedConv) and weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous():
-        return PackJob(weight, pc, transpose, fold)
+        return (GroupPackJob if pc.groups > 1 else PackJob)(weight, pc, transpose, fold)
     return None
 
 
@@ -151,7 +172,7 @@ class _PackCache:
             return
         ptrs = [j.ptrs() for _, j in live]
         if self._tables is None or self._tables[0] != ptrs:       # the job set changed or a pointer moved
-            rows = {_FOLDS: [], _PACKS16: [], _PACKS32: []}
+            rows = {_FOLDS: [], _PACKS16: [], _PACKS32: [], _PACKSG: []}
             extent = dict.fromkeys(rows, 0)
             for (_, j), p in zip(live, ptrs):
                 row, extent[j.multi] = j.row(p, extent[j.multi])
@@ -174,7 +195,7 @@ class _PackCache:
 
 def packed_conv(cache, conv, dtype=torch.float32):
     return cache.get(('pc', id(conv), dtype), [conv.weight],
-                     lambda: ops.PackedConv(conv.weight, conv.stride[0], conv.padding[0], dtype),
+                     lambda: ops.PackedConv(conv.weight, conv.stride[0], conv.padding[0], dtype, groups=conv.groups),
                      lambda pc: _pack_job(pc, conv.weight))
 
 
@@ -206,12 +227,13 @@ def dgrad_packed(cache, conv, bn=None, dtype=torch.float32):
     folded scale of the eval-mode ``bn`` multiplied in -- or the raw weights (bn None: a batch-statistics layer)."""
     w, stride, pad = conv.weight, conv.stride[0], conv.padding[0]
     if bn is None:
-        return cache.get(('dgrad_raw', id(conv)), [w], lambda: ops.dgrad_pack(w, stride, pad), lambda pc: _pack_job(pc, w, 1))
+        return cache.get(('dgrad_raw', id(conv)), [w], lambda: ops.dgrad_pack(w, stride, pad, groups=conv.groups),
+                         lambda pc: _pack_job(pc, w, 1))
 
     def make():
         scale, _ = folded_bn(cache, bn)
-        if dtype == torch.float32 or stride != 1:
-            return ops.dgrad_pack(w, stride, pad, scale=scale, dtype=dtype)
+        if dtype == torch.float32 or stride != 1 or conv.groups > 1:
+            return ops.dgrad_pack(w, stride, pad, scale=scale, dtype=dtype, groups=conv.groups)
         return ops.PackedConv.for_dgrad_bf16(w, pad, scale=scale)
 
     def job(pc):        # linked to the fold job of the scale make() multiplied in

@@ -71,13 +71,18 @@ class PackedConv:
     wino = None     # transformed weights of the Winograd path, built on first use (conv3x3_wino)
     wino32 = None   # the same for the two-workgroups-per-CU kernel (csrc/conv_wino32.hip: chunks of 4 input channels)
     ready = None    # record_ready() behind the last pack kernel (weights / Winograd image); see pack_ready()
+    groups = 1      # > 1: a grouped 3x3 layer (ResNeXt conv2) in the layout of csrc/conv_group.hip, see _init_grouped
+    cg = None       # ... its group width (channels per group)
 
     def _packed(self):
         """A pack kernel was just enqueued on the current stream: consumers on OTHER streams (CPR_STREAMS > 1 sub-batches)
         must order themselves behind it."""
         self.ready = record_ready()
 
-    def __init__(self, weight, stride=1, padding=0, dtype=torch.float32):
+    def __init__(self, weight, stride=1, padding=0, dtype=torch.float32, groups=1):
+        if groups > 1:
+            self._init_grouped(weight, stride, padding, dtype, groups, None, 0)
+            return
         Cout, Cin, KH, KW = weight.shape
         w = weight.detach().to(torch.float32).permute(0, 2, 3, 1)  # OHWI
         self.dtype = dtype
@@ -113,6 +118,35 @@ class PackedConv:
         packed = torch.zeros((Cout, Kpad), device=weight.device, dtype=torch.float32)
         packed[:, :K] = wp.reshape(Cout, K)
         self.w = packed.contiguous()
+
+    def _init_grouped(self, weight, stride, padding, dtype, groups, scale, transpose):
+        """A grouped 3x3 / padding 1 conv, weight (C, cg, 3, 3) with cg = C / groups in GROUP_WIDTHS (csrc/conv_group.hip): self.w is the
+        kernel's own image, 9 * cg * C floats [tap][cg / 4][4][C / 4][4] (cpr_pack_weights_grouped), not the dense [Cout][Kpad] rows.
+        transpose: the data-gradient pack -- per group in / out channels swapped, taps flipped, ``scale`` multiplied in.  fp32 only."""
+        C, cg, KH, KW = weight.shape
+        if dtype != torch.float32:
+            raise NotImplementedError('a grouped convolution (groups=%d) runs in the fp32 compute mode only, not in %s' % (groups, dtype))
+        assert weight.is_cuda, 'the grouped pack is built on the device'
+        assert cg * groups == C and cg in GROUP_WIDTHS and (KH, KW) == (3, 3) and padding == 1 and stride in (1, 2), \
+            'grouped conv: 3x3 / padding 1 / stride 1 or 2 with a group width in %s, got weight %s groups %d stride %d padding %d' \
+            % (GROUP_WIDTHS, tuple(weight.shape), groups, stride, padding)
+        self.dtype, self.groups, self.cg = torch.float32, groups, cg
+        self.Cout, self.Cin, self.KH, self.KW, self.Kpad = C, C, 3, 3, 9 * cg
+        self.stride, self.padding = stride, 1
+        src = weight.detach()
+        if src.dtype != torch.float32 or not src.is_contiguous():
+            src = src.float().contiguous()
+        self.w = torch.empty((9 * cg * C,), device=weight.device, dtype=torch.float32)
+        _lib.call('cpr_pack_weights_grouped', _ptr(src), _ptr(scale), _ptr(self.w), C, cg, int(transpose), _stream())
+        self._packed()
+
+    @classmethod
+    def for_dgrad_grouped(cls, weight, groups, scale=None):
+        """The grouped pack of the stride-1 grouped conv over dy (zero-inserted first for a stride-2 layer, conv2d_dgrad) that yields
+        the data gradient of a grouped 3x3 / padding 1 conv: what for_dgrad is to the dense layers."""
+        self = cls.__new__(cls)
+        self._init_grouped(weight, 1, 1, torch.float32, groups, scale, 1)
+        return self
 
     def _pack_bf16(self, weight, scale, transpose):
         """csrc/pack.hip, cpr_pack_weights_bf16: OIHW fp32 master -> self.w (bf16 [rows][K]) and, for rows % 256 == 0, self.wfrag.
@@ -187,6 +221,7 @@ class PackedConv:
 
 
 CONV_RELU, CONV_OUT_BF16, CONV_RES_MASK, CONV_COLSUM = 1, 2, 4, 8      # include/cpr_hip.h CPR_CONV_*
+GROUP_WIDTHS = (4, 8, 16, 32)      # channels per group the grouped 3x3 kernels are built for (csrc/conv_group.hip)
 # bf16 mode: hand the fragment-order weight image to the conv launcher (the 256 x 256 tile then loads its weight operand
 # straight into registers, csrc/conv_bf16_dma.hip BD instance).  False keeps both operands on the LDS-DMA path (tests).
 WFRAG = [True]
@@ -232,7 +267,7 @@ def pack_ready(pc):
 
 
 def wino_eligible(pc, H, W, dtype=torch.float32):
-    if not (WINOGRAD[0] and dtype == torch.float32 and pc.dtype == torch.float32 and pc.KH == 3 and pc.KW == 3 and
+    if not (pc.groups == 1 and WINOGRAD[0] and dtype == torch.float32 and pc.dtype == torch.float32 and pc.KH == 3 and pc.KW == 3 and
             pc.stride == 1 and pc.padding == 1 and pc.Cin % 16 == 0 and pc.Cin >= 32 and pc.Cout % 64 == 0):
         return False
     fill = (H * W) / float(((H + 15) // 16 * 16) * ((W + 15) // 16 * 16))
@@ -355,6 +390,18 @@ def conv2d(x, pc, scale=None, bias=None, residual=None, relu=False, in_ab=None, 
     assert x.dtype == pc.dtype, 'weights were packed for %s, input is %s' % (pc.dtype, x.dtype)
     OH, OW = pc.out_hw(H, W)
     odt = out_dtype or x.dtype
+    if pc.groups > 1:
+        # grouped 3x3 (csrc/conv_group.hip): scale / bias / ReLU epilogue or the raw form, nothing else
+        assert residual is None and in_ab is None and not (in_relu or gn_part or res_mask or colsum or out_b8) and \
+            odt == torch.float32, 'the grouped conv has no residual, GroupNorm-statistics, fused-input-affine or bf16 form'
+        if out is None:
+            out = torch.empty((N, OH, OW, pc.Cout), device=x.device, dtype=torch.float32)
+        assert tuple(out.shape) == (N, OH, OW, pc.Cout) and out.is_contiguous()
+        _lib.call('cpr_conv_group_fwd', _ptr(x), _ptr(pc.w), _ptr(out), _ptr(scale), _ptr(bias), N, H, W, Cin, pc.cg, pc.stride,
+                  CONV_RELU if relu else 0, _stream())
+        if TRACE_CONV_VARIANT[0]:
+            TRACE_CONV_VARIANT[1] = ('group', pc.cg)
+        return out
     if residual is None and not (res_mask or colsum) and odt == torch.float32 and wino_eligible(pc, H, W, x.dtype) and \
             (in_ab is None or Cin <= 512):
         return conv3x3_wino(x, pc, scale, bias, relu, gn_part, out, in_ab, in_relu, out_b8)
@@ -410,7 +457,7 @@ def conv2d_bf16_mask_slots(x_shape, pc, out_dtype=torch.bfloat16, fused_add=Fals
     0 = the shape's kernel does not know the mode (include/cpr_hip.h, cpr_conv2d_bf16_mask_slots).  fused_add: the form with the
     shortcut sum and two outputs (``conv2d_dgrad_bf16_fused``)."""
     N, H, W, Cin = x_shape
-    if fused_add and (not WFRAG[0] or pc.Cout % 256 != 0):
+    if pc.groups > 1 or (fused_add and (not WFRAG[0] or pc.Cout % 256 != 0)):
         return 0
     return _lib.call('cpr_conv2d_bf16_mask_slots', N, H, W, Cin, pc.Cout, pc.KH, pc.KW, pc.stride, pc.padding,
                      2 if fused_add else int(out_dtype == torch.float32), positive=True)
@@ -1356,11 +1403,17 @@ def match_cost(pred, logits, gt, labels, cls_terms, reg_terms):
 
 
 # ------------------------------------------------------------------------------------------------ backward / optimizer
-def dgrad_pack(weight, stride, padding, scale=None, dtype=torch.float32):
+def dgrad_pack(weight, stride, padding, scale=None, dtype=torch.float32, groups=1):
     """PackedConv that computes the data gradient of ``conv2d(x, weight, stride, padding)`` as a stride-1 forward conv
     over dy (zero-inserted first when stride > 1): channels swapped, taps flipped, padding K-1-p; ``scale`` (Cout,) is
     the forward conv's folded-BatchNorm scale, multiplied into the weights.  Stride-2 convs with k in {1, 3} and
-    padding k//2 (every strided conv of the ResNet body) get the phase-decomposed form (PhasedDgrad)."""
+    padding k//2 (every strided conv of the ResNet body) get the phase-decomposed form (PhasedDgrad).  groups > 1 (a grouped 3x3 layer):
+    the grouped data-gradient pack at either stride -- conv2d_dgrad zero-inserts a strided layer's gradient."""
+    if groups > 1:
+        if dtype != torch.float32:
+            raise NotImplementedError('a grouped convolution (groups=%d) runs in the fp32 compute mode only, not in %s' % (groups, dtype))
+        assert padding == 1 and stride in (1, 2)
+        return PackedConv.for_dgrad_grouped(weight, groups, scale)
     if stride == 2 and weight.shape[2] == weight.shape[3] and weight.shape[2] in (1, 3) and padding == weight.shape[2] // 2 \
             and _PHASED[0]:
         return PhasedDgrad(weight, stride, padding, scale, dtype)
@@ -1415,6 +1468,21 @@ def conv2d_dgrad(dy, pc_t, in_hw, stride=1, mask=None, add=None, colsum=False):
     per-channel sums of the result as TilePartials (-> (dx, partials); ``partials.reduce()`` gives the (C,) vector)."""
     N, OH, OW, Cout = _check(dy).shape
     H, W = in_hw
+    if not isinstance(pc_t, PhasedDgrad) and pc_t.groups > 1:
+        # grouped layer: the grouped kernel over dy (its epilogue has no extra operand), then sum / mask / column sums as ONE streaming
+        # pass over the result.  Stride 2: zero insertion -- the map is the block's narrow one and three layers of the net are strided
+        if stride > 1:
+            z = torch.empty((N, H, W, Cout), device=dy.device, dtype=torch.float32)
+            _lib.call('cpr_zero_insert', _ptr(dy), _ptr(z), N, OH, OW, Cout, H, W, stride, _stream())
+            dy = z
+        dx = conv2d(dy, pc_t)
+        assert dx.shape[1] == H and dx.shape[2] == W, (dx.shape, in_hw)
+        if mask is None and not colsum:
+            return dx if add is None else axpby(dx, add, 1.0, 1.0)
+        keep = mask is not None or add is not None
+        g, cs = relu_bwd_colsum(dx, mask, want_g=keep, add=add)
+        dx = g if keep else dx
+        return (dx, cs) if colsum else dx
     if mask is not None and add is not None:
         # the conv epilogue has one extra operand (the sum OR the mask source): the sum rides in the epilogue, mask and column sums
         # are one streaming pass over the result
@@ -1446,6 +1514,8 @@ def conv_wgrad_bf16_supported(x_shape, weight_shape, stride, padding, maps_bf16=
     layer below 256 couts.  The shape rule itself is the C query's (cpr_conv_wgrad_bf16_workspace_s: negative = unsupported, called
     directly -- here that is an answer, not an error)."""
     Cout, Cin, KH, KW = weight_shape
+    if Cin != x_shape[3]:          # a grouped layer: fp32 only
+        return False
     if KH == 1 and Cout < 256 and not maps_bf16:      # measured (tools/wgrad_bf16_bench.py): the two rewrites cost what the bf16 GEMM saves
         return False
     if KH != KW or padding != KH // 2:                 # (the query sees one kernel size and no padding)
@@ -1493,12 +1563,26 @@ def conv3x3_wino_wgrad(dy, x, weight_shape, in_ab=None, in_relu=False, grad=None
     return grad
 
 
-def conv2d_wgrad(dy, x, weight_shape, stride, padding, in_ab=None, in_relu=False, grad=None, out=None):
+def conv2d_wgrad(dy, x, weight_shape, stride, padding, in_ab=None, in_relu=False, grad=None, out=None, groups=1):
     """grad_w [Cout][Cin][KH][KW]: accumulated into ``grad`` when given, written into ``out`` when given, else a new
-    tensor.  in_ab: fused GroupNorm affine (+ReLU) of the input."""
+    tensor.  in_ab: fused GroupNorm affine (+ReLU) of the input.  groups > 1: a grouped 3x3 / padding 1 layer, grad_w (C, C / groups, 3, 3)
+    (csrc/conv_group.hip; the split over pixels is added up in a fixed order)."""
     N, H, W, Cin = _check(x).shape
     _, OH, OW, Cout = _check(dy).shape
     KH, KW = weight_shape[2], weight_shape[3]
+    if groups > 1:
+        cg = weight_shape[1]
+        assert Cout == Cin == weight_shape[0] == cg * groups and cg in GROUP_WIDTHS and (KH, KW) == (3, 3) and padding == 1 and \
+            in_ab is None and not in_relu and x.dtype == torch.float32 and dy.dtype == torch.float32, (weight_shape, groups, Cin, Cout)
+        assert (OH, OW) == ((H - 1) // stride + 1, (W - 1) // stride + 1), (dy.shape, x.shape, stride)
+        n = _lib.call('cpr_conv_group_wgrad_workspace', N, OH, OW, Cin, cg, positive=True)
+        ws = torch.empty((n,), device=x.device, dtype=torch.float32)
+        acc = grad is not None
+        if grad is None:
+            grad = out if out is not None else torch.empty(tuple(weight_shape), device=x.device, dtype=torch.float32)
+        assert tuple(grad.shape) == tuple(weight_shape) and grad.is_contiguous()
+        _lib.call('cpr_conv_group_wgrad', _ptr(dy), _ptr(x), _ptr(grad), _ptr(ws), N, H, W, Cin, cg, stride, int(acc), _stream())
+        return grad
     assert weight_shape[0] == Cout and weight_shape[1] == Cin, (weight_shape, Cout, Cin)
     if WINOGRAD[0] and KH == 3 and KW == 3 and stride == 1 and padding == 1 and Cin % 64 == 0 and Cout % 64 == 0 and \
             x.dtype == torch.float32 and W / float((W + 15) // 16 * 16) >= WINO_MIN_FILL and H * W >= 1024 and \

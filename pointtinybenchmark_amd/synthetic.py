@@ -52,10 +52,12 @@ def _gn(sd, prefix, c, g):
     sd[prefix + '.bias'] = torch.randn(c, generator=g) * 0.1
 
 
-def resnet_state_dict(depth=50, seed=0, prefix='backbone.', deep_stem=False, avg_down=False):
+def resnet_state_dict(depth=50, seed=0, prefix='backbone.', deep_stem=False, avg_down=False, groups=1, base_width=4):
     """deep_stem: the keys of the three-conv stem (``stem.0 / .3 / .6`` convs, ``stem.1 / .4 / .7`` norms) in place of conv1 / bn1;
     avg_down: the projection shortcuts as ``downsample.1`` (conv) / ``downsample.2`` (norm) behind the parameter-free pool at index
-    0.  (style='caffe' moves a stride, no key.)  The defaults draw the tensors they always drew."""
+    0.  (style='caffe' moves a stride, no key.)  groups / base_width: the ResNeXt shapes (bottleneck depths) -- conv1 / conv2 / conv3
+    around width = floor(planes * base_width / 64) * groups channels, conv2 (width, width / groups, 3, 3).  The defaults draw the tensors
+    they always drew."""
     g = torch.Generator().manual_seed(seed)
     kind, blocks = ARCH[depth]
     sd = {}
@@ -75,11 +77,12 @@ def resnet_state_dict(depth=50, seed=0, prefix='backbone.', deep_stem=False, avg
         for bi in range(nb):
             p = '%slayer%d.%d.' % (prefix, li + 1, bi)
             if kind == 'bottleneck':
-                sd[p + 'conv1.weight'] = _kaiming((planes, inplanes, 1, 1), g)
-                _bn(sd, p + 'bn1', planes, g)
-                sd[p + 'conv2.weight'] = _kaiming((planes, planes, 3, 3), g)
-                _bn(sd, p + 'bn2', planes, g)
-                sd[p + 'conv3.weight'] = _kaiming((planes * 4, planes, 1, 1), g)
+                width = planes if groups == 1 else int(planes * base_width // 64) * groups
+                sd[p + 'conv1.weight'] = _kaiming((width, inplanes, 1, 1), g)
+                _bn(sd, p + 'bn1', width, g)
+                sd[p + 'conv2.weight'] = _kaiming((width, width // groups, 3, 3), g)
+                _bn(sd, p + 'bn2', width, g)
+                sd[p + 'conv3.weight'] = _kaiming((planes * 4, width, 1, 1), g)
                 _bn(sd, p + 'bn3', planes * 4, g)
             else:
                 sd[p + 'conv1.weight'] = _kaiming((planes, inplanes, 3, 3), g)
@@ -174,8 +177,8 @@ def p2p_head_state_dict(num_classes=1, num_points=1, in_channels=256, feat_chann
 
 def locator_state_dict(depth=50, num_classes=1, start_level=0, head='cpr', seed=0, head_std=0.01, num_points=1,
                        num_cls_fcs=0, fc_out_channels=1024, binary_ins=False, ins_tower=False, out_bg_cls=False, deep_stem=False,
-                       avg_down=False):
-    sd = resnet_state_dict(depth, seed, deep_stem=deep_stem, avg_down=avg_down)
+                       avg_down=False, groups=1, base_width=4):
+    sd = resnet_state_dict(depth, seed, deep_stem=deep_stem, avg_down=avg_down, groups=groups, base_width=base_width)
     sd.update(fpn_state_dict(backbone_out_channels(depth), 256, start_level, 1, seed + 1))
     if head == 'cpr':
         sd.update(cpr_head_state_dict(num_classes, seed=seed + 2, std=head_std, num_cls_fcs=num_cls_fcs,

@@ -280,6 +280,10 @@ class BackwardEngine:
 
     def __init__(self, model, two_streams=True):
         self.model = model
+        bb = getattr(model, 'backbone', model)      # (tests drive a bare backbone through the engine)
+        if getattr(bb, 'compute_dtype', torch.float32) != torch.float32 and getattr(bb, 'groups', 1) > 1:
+            raise NotImplementedError('a grouped backbone (ResNeXt groups=%d) trains in the fp32 compute mode only: the bf16 compute mode '
+                                      'has no grouped convolution' % bb.groups)
         dev = next(model.parameters()).device
         self._mixed, self._wide = False, {}     # set per step (bf16 compute mode = mixed precision)
         self._sink = None                       # None: p.grad (CprTrainer); dict: id(p) -> fresh tensor (autograd bridge)
@@ -911,7 +915,7 @@ class BackwardEngine:
                 if w16:
                     ops.conv_wgrad_bf16(g16, x, w.shape, out=gw, stride=conv.stride[0])    # (x: the bf16 recorded map, or a widened copy that rounds back exactly)
                 else:
-                    ops.conv2d_wgrad(g, self._f32(x), w.shape, conv.stride[0], conv.padding[0], out=gw)
+                    ops.conv2d_wgrad(g, self._f32(x), w.shape, conv.stride[0], conv.padding[0], out=gw, groups=conv.groups)
                 ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, cs,
                                 out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
             # x may be a widened fp32 temporary of the mixed-precision step that the main stream frees right after this call
@@ -955,6 +959,10 @@ class BackwardEngine:
                 g16 = g.to(torch.bfloat16)
             return finish(pt16(g16, (x.shape[1], x.shape[2]), add=add))
         pt = dgrad_packed(cache, conv, bn)
+        if conv.groups > 1:
+            # a grouped conv2 (ResNeXt): the grouped kernel has no extra epilogue operand -- the data gradient, then sum / mask /
+            # column sums as the streaming pass (the route of the Winograd data gradient below)
+            return finish(ops.conv2d_dgrad(g, pt, (x.shape[1], x.shape[2]), conv.stride[0]), add)
         if k == 3 and conv.stride[0] == 1 and add is None and \
                 (mask is not None or want_colsum) and ops.wino_eligible(pt, x.shape[1], x.shape[2], torch.float32):
             # a 3x3 stride-1 data gradient with a mask / column-sum epilogue would run the direct kernel (2.25x the multiplies of
@@ -1039,7 +1047,7 @@ class BackwardEngine:
         w = conv.weight
         if w.requires_grad:
             def param_grads():
-                ops.conv2d_wgrad(dy, x, w.shape, conv.stride[0], conv.padding[0], out=self._g(w))
+                ops.conv2d_wgrad(dy, x, w.shape, conv.stride[0], conv.padding[0], out=self._g(w), groups=conv.groups)
             self._param_side(param_grads, dy, x)
         if not need_dx:
             return None
