@@ -477,6 +477,13 @@ int cpr_subsample2(const void* x, int x_bf16, const float* a, const float* b, vo
 int cpr_subsample2_bwd_add(const float* dfine, const float* dcoarse, float* out, int N, int H, int W, int C, void* stream);
 /* relu_before_extra_convs: out = dz + (y > 0 ? d : 0) on flat buffers of n floats (n%4==0); y fp32, or bf16 with y_bf16 */
 int cpr_relu_mask_add(const float* dz, const float* d, const void* y, int y_bf16, float* out, long long n, void* stream);
+/* PAFPN bottom-up sum (pafpn.py:131-135; csrc/pafpn.hip): y (N,H,W,C) = (x1*a1[n,c] + b1[n,c]) + (x2*a2[n,c] + b2[n,c]), two raw conv outputs
+ * under the pending GroupNorm affines (N,C) of their layers, one streaming pass; y may be x1 or x2.  fp32 (C%4==0, C<=1024), or _bf16: both
+ * maps and y bf16 (C%8==0, C<=2048), fp32 arithmetic, one rounding.  N*H*W < 2^31. */
+int cpr_gn_apply2(const float* x1, const float* a1, const float* b1, const float* x2, const float* a2, const float* b2, float* y, int N, int H,
+                  int W, int C, void* stream);
+int cpr_gn_apply2_bf16(const void* x1, const float* a1, const float* b1, const void* x2, const float* a2, const float* b2, void* y, int N,
+                       int H, int W, int C, void* stream);
 /* d(gt_loss + pos_loss + neg_loss)/d(logit map) of CPRHead.loss (cpr_head.py:1101-1229): negative-grid term, MIL bag
  * and gt-centre terms taken back through the bilinear taps -- deterministically: every bag's taps are gathered into a
  * win x win cell window (win >= 2 * ceil(max |offset| / stride) + 3; win_ws (G, win, win, J) fp32 and win_org (G, 2) int32

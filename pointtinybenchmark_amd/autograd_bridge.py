@@ -11,7 +11,7 @@ chain have none: a raw map travels with a pending affine):
     image -> stem + frozen stages (no graph)
           -> _StageFn (layer2) -> _StageFn (layer3) -> _StageFn (layer4)          d(stage output) between them
           -> _LateralsFn: lateral 1x1 convs + GN + top-down adds -> the lateral sums the output convs read   d(lateral sums)
-          -> _HeadLossFn: FPN 3x3 output conv(s) + extra pyramid levels + head towers + projection + point stage + losses -> the loss vector
+          -> _HeadLossFn: FPN 3x3 output conv(s) (+ a PAFPN's bottom-up path) + extra pyramid levels + head towers + projection + point stage + losses -> the loss vector
              (add_extra_convs='on_input': the last stage's output is one more input of it, d(stage output) comes back from it too)
 
 Every Function takes its trainable parameters as explicit inputs, so they sit in the autograd graph as leaves: gradient
@@ -65,7 +65,9 @@ class Bridge:
                             for p in m.parameters() if p.requires_grad]
         self.stage_params = [[p for p in getattr(bb, name).parameters() if p.requires_grad] for name in bb.res_layers]
         self.lateral_params = [p for cm in neck.lateral_convs for p in cm.parameters() if p.requires_grad]
-        self.head_params = [p for p in [q for cm in neck.fpn_convs for q in cm.parameters()] + list(head.parameters())
+        # (a PAFPN's bottom-up modules sit between the output convs and the head: the same Function)
+        neck_out = list(neck.fpn_convs) + list(getattr(neck, 'downsample_convs', ())) + list(getattr(neck, 'pafpn_convs', ()))
+        self.head_params = [p for p in [q for cm in neck_out for q in cm.parameters()] + list(head.parameters())
                             if p.requires_grad]
         # add_extra_convs='on_input': the first extra conv reads the last backbone stage's output, one more differentiable input
         self.extra_on_input = bool(getattr(neck, 'extra_levels', 0)) and neck.add_extra_convs == 'on_input'
@@ -96,9 +98,11 @@ def signature(model):
 def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     """None when ``forward_train`` can be differentiable, else why not."""
     bb, neck, head = model.backbone, model.neck, model.bbox_head
-    if neck is None or type(neck).__name__ != 'FPN' or len(neck.fpn_convs) < 1:
+    if neck is None or type(neck).__name__ not in ('FPN', 'PAFPN') or len(neck.fpn_convs) < 1:
         return 'needs an FPN neck'
     n_outs = min(len(neck.lateral_convs), neck.num_outs) + getattr(neck, 'extra_levels', 0)    # outputs, not fpn_convs: max-pool extras
+    if n_outs != 1 and type(head).__name__ == 'CPRHead' and type(neck).__name__ == 'PAFPN':
+        return 'CPRHead takes one pyramid level (cpr_head.py:487); this PAFPN has %d output levels' % n_outs
     if n_outs != 1 and type(head).__name__ != 'P2PHead':
         return 'needs an FPN neck with num_outs == 1 (every shipped CPR config; CPRHead asserts one level, cpr_head.py:487)'
     if bb.compute_dtype != torch.float32 and getattr(bb, 'groups', 1) > 1:

@@ -1,1 +1,2 @@
 from .fpn import FPN  # noqa: F401
+from .pafpn import PAFPN  # noqa: F401

@@ -981,6 +981,19 @@ def gn_apply(x, a, b, relu=False, up=None, out=None):
     return out
 
 
+def gn_apply2(x1, a1, b1, x2, a2, b2, out=None):
+    """y = (x1*a1[n,c] + b1[n,c]) + (x2*a2[n,c] + b2[n,c]): two raw conv outputs under their pending GroupNorm affines, summed in one
+    pass (the PAFPN bottom-up path).  In place when out is x1 (or x2)."""
+    N, H, W, C = _check(x1, ACT).shape
+    assert _check(x2, ACT).shape == x1.shape and x2.dtype == x1.dtype, (x1.shape, x2.shape, x1.dtype, x2.dtype)
+    assert tuple(a1.shape) == tuple(b1.shape) == tuple(a2.shape) == tuple(b2.shape) == (N, C)
+    if out is None:
+        out = torch.empty_like(x1)
+    _lib.call('cpr_gn_apply2' + _sfx(x1), _ptr(x1), _ptr(_check(a1)), _ptr(_check(b1)), _ptr(x2), _ptr(_check(a2)), _ptr(_check(b2)),
+              _ptr(out), N, H, W, C, _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ CPR points
 def box_centers(boxes):
     n = boxes.shape[0]

@@ -119,6 +119,23 @@ def fpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=1, see
     return sd
 
 
+def pafpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=None, seed=1, prefix='neck.', add_extra_convs=False,
+                     extra_convs_on_inputs=True):
+    """``fpn_state_dict`` of the same arguments plus PAFPN's bottom-up modules (pafpn.py:69-93): ``downsample_convs.<i>`` (3x3 stride 2)
+    and ``pafpn_convs.<i>`` (3x3) for the len(in_channels) - start_level - 1 steps, drawn from a generator of their own (so the FPN part
+    of a seed is fpn_state_dict's).  num_outs: None = one output per used level."""
+    levels = len(in_channels) - start_level
+    num_outs = levels if num_outs is None else num_outs
+    assert num_outs >= levels
+    sd = fpn_state_dict(in_channels, out_channels, start_level, num_outs, seed, prefix, add_extra_convs, extra_convs_on_inputs)
+    g = torch.Generator().manual_seed(seed + 7919)
+    for i in range(levels - 1):
+        for name in ('downsample_convs', 'pafpn_convs'):
+            sd['%s%s.%d.conv.weight' % (prefix, name, i)] = _xavier_uniform((out_channels, out_channels, 3, 3), g)
+            _gn(sd, '%s%s.%d.gn' % (prefix, name, i), out_channels, g)
+    return sd
+
+
 def cpr_head_state_dict(num_classes=1, in_channels=256, feat_channels=256, stacked_convs=4, seed=2,
                         prefix='bbox_head.', std=0.01, num_cls_fcs=0, fc_out_channels=1024, binary_ins=False,
                         ins_tower=False, out_bg_cls=False):

@@ -270,6 +270,11 @@ FUSED_CAST = True
 MIXED_BF16 = dict(wgrad=True, dgrad=True, dz16=True, mask_mode=True, force=False)
 
 
+def _is_pafpn(neck):
+    """A PAFPN with a bottom-up path (necks/pafpn.py); with one used level it has no such module and is FPN itself."""
+    return len(getattr(neck, 'downsample_convs', ())) > 0
+
+
 class BackwardEngine:
     """The backward rules of the recorded forward -- shared by ``CprTrainer`` (gradients written straight into the views of
     its flat buffer, bucketed reducer, native optimizer) and by the autograd bridge (``autograd_bridge.py``: the same rules
@@ -385,6 +390,11 @@ class BackwardEngine:
         from .layers import conv_gn
         neck, head = self.model.neck, self.model.bbox_head
         lats = list(lat) if isinstance(lat, (tuple, list)) else [lat]
+        if _is_pafpn(neck):      # the bottom-up path sits between the output convs and the head: the neck's own walk, one tape
+            tape = []
+            lazy = neck.run_outputs(lats, extra_src, True, tape)
+            _, saved = self._forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
+            return saved[self.loss_vector_key], (dict(pafpn=tape), saved)
         recs = [dict(kind='out', level=i) for i in range(len(lats))]
         lazy = [conv_gn(neck._cache, neck.fpn_convs[i], t, materialize=False, save=rec) for i, (t, rec) in enumerate(zip(lats, recs))]
         extras = []
@@ -400,6 +410,10 @@ class BackwardEngine:
         gradients, then the gradient wrt extra_src (None unless need_src)."""
         rec, saved = state[:2]
         dz = self._backward_head(self.model.bbox_head, saved, upstream=upstream)
+        if isinstance(rec, dict) and 'pafpn' in rec:
+            neck = self.model.neck
+            dlats, d_src = self._backward_pafpn(neck, rec['pafpn'], list(dz), need_src=need_src)
+            return dlats + [d_src] if neck.add_extra_convs == 'on_input' and neck.extra_levels else dlats
         if len(state) == 3:
             neck = self.model.neck
             dzs, d_lat, d_src = self._backward_extras(neck, state[2], list(dz), need_src=need_src)
@@ -462,9 +476,11 @@ class BackwardEngine:
             self._wide[id(t)] = w
         return w
 
-    def _gn_conv_backward(self, rec, dz, relu, need_dx, dx_bf16=False):
+    def _gn_conv_backward(self, rec, dz, relu, need_dx, dx_bf16=False, add=None):
         """Backward of conv -> GN (-> ReLU) given dz wrt the module output.  Writes the three parameter gradients;
-        returns the gradient wrt the conv INPUT as the consumer saw it (after the producer's pending affine, if any)."""
+        returns the gradient wrt the conv INPUT as the consumer saw it (after the producer's pending affine, if any).
+        add (fp32, the input's shape): another gradient of that input, summed where the data gradient is written (conv2d_dgrad) --
+        the layers on the fp32 data-gradient kernels only (every stride-2 layer)."""
         cm = rec['module']
         w, gn = cm.conv.weight, cm.gn
         assert cm.conv.bias is None
@@ -505,11 +521,12 @@ class BackwardEngine:
         if not need_dx:
             return None
         if dgrad16:
+            assert add is None, 'the bf16 data gradient has no summed operand'
             # dx_bf16 (round 6): the caller hands the result to another bf16 GroupNorm backward, which reads a bf16 gradient map as it is
             return self._dgrad_bf16(draw if d16 is None else d16, w, cm.conv.padding[0],
                                     torch.bfloat16 if dx_bf16 else torch.float32)
         pt = ops.dgrad_pack(w, cm.conv.stride[0], cm.conv.padding[0])
-        return ops.conv2d_dgrad(draw, pt, (rec['x'].shape[1], rec['x'].shape[2]), cm.conv.stride[0])
+        return ops.conv2d_dgrad(draw, pt, (rec['x'].shape[1], rec['x'].shape[2]), cm.conv.stride[0], add=add)
 
     @staticmethod
     def _dgrad_bf16(dy, w, padding, out_dtype=torch.float32):
@@ -732,6 +749,13 @@ class BackwardEngine:
         out_recs = {r['level']: r for r in neck_tape if r['kind'] == 'out'}
         extra_recs = [r for r in neck_tape if r['kind'] in ('extra', 'pool')]
         dzs = list(dz) if isinstance(dz, (list, tuple)) else [dz]
+        if _is_pafpn(neck):
+            dlats, d_src = self._backward_pafpn(neck, [r for r in neck_tape if r['kind'] != 'lateral'], dzs)
+            d_stage = self._backward_laterals(neck, lat_recs, dlats)
+            if d_src is not None:
+                stage = neck.backbone_end_level - 1
+                d_stage[stage] = d_src if d_stage.get(stage) is None else ops.axpby(d_stage[stage], d_src, 1.0, 1.0)
+            return d_stage
         assert sorted(out_recs) == list(range(len(dzs) - len(extra_recs))), 'one gradient per FPN output level (%d outputs, %d gradients)' \
             % (len(out_recs) + len(extra_recs), len(dzs))
         dzs, d_lat, d_src = self._backward_extras(neck, extra_recs, dzs)
@@ -776,6 +800,37 @@ class BackwardEngine:
             else:
                 dzs[n + k - 1] = ops.axpby(dx, dzs[n + k - 1], 1.0, 1.0)
         return dzs[:n], d_lat, d_src
+
+    def _backward_pafpn(self, neck, recs, dzs, need_src=None):
+        """The PAFPN outputs behind the lateral sums (necks/pafpn.py run_outputs; T/mmdet/models/necks/pafpn.py:113-153): the extra
+        levels last first, then the bottom-up path in reverse, from the top level down.  g_inter[i] is the gradient of the SUM
+        inter[i], so it feeds the GroupNorm backward of fpn_convs[i] and (as its output gradient) of downsample_convs[i-1] unchanged:
+          g_inter[i] = dgrad(pafpn_convs[i-1], dzs[i])  [i >= 1; dzs[0] itself at level 0]
+                       + dgrad(downsample_convs[i], g_inter[i+1])  [i < L-1: stride 2, summed where it is written]
+          dlats[i]   = dgrad(fpn_convs[i], g_inter[i])
+        recs: the tape without the laterals.  dzs: one gradient per output level.  -> (the gradients wrt the L lateral sums -- the
+        coarsest joined by an 'on_lateral' extra's --, the gradient an 'on_input' extra adds to the last backbone stage's output | None)."""
+        by = {k: {r['level']: r for r in recs if r['kind'] == k} for k in ('out', 'down', 'pa_out')}
+        extra_recs = [r for r in recs if r['kind'] in ('extra', 'pool')]
+        L = len(by['out'])
+        assert sorted(by['out']) == list(range(L)) and sorted(by['down']) == list(range(L - 1)) and \
+            sorted(by['pa_out']) == list(range(1, L)) and len(dzs) == L + len(extra_recs), \
+            'one gradient per PAFPN output level (%d outputs, %d gradients)' % (L + len(extra_recs), len(dzs))
+        dzs, d_lat, d_src = self._backward_extras(neck, extra_recs, list(dzs), need_src=need_src)
+        dlats, above = [None] * L, None          # above: g_inter[i + 1]
+        for i in range(L - 1, -1, -1):
+            g = dzs[i]
+            if i >= 1:
+                g = self._gn_conv_backward(by['pa_out'][i], g, relu=False, need_dx=True)
+                self._done(by['pa_out'][i]['module'].conv.weight)
+            if i < L - 1:
+                g = self._gn_conv_backward(by['down'][i], above, relu=False, need_dx=True, add=g)
+                self._done(by['down'][i]['module'].conv.weight)
+            dlats[i] = self._backward_out_conv(by['out'][i], g)
+            above = g
+        if d_lat is not None:
+            dlats[-1] = ops.axpby(dlats[-1], d_lat, 1.0, 1.0)
+        return dlats, d_src
 
     def _backward_out_conv(self, rec, dz):
         """FPN output conv (3x3 + GN, no activation): dz wrt its normalised output -> gradient wrt the finest lateral sum."""
@@ -1104,6 +1159,9 @@ class CprTrainer(BackwardEngine):
         optimizer: an mmcv-style dict (``type`` 'SGD', 'Adam' or 'AdamW' + torch.optim's keyword arguments, torch's
         defaults) in place of the positional SGD arguments ``lr`` / ``momentum`` / ``weight_decay``; None: SGD with those."""
         BackwardEngine.__init__(self, model, two_streams)
+        n_levels = min(len(model.neck.lateral_convs), model.neck.num_outs) + getattr(model.neck, 'extra_levels', 0)
+        if _is_pafpn(model.neck) and type(model.bbox_head).__name__ == 'CPRHead' and n_levels != 1:
+            raise NotImplementedError('CPRHead takes one pyramid level (cpr_head.py:487); this PAFPN has %d output levels' % n_levels)
         self.schedule = schedule
         if optimizer is None:
             optimizer = dict(type='SGD', lr=lr, momentum=momentum, weight_decay=weight_decay)
@@ -1326,6 +1384,11 @@ class CprTrainer(BackwardEngine):
         regular = min(len(neck.lateral_convs), neck.num_outs)
         for cm in reversed(list(neck.fpn_convs)[regular:]):      # the extra levels' convs, last first (_backward_extras)
             add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+        if _is_pafpn(neck):       # the bottom-up path in reverse (_backward_pafpn): per level its pafpn conv, downsample conv, output conv
+            for i in range(regular - 1, -1, -1):
+                for cm in ([neck.pafpn_convs[i - 1]] if i >= 1 else []) + ([neck.downsample_convs[i]] if i < regular - 1 else []):
+                    add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+                add(neck.fpn_convs[i].gn.weight, neck.fpn_convs[i].gn.bias, neck.fpn_convs[i].conv.weight)
         for cm in list(neck.fpn_convs)[:regular]:
             add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
         for cm in neck.lateral_convs:

@@ -1,0 +1,453 @@
+"""-m gpu: the PAFPN neck (FPN + bottom-up path aggregation), forward and training.
+
+  kernel     ops.gn_apply2 (csrc/pafpn.hip) against fp64 torch: fp32 |err| <= 1e-5 max|want| (the bar bn_apply's two-input form is held
+             to), bf16 |err| <= 2^-8 |want| + 1e-5 max|want| (one bf16 rounding of an fp32 result); repeatable; in place == out of place
+  neck       PAFPN.forward per fixture case against the reference class (tests/golden/pafpn.npz): each level <= 2e-4 * max|level| (the
+             a3 bar); forward_lazy materialised equals forward; a single-level PAFPN equals FPN bit for bit; the neck backward against
+             the fixture's gradients, rel-L2 <= 2e-3 on norms and samples (the reference-golden bar)
+  locator    R18 128x160, the 4-point grid, C = 2, two pyramids -- strides [4, 8, 16, 32], and start_level=1, num_outs=5, 'on_input',
+             strides [8 .. 128]: P2PTrainer against fp64 autograd of tests/pafpn_ref.pafpn_forward + the oracle backbone / head / loss
+             on the device's assignment; the bridge bit-equal to the trainer; repeatable; three SGD steps lower the loss; bucket ready
+             points; mixed precision; the bf16 forward against FPN's; inference"""
+import pytest
+import torch
+
+from oracle import cpr_oracle as O
+from oracle import p2p_options_oracle as PO
+from pointtinybenchmark_amd import synthetic
+from tests import pafpn_ref as PR
+from tests.test_gpu_fpn_extra import GRID4, _cells, _data, _NeckOnly, _record_assignments
+
+pytestmark = pytest.mark.gpu
+
+
+# ------------------------------------------------------------------------------------------------ the kernel
+APPLY2_SHAPES = [(2, 13, 21, 64), (1, 1, 2, 64), (3, 7, 11, 256), (2, 25, 42, 64)]
+# 270 000 pixels at 4 pixels per block step: more than the launcher's 65 536 blocks -- lanes walk on to a second pixel, in another image
+APPLY2_WRAP = {torch.float32: (3, 300, 300, 256), torch.bfloat16: (3, 300, 300, 512)}
+
+
+def _rand(shape, seed, dtype=torch.float32):
+    if len(shape) == 4 and shape[1] * shape[2] > 10000:       # the large maps are drawn on the device
+        return torch.randn(shape, generator=torch.Generator('cuda').manual_seed(seed), device='cuda').to(dtype)
+    return torch.randn(shape, generator=torch.Generator().manual_seed(seed)).to(dtype).cuda()
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('shape', APPLY2_SHAPES + ['wrap'])
+def test_gn_apply2_vs_fp64(shape, dtype):
+    from pointtinybenchmark_amd import ops
+    shape = APPLY2_WRAP[dtype] if shape == 'wrap' else shape
+    N, C = shape[0], shape[3]
+    x1, x2 = _rand(shape, 1, dtype), _rand(shape, 2, dtype)
+    a1, a2 = _rand((N, C), 3) * 0.5 + 1.0, _rand((N, C), 4) * 0.5 - 1.0
+    b1, b2 = _rand((N, C), 5), _rand((N, C), 6)
+    got = ops.gn_apply2(x1, a1, b1, x2, a2, b2)
+    again = ops.gn_apply2(x1, a1, b1, x2, a2, b2)
+    torch.cuda.synchronize()
+    assert got.shape == x1.shape and got.dtype == dtype and got.is_contiguous()
+
+    def aff(x, a, b):
+        return x.double() * a.double()[:, None, None, :] + b.double()[:, None, None, :]
+    want = aff(x1, a1, b1) + aff(x2, a2, b2)
+    err = (got.double() - want).abs()
+    bar = 1e-5 * want.abs().max() + (2.0 ** -8 * want.abs() if dtype == torch.bfloat16 else 0.0)
+    print('ERR gn_apply2 %-18s %-8s max err %.3e  max err / bar %.3f  max|want| %.3f' % (
+        shape, str(dtype).split('.')[1], float(err.max()), float((err / bar).max()), float(want.abs().max())), flush=True)
+    assert bool((err <= bar).all()), float((err / bar).max())
+    assert torch.equal(got, again), 'two runs differ'
+    x1c = x1.clone()
+    assert ops.gn_apply2(x1c, a1, b1, x2, a2, b2, out=x1c) is x1c
+    torch.cuda.synchronize()
+    assert torch.equal(x1c, got), 'in place on x1 != out of place'
+
+
+def test_gn_apply2_refuses_what_it_cannot_run():
+    from pointtinybenchmark_amd import ops
+    from pointtinybenchmark_amd._lib import CprHipError
+    x, ab = _rand((1, 2, 2, 6), 1), _rand((1, 6), 2)
+    with pytest.raises(CprHipError):
+        ops.gn_apply2(x, ab, ab, x, ab, ab)               # C % 4 != 0
+    with pytest.raises(AssertionError):
+        ops.gn_apply2(_rand((1, 2, 2, 8), 1), ab, ab, _rand((1, 2, 3, 8), 1), ab, ab)
+
+
+# ------------------------------------------------------------------------------------------------ the neck against the reference
+def _neck(name, dtype=torch.float32, kind='PAFPN'):
+    import pointtinybenchmark_amd as P
+    cfg = PR.cases()[name]
+    neck = P.build_neck(dict(type=kind, **PR.neck_kwargs(cfg))).cuda()
+    sd = PR.case_state_dict(cfg, torch.float32)
+    if kind == 'FPN':
+        sd = {k: v for k, v in sd.items() if not k.startswith(('downsample_convs.', 'pafpn_convs.'))}
+    neck.load_state_dict(sd, strict=True)
+    xs = [x.cuda().to(dtype).contiguous(memory_format=torch.channels_last) for x in PR.case_inputs(cfg, torch.float32)]
+    return cfg, neck, xs
+
+
+@pytest.mark.parametrize('name', PR.CASE_NAMES)
+def test_pafpn_forward_vs_reference(name):
+    from pointtinybenchmark_amd import ops
+    cfg, neck, xs = _neck(name)
+    with torch.no_grad():
+        outs = neck(xs)
+        lazy = neck.forward_lazy(xs)
+    torch.cuda.synchronize()
+    assert len(outs) == len(lazy) == cfg['num_outs']
+    failed = []
+    for l, o in enumerate(outs):
+        e = PR.output_error(name, l, o)
+        print('ERR forward %-20s level %d %-10s max|diff|/max|level| %.2e (bar 2e-4)' % (name, l, tuple(o.shape[2:]), e), flush=True)
+        if not e <= 2e-4:
+            failed.append((l, e))
+        raw, (a, b) = lazy[l]
+        assert torch.equal(ops.as_nchw(ops.gn_apply(raw, a, b)), o), 'forward_lazy materialised != forward at level %d' % l
+    assert not failed, failed
+
+
+def test_single_level_pafpn_equals_fpn_bit_for_bit():
+    import pointtinybenchmark_amd as P
+    cfg = PR.cases()['pa4']
+    kw = dict(PR.neck_kwargs(cfg), start_level=3, num_outs=1)
+    sd = {k: v for k, v in synthetic.fpn_state_dict(cfg['in_channels'], cfg['out_channels'], 3, 1, 9, prefix='').items()}
+    xs = [x.cuda().contiguous(memory_format=torch.channels_last) for x in PR.case_inputs(cfg, torch.float32)]
+    res = []
+    for kind in ('PAFPN', 'FPN'):
+        neck = P.build_neck(dict(type=kind, **kw)).cuda()
+        neck.load_state_dict(sd, strict=True)
+        with torch.no_grad():
+            (o,), ((raw, (a, b)),) = neck(xs), neck.forward_lazy(xs)
+        res.append((o, raw, a, b))
+    torch.cuda.synchronize()
+    for p, f in zip(*res):
+        assert torch.equal(p, f)
+    assert len(neck.fpn_convs) == 1
+
+
+@pytest.mark.parametrize('name', PR.CASE_NAMES)
+def test_neck_backward_vs_reference_gradients(name):
+    """The recorded forward + BackwardEngine._backward_neck on the fixture's linear functional (dz of level l = w_l) against the
+    reference class's fp64 autograd: rel-L2 <= 2e-3 per tensor, on the norm and on the strided sample."""
+    from pointtinybenchmark_amd.training import BackwardEngine
+    cfg, neck, xs = _neck(name)
+    eng = BackwardEngine(_NeckOnly(neck))
+    eng._sink = {}
+    eng.begin_step()
+    tape = []
+    lazy = neck.forward_lazy(xs, tape=tape)
+    dzs = [PR.functional_weight(cfg, l, (raw.shape[0], raw.shape[3], raw.shape[1], raw.shape[2]), torch.float32)
+           .permute(0, 2, 3, 1).contiguous().cuda() for l, (raw, _) in enumerate(lazy)]
+    d_stage = eng._backward_neck(neck, tape, dzs)
+    params = dict(neck.named_parameters())
+    grads = dict(zip(params, eng.collect(list(params.values()))))
+    torch.cuda.synchronize()
+    s = cfg.get('start_level', 0)
+    assert sorted(d_stage) == list(range(s, 4))
+    for i, d in d_stage.items():
+        grads['in%d' % i] = d.permute(0, 3, 1, 2)
+    assert set(grads) == set(PR.grad_names(name))
+    failed = []
+    for k in sorted(grads):
+        assert grads[k] is not None and bool(torch.isfinite(grads[k]).all()), k
+        en, es = PR.grad_errors(name, k, grads[k])
+        print('ERR backward %-20s %-34s norm %.2e  sample rel-L2 %.2e (bar 2e-3)' % (name, k, en, es), flush=True)
+        if not (en <= 2e-3 and es <= 2e-3):
+            failed.append((k, en, es))
+    assert not failed, failed
+
+
+# ------------------------------------------------------------------------------------------------ the whole locator
+LOCATORS = {
+    #               start_level, num_outs, add_extra_convs, strides
+    'pa4':         (0, 4, False, [4, 8, 16, 32]),
+    'pa_on_input': (1, 5, 'on_input', [8, 16, 32, 64, 128]),
+}
+GRAD_SEED = {'pa4': 119, 'pa_on_input': 74}       # admitted by tools/pafpn_locator_conditioning.py (test_locator_gradients_vs_fp64_autograd)
+
+
+def build_locator(kind, C=2, seed=3, depth=18, test_cfg=None, neck_type='PAFPN'):
+    import pointtinybenchmark_amd as P
+    from bench import p2p_model_cfg
+    start, num_outs, extra, strides = LOCATORS[kind]
+    cfg = p2p_model_cfg(depth, C)
+    cfg['neck'] = dict(cfg['neck'], type=neck_type, start_level=start, num_outs=num_outs, add_extra_convs=extra)
+    cfg['bbox_head'] = dict(cfg['bbox_head'], strides=strides, point_anchor=list(GRID4))
+    if test_cfg:
+        cfg['test_cfg'] = dict(cfg['test_cfg'], **test_cfg)
+    m = P.build_detector(cfg).cuda()
+    sd = synthetic.locator_state_dict(depth, C, start, 'p2p', seed, head_std=0.05, num_points=4)
+    sd = {k: v for k, v in sd.items() if not k.startswith('neck.')}
+    make = synthetic.pafpn_state_dict if neck_type == 'PAFPN' else synthetic.fpn_state_dict
+    sd.update(make(synthetic.backbone_out_channels(depth), 256, start, num_outs, seed + 1, add_extra_convs=extra))
+    m.load_state_dict(sd, strict=True)
+    m.train()
+    return m, sd
+
+
+def _is_bottom_up(name):
+    return name.startswith(('neck.downsample_convs.', 'neck.pafpn_convs.'))
+
+
+@pytest.mark.parametrize('kind', list(LOCATORS))
+def test_locator_gradients_vs_fp64_autograd(kind):
+    """P2PTrainer.forward_backward on BasicLocator(R18, PAFPN, P2PHead, the 4-point grid, C=2) against fp64 autograd of the oracle
+    backbone -> tests/pafpn_ref.pafpn_forward -> oracle head / loss, on the device's own assignment: losses within 3e-4, gradients
+    <= 2e-3 relative L2 per parameter tensor.
+    The data seed is admitted by the reference alone, as in tests/test_gpu_fpn_extra.py (the loss has kinks; see there):
+    tools/pafpn_locator_conditioning.py runs this very oracle network in fp32 against its fp64 run on the CPU and admits a seed whose
+    worst tensor stays within a quarter of the bar (5e-4), and reports the fp64 run's kink exposure: over the head towers' ReLU inputs
+    within the reference's own fp32 error of zero (|y| < 1e-5), the most that ONE of them flipping moves its layer's GroupNorm-bias
+    gradient.  Whether such an input flips is a matter of the evaluation's rounding, not of the network: 'pa4' seed 7 passes the first
+    condition at 2.9e-5 and has an input of 6.0e-7 carrying 4.7e-3, which the HIP step lands on the other side of (every tensor from
+    reg_convs.2 down then moves by 2e-3 .. 4.7e-3); 'pa_on_input' seed 17 (2.0e-5) has one of 6.2e-6 under cls_convs.3 (4.4e-3 .. 1e-2
+    from there down).  A seed is admitted when one flip alone stays below the bar; each locator takes the admitted seed with the least
+    exposure of the 400 / 240 scanned: 'pa4' seed 119 (fp32 vs fp64 2.2e-5, exposure 1.4e-3), 'pa_on_input' seed 74 (1.7e-5, 9.2e-4)."""
+    from pointtinybenchmark_amd.training import P2PTrainer
+    start, num_outs, extra, strides = LOCATORS[kind]
+    m, sd = build_locator(kind)
+    batch, data = _data(seed=GRAD_SEED[kind])
+    rec = _record_assignments(m.bbox_head)
+    tr = P2PTrainer(m, lr=1e-3)
+    losses = tr.forward_backward(**data)
+    torch.cuda.synchronize()
+    gt_inds = rec[-1].cpu()
+    assert int((gt_inds > 0).sum()) > 0 and gt_inds.shape[1] == sum(h * w * 4 for h, w in _cells(strides))
+    trainable = {k for k, p in m.named_parameters() if p.requires_grad}
+    assert any(_is_bottom_up(k) for k in trainable)
+    sd64 = {k: v.double().requires_grad_(k in trainable) for k, v in sd.items()}
+    head = m.bbox_head
+    feats = O.resnet_forward(sd64, batch['img'].double(), depth=18)
+    outs = PR.pafpn_forward(sd64, list(feats), num_outs, start, extra, prefix='neck.')
+    assert [tuple(o.shape[2:]) for o in outs] == _cells(strides)
+    co, po = O.p2p_head_forward(sd64, outs)
+    pred, cls = PO.get_pred_points(co, po, strides, GRID4, head.pts_gamma, 2)
+    ctr = [(b[:, :2] + b[:, 2:]) / 2 for b in batch['gt_bboxes']]
+    counts = [len(c) for c in ctr]
+    rc, rp = PO.p2p_loss_from_assignment(cls, pred, gt_inds, torch.cat(ctr).double(), torch.cat(list(batch['gt_labels'])),
+                                         torch.tensor([0] + counts[:-1]).cumsum(0), 0.25, 2.0, 1.0 / 9.0, 1.0, 1.0, head.reg_norm,
+                                         1.0, 0.5, 0, 0)
+    got_l = torch.tensor([[float(losses['loss_cls'][b]), float(losses['loss_pts'][b])] for b in range(2)], dtype=torch.float64)
+    ref_l = torch.stack([rc, rp], 1).detach()
+    print('ERR locator %-12s losses max|diff| %.2e (bar 3e-4 * %.3f)' % (kind, float((got_l - ref_l).abs().max()),
+                                                                        max(1.0, float(ref_l.abs().max()))), flush=True)
+    assert float((got_l - ref_l).abs().max()) <= 3e-4 * max(1.0, float(ref_l.abs().max())), (got_l, ref_l)
+    (rc.sum() + rp.sum()).backward()
+    gmax = max(float(sd64[k].grad.norm()) for k in trainable)
+    params = dict(m.named_parameters())
+    failed = []
+    for k in sorted(trainable):
+        gr, ref = params[k].grad.detach().double().cpu().flatten(), sd64[k].grad.flatten()
+        rel = float((gr - ref).norm()) / max(float(ref.norm()), 1e-5 * gmax)
+        print('ERR locator %-12s %-44s rel %.2e |g|/gmax %.1e (bar 2e-3)' % (kind, k, rel, float(ref.norm()) / gmax), flush=True)
+        if not rel <= 2e-3:
+            failed.append((k, rel))
+    assert not failed, failed
+
+
+@pytest.mark.parametrize('kind', list(LOCATORS))
+def test_bridge_is_bit_equal_to_the_trainer_and_steps_repeat(kind):
+    from pointtinybenchmark_amd import autograd_bridge
+    from pointtinybenchmark_amd.training import P2PTrainer
+    _, data = _data(seed=8)
+    ma, _ = build_locator(kind)
+    assert autograd_bridge.unsupported_reason(ma, data['gt_bboxes'], data['gt_labels']) is None
+    tr = P2PTrainer(ma)
+    la = tr.forward_backward(**data)
+    torch.cuda.synchronize()
+    want = {k: p.grad.clone() for k, p in ma.named_parameters() if p.requires_grad}
+    mb, _ = build_locator(kind)
+    out = mb.train_step(dict(data))
+    assert out['loss'].requires_grad and out['loss'].grad_fn is not None
+    out['loss'].backward()
+    torch.cuda.synchronize()
+    la_total = float(sum(sum(v) for k, v in la.items() if 'loss' in k))
+    assert abs(out['log_vars']['loss'] - la_total) <= 1e-6 * max(1.0, abs(la_total))
+    for k, p in mb.named_parameters():
+        if p.requires_grad:
+            assert p.grad is not None and torch.equal(p.grad, want[k]), k
+    mc, _ = build_locator(kind)
+    trc = P2PTrainer(mc)
+    for _ in range(2):
+        tr.forward_backward(**data)
+        tr.step()
+        trc.forward_backward(**data)
+        trc.step()
+        torch.cuda.synchronize()
+        assert torch.equal(tr.flat_g, trc.flat_g)
+    pa, pc = dict(ma.named_parameters()), dict(mc.named_parameters())
+    for k in pa:
+        assert torch.equal(pa[k], pc[k]), k
+
+
+@pytest.mark.parametrize('kind', list(LOCATORS))
+def test_three_sgd_steps_lower_the_loss(kind):
+    from pointtinybenchmark_amd.training import P2PTrainer
+    m, _ = build_locator(kind)
+    _, data = _data()
+    with torch.no_grad():
+        ref = m.forward_train(**data)
+        ref_total = sum(float(v) for vs in ref.values() for v in vs)
+    tr = P2PTrainer(m, lr=2e-4, momentum=0.9, weight_decay=1e-4, max_norm=35.0)
+    mods = list(m.neck.fpn_convs) + list(m.neck.downsample_convs) + list(m.neck.pafpn_convs)
+    w0 = [cm.conv.weight.detach().clone() for cm in mods]
+    totals = []
+    for _ in range(3):
+        out = tr.train_step(dict(data))
+        assert out['log_vars']['loss'] == out['log_vars']['loss'] and abs(out['log_vars']['loss']) < float('inf')
+        totals.append(out['log_vars']['loss'])
+    print('ERR steps %-12s totals %s (forward-only %.6f)' % (kind, totals, ref_total), flush=True)
+    assert abs(totals[0] - ref_total) <= 1e-4 * max(1.0, abs(ref_total)), (totals[0], ref_total)
+    assert totals[2] < totals[0], totals
+    for cm, w in zip(mods, w0):
+        assert float((cm.conv.weight - w).abs().max()) > 0, 'every neck conv, the bottom-up path included, trains'
+
+
+@pytest.mark.parametrize('kind', list(LOCATORS))
+def test_bucket_ready_points_only_cover_finished_gradients(kind):
+    from pointtinybenchmark_amd import training
+    m, _ = build_locator(kind)
+    seen = []
+
+    class Checked(training.P2PTrainer):
+        def _done(self, p):
+            end = self.offset[id(p)][1]
+            torch.cuda.synchronize()
+            assert not bool(torch.isnan(self.flat_g[:end]).any()), 'gradient prefix [0, %d) declared final unwritten' % end
+            seen.append(end)
+    tr = Checked(m)
+    tr.flat_g.fill_(float('nan'))
+    _, data = _data(seed=8)
+    tr.forward_backward(**data)
+    torch.cuda.synchronize()
+    assert not bool(torch.isnan(tr.flat_g).any())
+    assert seen and max(seen) == tr.flat_g.numel() and seen == sorted(seen)
+    ends = {tr.offset[id(cm.conv.weight)][1] for cm in list(m.neck.downsample_convs) + list(m.neck.pafpn_convs) + list(m.neck.fpn_convs)}
+    assert ends <= set(seen), 'every neck conv declares its gradients final'
+
+
+def test_mixed_precision_step_tracks_the_fp32_step():
+    """The bf16 compute mode on the 'pa_on_input' locator, with the bars of
+    tests/test_gpu_fpn_extra.py::test_mixed_precision_step_with_extras_tracks_the_fp32_step and its data seed (22: admitted there on the
+    base network, which is this locator's too): worst large head / neck tensor <= 0.25 (the bottom-up modules count as neck tensors),
+    worst large backbone tensor <= 0.5, losses within 5e-2, bf16 gradient kernels against the fp32 ones behind the same bf16 forward
+    <= 0.02; the bottom-up modules' and the extras' own tensors, same comparison, <= 0.03.  Then the bridge, bit-equal to the native
+    mixed step."""
+    from pointtinybenchmark_amd import training
+    from pointtinybenchmark_amd.training import P2PTrainer
+    m, _ = build_locator('pa_on_input')
+    _, data = _data(seed=22)
+    rec = _record_assignments(m.bbox_head)
+    tr = P2PTrainer(m, lr=1e-3)
+    l32 = tr.forward_backward(**data)
+    torch.cuda.synchronize()
+    g32, inds32 = tr.flat_g.clone(), rec[-1]
+    rec16 = _record_assignments(m.bbox_head, force=inds32)
+    m.set_compute_dtype('bf16')
+    l16 = tr.forward_backward(**data)
+    torch.cuda.synchronize()
+    g16 = tr.flat_g.clone()
+    assert torch.equal(rec16[-1], inds32) and torch.isfinite(g16).all()
+    training.MIXED_BF16.update(wgrad=False, dgrad=False)
+    try:
+        tr.forward_backward(**data)
+        torch.cuda.synchronize()
+    finally:
+        training.MIXED_BF16.update(wgrad=True, dgrad=True)
+    gk = tr.flat_g.clone()
+    gmax = max(float(p.grad.norm()) for p in m.parameters() if p.requires_grad)
+    names = {id(p): k for k, p in m.named_parameters()}
+    L = len(m.neck.lateral_convs)
+
+    def new(k):      # the bottom-up modules and the extra levels' convs
+        return _is_bottom_up(k) or (k.startswith('neck.fpn_convs.') and int(k.split('.')[2]) >= L)
+    rows, off, hn16, hn32, worst_k, worst_new = [], 0, [], [], 0.0, 0.0
+    for p_ in tr.params:
+        n, k = p_.numel(), names[id(p_)]
+        a, b, c = g16[off:off + n].double(), g32[off:off + n].double(), gk[off:off + n].double()
+        off += n
+        rows.append((float((a - b).norm() / max(float(b.norm()), 1e-30)), float(b.norm()) / gmax, k))
+        relk = float((a - c).norm() / max(float(c.norm()), 1e-30))
+        if new(k):
+            print('ERR mixed new %-40s bf16 vs fp32 backward %.3e (bar 0.03)  vs fp32 step %.3e  |g|/gmax %.2e' % (k, relk, rows[-1][0], rows[-1][1]),
+                  flush=True)
+            worst_new = max(worst_new, relk)
+        elif float(c.norm()) >= 1e-2 * gmax:
+            worst_k = max(worst_k, relk)
+        if not k.startswith('backbone.'):
+            hn16.append(a), hn32.append(b)
+    for r in sorted(rows, reverse=True)[:8]:
+        print('ERR mixed %-44s rel %.3e  |g|/gmax %.2e' % (r[2], r[0], r[1]), flush=True)
+    big = [r for r in rows if r[1] >= 1e-2]
+    worst_hn = max(r[0] for r in big if not r[2].startswith('backbone.'))
+    worst_bb = max([r[0] for r in big if r[2].startswith('backbone.')] or [0.0])
+    a, b = torch.cat(hn16), torch.cat(hn32)
+    cos = float(torch.dot(a, b) / (a.norm() * b.norm()))
+    print('ERR mixed head+neck cos %.5f worst %.4f | backbone worst %.4f | kernels worst %.4f | new modules worst %.4f'
+          % (cos, worst_hn, worst_bb, worst_k, worst_new), flush=True)
+    assert worst_new <= 0.03, 'bottom-up / extra modules: bf16 backward against the fp32 backward behind the same bf16 forward: %.4f' % worst_new
+    assert worst_k <= 0.02, 'bf16 gradient kernels against fp32 ones behind the same bf16 forward: %.4f' % worst_k
+    for k in ('loss_cls', 'loss_pts'):
+        x, y = sum(float(v) for v in l16[k]), sum(float(v) for v in l32[k])
+        assert abs(x - y) <= 5e-2 * max(1.0, abs(y)), (k, x, y)
+    assert worst_hn <= 0.25, 'mixed-precision gradient, worst relative L2 over the large head / neck tensors: %.3f' % worst_hn
+    assert worst_bb <= 0.5, 'mixed-precision gradient, worst relative L2 over the large backbone tensors: %.3f' % worst_bb
+    mb, _ = build_locator('pa_on_input')
+    mb.set_compute_dtype('bf16')
+    _record_assignments(mb.bbox_head, force=inds32)
+    tr.forward_backward(**data)
+    torch.cuda.synchronize()
+    want = {k: p.grad.clone() for k, p in m.named_parameters() if p.requires_grad}
+    out = mb.train_step(dict(data))
+    out['loss'].backward()
+    torch.cuda.synchronize()
+    for k, p in mb.named_parameters():
+        if p.requires_grad:
+            assert p.grad is not None and torch.equal(p.grad, want[k]), k
+
+
+@pytest.mark.parametrize('name', PR.CASE_NAMES)
+def test_bf16_forward_against_fpn_as_the_yardstick(name):
+    """PAFPN in bf16 against PAFPN in fp32, relative L2 per level; FPN on the same inputs and weights, measured the same way, is the
+    yardstick: PAFPN's worst level may be at most twice FPN's worst level (every PAFPN level stacks two more bf16 conv + GN layers
+    behind FPN's)."""
+    worst = {}
+    for kind in ('PAFPN', 'FPN'):
+        _, neck, xs = _neck(name, kind=kind)
+        with torch.no_grad():
+            o32 = neck(xs)
+            o16 = neck([x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last) for x in xs])
+        torch.cuda.synchronize()
+        assert all(o.dtype == torch.bfloat16 for o in o16)
+        rel = [float((a.double() - b.double()).norm() / b.double().norm()) for a, b in zip(o16, o32)]
+        print('ERR bf16 forward %-20s %-5s per level %s' % (name, kind, ' '.join('%.3e' % r for r in rel)), flush=True)
+        worst[kind] = max(rel)
+    print('ERR bf16 forward %-20s worst PAFPN %.4e  FPN %.4e  ratio %.3f (bar 2)' % (name, worst['PAFPN'], worst['FPN'],
+                                                                                    worst['PAFPN'] / worst['FPN']), flush=True)
+    assert worst['PAFPN'] <= 2.0 * worst['FPN'], worst
+
+
+# ------------------------------------------------------------------------------------------------ inference
+def test_extract_feat_returns_the_levels():
+    for kind, want in (('pa4', [(32, 40), (16, 20), (8, 10), (4, 5)]), ('pa_on_input', [(16, 20), (8, 10), (4, 5), (2, 3), (1, 2)])):
+        m, _ = build_locator(kind)
+        m.eval()
+        _, data = _data()
+        with torch.no_grad():
+            feats = m.extract_feat(data['img'])
+        torch.cuda.synchronize()
+        assert [tuple(f.shape) for f in feats] == [(2, 256) + hw for hw in want]
+        assert all(bool(torch.isfinite(f).all()) for f in feats)
+
+
+def test_simple_test_respects_max_per_img():
+    """64 x 160: 215 cells over the five levels -- the reference cuts the concatenated proposals into len(strides) equal chunks
+    (p2p_head.py:357), so their number must divide by 5."""
+    m, _ = build_locator('pa_on_input', test_cfg=dict(max_per_img=7, score_thr=0.0))
+    m.eval()
+    _, data = _data(hw=(64, 160))
+    with torch.no_grad():
+        res = m.simple_test(data['img'], data['img_metas'])
+    torch.cuda.synchronize()
+    assert len(res) == 2
+    for dets, labels in res:
+        assert dets.shape[0] == labels.shape[0] == 7 and dets.shape[1] >= 5 and bool(torch.isfinite(dets).all())
