@@ -236,7 +236,8 @@ int cpr_logit_project(const float* x, const float* w, const float* bias, const f
  * = block partial sums of gfocal(prob(logit), 0, valid).  d2_thr = smallest fp32 whose torch-CPU sqrt is
  * >= stride*radius (the reference thresholds cdist, i.e. a sqrt).  n_partial [host, may be NULL] receives the count.
  * mask_classes = C, or 1 with C = 2 (normal_cfg.out_bg_cls, cpr_head.py:953: the one-class validity broadcasts over
- * [class, background] outputs). */
+ * [class, background] outputs).  CPR_ERR_ARG when stride <= 0, N > 65535 or H*W*C (rounded up to whole 256-thread blocks)
+ * does not fit an int. */
 int cpr_neg_mask_loss(const float* logit, int J, const float* centers, const int* labels, const int* gt_start,
                       const int* pad_hw, unsigned char* mask, double* partial, int N, int H, int W, int C,
                       float stride, float d2_thr, float eps, int class_wise, int prob_type, float norm_p,
@@ -268,7 +269,8 @@ int cpr_grid_bag(const float* map, int J, const float* points, const int* gt_img
  * entries of bag b: b*bag_stride + ctr_off + j*ctr_stride (j < ctr_count), used when b % ctr_mod == 0.
  * labels / gt_weight are per bag.  allpos = AllPosLoss instead of MILLoss.  bag_ws (num_bags,5) workspace.
  * out5 = {gt_loss, pos_loss, bag_acc, neg_loss, num_sample} (device scalars, no host sync); neg_from_gt: average the
- * negative loss over the gt count instead of num_sample (with_mil_loss = False). */
+ * negative loss over the gt count instead of num_sample (with_mil_loss = False).  CPR_ERR_ARG when ins_off < 0, J < C,
+ * ctr_stride < 0 (with ctr_count > 0) or an annotated-point entry falls outside its bag's stride. */
 int cpr_mil_loss(const float* logits, int J, int ins_off, const unsigned char* valid, const int* labels,
                  const float* gt_weight, float* bag_ws, const double* neg_partial, int n_partial, int num_bags,
                  int bag_stride, int bag_off, int bag_len, int ctr_off, int ctr_stride, int ctr_count, int ctr_mod,

@@ -130,6 +130,9 @@ extern "C" int cpr_neg_mask_loss(const float* logit, int J, const float* centers
     CPR_CHECK_ARG(logit && gt_start && pad_hw && mask && partial && N > 0 && H > 0 && W > 0 && C > 0 && J >= C);
     CPR_CHECK_ARG(mask_classes == C || (mask_classes == 1 && C == 2));   // the reference's broadcast only exists for one class
     CPR_CHECK_ARG(prob_type >= 0 && prob_type <= 2 && norm_p > 0.f);
+    CPR_CHECK_ARG(stride > 0.f && N <= 65535);
+    // one thread per (pixel, class), indexed in int: the last block's thread indices must fit as well
+    CPR_CHECK_ARG((long long)H * W * C <= 0x7fffffffll - 255);
     const int blocks = cdiv(H * W * C, 256);
     if (n_partial) *n_partial = blocks * N;
     hipLaunchKernelGGL(neg_mask_loss_kernel, dim3(blocks, N), dim3(256), 0, stream, logit, J, centers, labels,
@@ -555,8 +558,10 @@ extern "C" int cpr_mil_loss(const float* logits, int J, int ins_off, const unsig
                             hipStream_t stream) {
     const int G = num_bags, K = bag_len;
     CPR_CHECK_ARG(G > 0 && K > 0 && C > 0 && bag_off >= 0 && bag_stride >= bag_off + K && ctr_count >= 0 && ctr_mod >= 1);
-    CPR_CHECK_ARG(J >= ins_off + C * (binary_ins ? 2 : 1) && logits && valid && labels && bag_ws && out5);
-    CPR_CHECK_ARG(ctr_count == 0 || (ctr_off >= 0 && ctr_off + (ctr_count - 1) * ctr_stride < bag_stride));
+    CPR_CHECK_ARG(ins_off >= 0 && J >= C && (long long)J >= (long long)ins_off + (long long)C * (binary_ins ? 2 : 1));
+    CPR_CHECK_ARG(logits && valid && labels && bag_ws && out5);
+    CPR_CHECK_ARG(ctr_count == 0 || (ctr_off >= 0 && ctr_stride >= 0 &&
+                                     (long long)ctr_off + (long long)(ctr_count - 1) * ctr_stride < bag_stride));
     CPR_CHECK_ARG(prob_type >= 0 && prob_type <= 3 && norm_p > 0.f && (n_partial == 0 || neg_partial));
     const int terms = C * (binary_ins ? 2 : 1);
     if (!allpos && terms >= MIL_NW && terms <= MIL_MAXT)       // many classes: one workgroup per bag, classes over its waves
