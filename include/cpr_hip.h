@@ -486,6 +486,39 @@ int cpr_gn_apply2(const float* x1, const float* a1, const float* b1, const float
                   int W, int C, void* stream);
 int cpr_gn_apply2_bf16(const void* x1, const float* a1, const float* b1, const void* x2, const float* a2, const float* b2, void* y, int N,
                        int H, int W, int C, void* stream);
+/* BFP neck, the Balanced Feature Pyramid (bfp.py:69-101; csrc/bfp.hip), NHWC.  One launch each over a HOST table of L <= 8 levels,
+ * finest first; r = refine_level, (h, w) = the size of level r.  A level finer than r is pooled to (h, w) by adaptive max (window i of an
+ * axis = [floor(i*in/out), ceil((i+1)*in/out)), first maximum in row-major order), level r and coarser ones are resized by nearest
+ * (src = min((int)floorf(dst * scale), in - 1), scale = (float)in / (float)out: sy, sx are formed by the HOST in fp32); the scatter runs
+ * the other way round.  a, b (N,C): the pending GroupNorm affine of a raw level, applied on load, or both null.  arg: the recorded argmax
+ * of every pooled window, (N, out_h, out_w, C) window-local codes -- uint8 (ly << 4 | lx) when no window side exceeds 16, else with
+ * arg_wide uint16 (ly << 8 | lx); CPR_ERR_UNSUPPORTED for a window beyond the chosen width.
+ *   cpr_bfp_gather        x = level_i [a, b]; sy = (float)H/h, sx = (float)W/w (levels >= r); arg: optional record (levels < r).
+ *                         bsf (N,h,w,C) = (sum_i feat_i) / L
+ *   cpr_bfp_scatter       x = level_i [a, b], y = out_i = residual_i + level_i; sy = (float)h/H, sx = (float)w/W (levels < r); arg: optional
+ *                         record (levels > r).  ref (N,h,w,C): the refined map, materialised, or raw under ref_a, ref_b (N,C) AND ReLU
+ *   cpr_bfp_scatter_bwd   x = g_i (the level's shape), sy / sx as in the scatter, arg: its record (levels > r).  d_ref (N,h,w,C) = the sum
+ *                         over the levels in ascending order, gather form, no atomics
+ *   cpr_bfp_gather_bwd    x = g_i, y = d_level_i = g_i + (d_bsf / L routed back), sy / sx as in the gather, arg: its record (levels < r)
+ * fp32: C%4==0; _bf16: levels, bsf / ref and out_i bf16, C%8==0, fp32 arithmetic, one rounding at the store.  The backward maps are fp32.
+ * Every map below 2^31 elements.  Bit-repeatable; an image's result does not depend on the batch. */
+typedef struct cpr_bfp_level {
+    const void* x;
+    const float* a;
+    const float* b;
+    void* y;
+    void* arg;
+    int H, W;
+    float sy, sx;
+} cpr_bfp_level;
+int cpr_bfp_gather(const cpr_bfp_level* levels, int L, int refine_level, float* bsf, int N, int C, int arg_wide, void* stream);
+int cpr_bfp_gather_bf16(const cpr_bfp_level* levels, int L, int refine_level, void* bsf, int N, int C, int arg_wide, void* stream);
+int cpr_bfp_scatter(const cpr_bfp_level* levels, int L, int refine_level, const float* ref, const float* ref_a, const float* ref_b, int N,
+                    int C, int arg_wide, void* stream);
+int cpr_bfp_scatter_bf16(const cpr_bfp_level* levels, int L, int refine_level, const void* ref, const float* ref_a, const float* ref_b,
+                         int N, int C, int arg_wide, void* stream);
+int cpr_bfp_scatter_bwd(const cpr_bfp_level* levels, int L, int refine_level, float* d_ref, int N, int C, int arg_wide, void* stream);
+int cpr_bfp_gather_bwd(const cpr_bfp_level* levels, int L, int refine_level, const float* d_bsf, int N, int C, int arg_wide, void* stream);
 /* d(gt_loss + pos_loss + neg_loss)/d(logit map) of CPRHead.loss (cpr_head.py:1101-1229): negative-grid term, MIL bag
  * and gt-centre terms taken back through the bilinear taps -- deterministically: every bag's taps are gathered into a
  * win x win cell window (win >= 2 * ceil(max |offset| / stride) + 3; win_ws (G, win, win, J) fp32 and win_org (G, 2) int32

@@ -103,6 +103,12 @@ SIGNATURES = {
     'cpr_relu_mask_add': [_p, _p, _p, _i, _p, _l, _p],
     'cpr_gn_apply2': [_p] * 7 + [_i] * 4 + [_p],
     'cpr_gn_apply2_bf16': [_p] * 7 + [_i] * 4 + [_p],
+    'cpr_bfp_gather': [_p, _i, _i, _p, _i, _i, _i, _p],
+    'cpr_bfp_gather_bf16': [_p, _i, _i, _p, _i, _i, _i, _p],
+    'cpr_bfp_scatter': [_p, _i, _i, _p, _p, _p, _i, _i, _i, _p],
+    'cpr_bfp_scatter_bf16': [_p, _i, _i, _p, _p, _p, _i, _i, _i, _p],
+    'cpr_bfp_scatter_bwd': [_p, _i, _i, _p, _i, _i, _i, _p],
+    'cpr_bfp_gather_bwd': [_p, _i, _i, _p, _i, _i, _i, _p],
     'cpr_loss_bwd': [_p] * 15 + [_i] * 10 + [_f] * 5 + [_p, _p],
     'cpr_bag_gather_bwd': [_p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p],
     'cpr_bag_points_gather_bwd': [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p],

@@ -33,7 +33,7 @@ import warnings
 import torch
 from torch.autograd.function import once_differentiable
 
-from .training import BackwardEngine, P2PBackwardEngine
+from .training import _BFP_UNDER_CPR, BackwardEngine, P2PBackwardEngine, _bfp_of, _inner_neck
 
 
 class _GtPack:
@@ -59,14 +59,17 @@ class Bridge:
         if getattr(engine, '_sink', None) is None:
             engine._sink = {}           # gradients go to fresh tensors handed to torch (any engine, also a caller's own)
         self.engine = engine
-        bb, neck = model.backbone, model.neck
+        bb, neck, bfp = model.backbone, _inner_neck(model.neck), _bfp_of(model.neck)
         self._maps = {}         # bf16 compute mode: data_ptr of an fp32 carrier -> the bf16 map it stands for (see carrier())
         self.stem_params = [p for m in (getattr(bb, 'conv1', None), getattr(bb, 'bn1', None)) if m is not None
                             for p in m.parameters() if p.requires_grad]
         self.stage_params = [[p for p in getattr(bb, name).parameters() if p.requires_grad] for name in bb.res_layers]
         self.lateral_params = [p for cm in neck.lateral_convs for p in cm.parameters() if p.requires_grad]
         # (a PAFPN's bottom-up modules sit between the output convs and the head: the same Function)
+        # (so does the refine layer of a BFP behind the neck)
         neck_out = list(neck.fpn_convs) + list(getattr(neck, 'downsample_convs', ())) + list(getattr(neck, 'pafpn_convs', ()))
+        if bfp is not None and bfp.refine_type is not None:
+            neck_out.append(bfp.refine)
         self.head_params = [p for p in [q for cm in neck_out for q in cm.parameters()] + list(head.parameters())
                             if p.requires_grad]
         # add_extra_convs='on_input': the first extra conv reads the last backbone stage's output, one more differentiable input
@@ -98,6 +101,10 @@ def signature(model):
 def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     """None when ``forward_train`` can be differentiable, else why not."""
     bb, neck, head = model.backbone, model.neck, model.bbox_head
+    if _bfp_of(neck) is not None:       # neck=[FPN | PAFPN, BFP] (necks/bfp.py NeckSequence checks the chain when it is built)
+        if type(head).__name__ == 'CPRHead':
+            return _BFP_UNDER_CPR
+        neck = _inner_neck(neck)
     if neck is None or type(neck).__name__ not in ('FPN', 'PAFPN') or len(neck.fpn_convs) < 1:
         return 'needs an FPN neck'
     n_outs = min(len(neck.lateral_convs), neck.num_outs) + getattr(neck, 'extra_levels', 0)    # outputs, not fpn_convs: max-pool extras
@@ -286,7 +293,7 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
     eng.begin_step()
     eng._sink.clear()
     bridge._maps.clear()
-    bb, neck = model.backbone, model.neck
+    bb, neck = model.backbone, _inner_neck(model.neck)
     if bridge.stem_params:
         x = _StemFn.apply(bridge, img.detach(), *bridge.stem_params)
     else:

@@ -113,7 +113,8 @@ class BasicLocator(nn.Module):
             return self.bbox_head.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore,
                                        **({'gt_true_bboxes': gt_true_bboxes} if 'CPR' in type(self.bbox_head).__name__
                                           else {}))
-        if self.with_neck and hasattr(self.neck, 'forward_lazy') and hasattr(self.bbox_head, 'forward_train_lazy'):
+        if self.with_neck and hasattr(self.neck, 'forward_lazy') and hasattr(self.bbox_head, 'forward_train_lazy') and \
+                not getattr(self.neck, 'materialised', False):      # (a [.., BFP] neck hands over materialised levels)
             lazy = self.neck.forward_lazy(self.backbone(img), out_b8=getattr(self.bbox_head, 'accepts_b8', False))
             return self.bbox_head.forward_train_lazy(lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore,
                                                      gt_true_bboxes)

@@ -1,2 +1,3 @@
 from .fpn import FPN  # noqa: F401
 from .pafpn import PAFPN  # noqa: F401
+from .bfp import BFP, NeckSequence  # noqa: F401

@@ -994,6 +994,128 @@ def gn_apply2(x1, a1, b1, x2, a2, b2, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ BFP neck (csrc/bfp.hip)
+class _BfpLevel(ctypes.Structure):      # include/cpr_hip.h: cpr_bfp_level
+    _fields_ = [('x', ctypes.c_void_p), ('a', ctypes.c_void_p), ('b', ctypes.c_void_p), ('y', ctypes.c_void_p), ('arg', ctypes.c_void_p),
+                ('H', ctypes.c_int), ('W', ctypes.c_int), ('sy', ctypes.c_float), ('sx', ctypes.c_float)]
+
+
+BFP_MAX_LEVELS = 8
+
+
+def nearest_scale(n_in, n_out):
+    """The scale of torch's nearest resize of an axis from n_in to n_out cells: ONE fp32 division, formed here on the host.
+    src = min(int(floorf(float(dst) * scale)), n_in - 1) -- ``nearest_index`` -- is torch's index for every dtype."""
+    import numpy as np
+    return float(np.float32(n_in) / np.float32(n_out))
+
+
+def nearest_index(n_in, n_out):
+    """The source index of every destination cell of a nearest resize, as the kernels compute it (numpy float32)."""
+    import numpy as np
+    src = np.floor(np.arange(n_out, dtype=np.float32) * np.float32(nearest_scale(n_in, n_out))).astype(np.int64)
+    return np.minimum(src, n_in - 1)
+
+
+def adaptive_windows(n_in, n_out):
+    """[(start, end)] of the n_out windows of adaptive pooling over an axis of n_in cells: [floor(i*in/out), ceil((i+1)*in/out))."""
+    return [((i * n_in) // n_out, -((-(i + 1) * n_in) // n_out)) for i in range(n_out)]
+
+
+def _bfp_arg_dtype(pairs):
+    """The code width of the recorded argmax for the pooled axes ``pairs`` = [(n_in, n_out)]: uint8 while no window side exceeds 16."""
+    widest = max([e - s for n_in, n_out in pairs for s, e in adaptive_windows(n_in, n_out)] + [1])
+    if widest > 256:
+        raise _lib.CprHipError('BFP: an adaptive-pooling window of %d cells cannot be recorded (256 at most)' % widest)
+    return torch.uint8 if widest <= 16 else torch.int16
+
+
+def _bfp_split(levels):
+    """levels: per level a materialised NHWC map, or (raw map, (a, b)) -> maps, [(a, b) | (None, None)]."""
+    maps, abs_ = [], []
+    for lv in levels:
+        x, ab = (lv, (None, None)) if torch.is_tensor(lv) else (lv[0], tuple(lv[1]))
+        maps.append(x), abs_.append(ab)
+    N, _, _, C = _check(maps[0], ACT).shape
+    for x, (a, b) in zip(maps, abs_):
+        assert _check(x, ACT).dtype == maps[0].dtype and x.shape[0] == N and x.shape[3] == C, (x.shape, maps[0].shape)
+        assert (a is None) == (b is None) and (a is None or tuple(_check(a).shape) == tuple(_check(b).shape) == (N, C))
+    assert 1 <= len(maps) <= BFP_MAX_LEVELS, 'BFP takes 1 .. %d levels' % BFP_MAX_LEVELS
+    return maps, abs_
+
+
+def _bfp_table(rows):
+    t = (_BfpLevel * len(rows))()
+    for e, (x, a, b, y, arg, H, W, sy, sx) in zip(t, rows):
+        e.x, e.a, e.b = x.data_ptr(), (a.data_ptr() if a is not None else None), (b.data_ptr() if b is not None else None)
+        e.y, e.arg = (y.data_ptr() if y is not None else None), (arg.data_ptr() if arg is not None else None)
+        e.H, e.W, e.sy, e.sx = H, W, sy, sx
+    return t
+
+
+def bfp_gather(levels, refine_level, record=False):
+    """BFP step 1 (bfp.py:73-85): bsf (N, h, w, C) = mean over the levels of adaptive_max_pool2d (levels finer than refine_level) /
+    nearest (the others) to level refine_level's size, one launch.  levels: materialised NHWC maps or (raw, (a, b)) pairs.
+    record: also the argmax of every window -> (bsf, [arg | None per level])."""
+    maps, abs_ = _bfp_split(levels)
+    r = int(refine_level)
+    N, h, w, C = maps[r].shape
+    dt = _bfp_arg_dtype([p for x in maps[:r] for p in ((x.shape[1], h), (x.shape[2], w))]) if record else torch.uint8
+    args = [torch.empty((N, h, w, C), device=maps[0].device, dtype=dt) if record and i < r else None for i in range(len(maps))]
+    bsf = torch.empty((N, h, w, C), device=maps[0].device, dtype=maps[0].dtype)
+    rows = [(x, a, b, None, g, x.shape[1], x.shape[2], nearest_scale(x.shape[1], h), nearest_scale(x.shape[2], w))
+            for x, (a, b), g in zip(maps, abs_, args)]
+    _lib.call('cpr_bfp_gather' + _sfx(bsf), _bfp_table(rows), len(maps), r, _ptr(bsf), N, C, int(dt != torch.uint8), _stream())
+    return (bsf, args) if record else bsf
+
+
+def bfp_scatter(levels, refine_level, ref, ref_ab=None, record=False):
+    """BFP step 3 (bfp.py:91-99): out_i = residual_i + level_i for every level, one launch; residual_i = nearest(ref) for the levels finer
+    than refine_level, adaptive_max_pool2d(ref) for the others.  ref (N, h, w, C): the refined map, materialised, or with ref_ab = (a, b)
+    the refine conv's raw output under its GroupNorm affine AND ReLU, applied on load.  -> outs [, args with record]."""
+    maps, abs_ = _bfp_split(levels)
+    r = int(refine_level)
+    N, h, w, C = maps[r].shape
+    assert tuple(_check(ref, ACT).shape) == (N, h, w, C) and ref.dtype == maps[0].dtype, (ref.shape, ref.dtype)
+    ra, rb = (None, None) if ref_ab is None else ref_ab
+    assert ra is None or tuple(_check(ra).shape) == tuple(_check(rb).shape) == (N, C)
+    dt = _bfp_arg_dtype([p for x in maps[r + 1:] for p in ((h, x.shape[1]), (w, x.shape[2]))]) if record else torch.uint8
+    args = [torch.empty(x.shape, device=x.device, dtype=dt) if record and i > r else None for i, x in enumerate(maps)]
+    outs = [torch.empty_like(x) for x in maps]
+    rows = [(x, a, b, y, g, x.shape[1], x.shape[2], nearest_scale(h, x.shape[1]), nearest_scale(w, x.shape[2]))
+            for x, (a, b), y, g in zip(maps, abs_, outs, args)]
+    _lib.call('cpr_bfp_scatter' + _sfx(ref), _bfp_table(rows), len(maps), r, _ptr(ref), _ptr(ra), _ptr(rb), N, C,
+              int(dt != torch.uint8), _stream())
+    return (outs, args) if record else outs
+
+
+def bfp_scatter_bwd(gs, refine_level, args):
+    """d(refined map) = the sum over the levels, ascending, of g_i through nearest / max-pool backward (gather form, no atomics).
+    gs: fp32 gradients of the scatter's outputs; args: its record."""
+    r = int(refine_level)
+    N, h, w, C = _check(gs[r]).shape
+    wide = [a.dtype != torch.uint8 for a in args if a is not None]
+    rows = [(_check(g), None, None, None, a, g.shape[1], g.shape[2], nearest_scale(h, g.shape[1]), nearest_scale(w, g.shape[2]))
+            for g, a in zip(gs, args)]
+    d_ref = torch.empty((N, h, w, C), device=gs[r].device, dtype=torch.float32)
+    _lib.call('cpr_bfp_scatter_bwd', _bfp_table(rows), len(gs), r, _ptr(d_ref), N, C, int(any(wide)), _stream())
+    return d_ref
+
+
+def bfp_gather_bwd(gs, refine_level, d_bsf, args):
+    """d_level_i = g_i + (d_bsf / L through max-pool / nearest backward) for every level, one launch.  gs: what reaches the levels
+    directly (the scatter's residual connection); args: the gather's record."""
+    r = int(refine_level)
+    N, h, w, C = _check(d_bsf).shape
+    assert tuple(gs[r].shape) == (N, h, w, C)
+    wide = [a.dtype != torch.uint8 for a in args if a is not None]
+    outs = [torch.empty_like(_check(g)) for g in gs]
+    rows = [(g, None, None, y, a, g.shape[1], g.shape[2], nearest_scale(g.shape[1], h), nearest_scale(g.shape[2], w))
+            for g, y, a in zip(gs, outs, args)]
+    _lib.call('cpr_bfp_gather_bwd', _bfp_table(rows), len(gs), r, _ptr(d_bsf), N, C, int(any(wide)), _stream())
+    return outs
+
+
 # ------------------------------------------------------------------------------------------------ CPR points
 def box_centers(boxes):
     n = boxes.shape[0]

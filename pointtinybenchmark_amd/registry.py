@@ -54,6 +54,11 @@ def build_backbone(cfg):
 
 
 def build_neck(cfg):
+    """A dict builds one neck; a list builds each entry and chains them (the reference's builder returns ``Sequential(*modules)`` for a
+    list, mmcv build_model_from_cfg): necks/bfp.py NeckSequence, which says which chains are built."""
+    if isinstance(cfg, (list, tuple)):
+        from .necks.bfp import NeckSequence
+        return NeckSequence(*[NECKS.build(c) for c in cfg])
     return NECKS.build(cfg)
 
 

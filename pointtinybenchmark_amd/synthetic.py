@@ -136,6 +136,19 @@ def pafpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=None
     return sd
 
 
+def bfp_state_dict(in_channels=256, refine_type='conv', seed=1, prefix='neck.1.'):
+    """BFP's parameters (bfp.py:53-60): the refine ConvModule -- ``refine.conv.weight`` (3x3, no bias under a norm layer), ``refine.gn.*`` --
+    for refine_type 'conv'; none for refine_type None.  prefix: 'neck.1.' is BFP's place in ``neck=[FPN | PAFPN, BFP]``."""
+    sd = {}
+    if refine_type == 'conv':
+        g = torch.Generator().manual_seed(seed + 104729)
+        sd[prefix + 'refine.conv.weight'] = _xavier_uniform((in_channels, in_channels, 3, 3), g)
+        _gn(sd, prefix + 'refine.gn', in_channels, g)
+    else:
+        assert refine_type is None, refine_type
+    return sd
+
+
 def cpr_head_state_dict(num_classes=1, in_channels=256, feat_channels=256, stacked_convs=4, seed=2,
                         prefix='bbox_head.', std=0.01, num_cls_fcs=0, fc_out_channels=1024, binary_ins=False,
                         ins_tower=False, out_bg_cls=False):

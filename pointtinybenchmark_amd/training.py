@@ -275,6 +275,19 @@ def _is_pafpn(neck):
     return len(getattr(neck, 'downsample_convs', ())) > 0
 
 
+def _inner_neck(neck):
+    """The FPN / PAFPN of a model's neck: the neck itself, or the first entry of a [FPN | PAFPN, BFP] list (necks/bfp.py NeckSequence)."""
+    return neck.inner if hasattr(neck, 'bfp') else neck
+
+
+def _bfp_of(neck):
+    """The BFP behind the FPN / PAFPN of a list-valued neck, else None."""
+    return getattr(neck, 'bfp', None)
+
+
+_BFP_UNDER_CPR = 'CPRHead takes one pyramid level without a BFP behind it: the BFP neck trains under P2PHead (neck=[FPN | PAFPN, BFP])'
+
+
 class BackwardEngine:
     """The backward rules of the recorded forward -- shared by ``CprTrainer`` (gradients written straight into the views of
     its flat buffer, bucketed reducer, native optimizer) and by the autograd bridge (``autograd_bridge.py``: the same rules
@@ -372,14 +385,14 @@ class BackwardEngine:
         """-> (the lateral sums the FPN output convs read: the finest one alone when num_outs == 1, else a tuple finest first,
         the backward state)."""
         tape = []
-        neck = self.model.neck
+        neck = _inner_neck(self.model.neck)
         lat = neck.run_laterals(list(xs), tape)
         n = min(len(lat), neck.num_outs)        # the regular output convs (fpn_convs may hold extra levels behind them)
         return (lat[0] if n == 1 else tuple(lat[:n])), {r['level']: r for r in tape}
 
     def backward_laterals(self, recs, dlat, need):
         """dlat: gradient wrt the lateral sum(s) forward_laterals returned.  need[i]: whether the gradient wrt the i-th input (stage start_level + i) is wanted -> list of gradients / None."""
-        neck = self.model.neck
+        neck = _inner_neck(self.model.neck)
         d_stage = self._backward_laterals(neck, recs, dlat, need_dx_of=lambda stage: need[stage - neck.start_level])
         return [d_stage.get(i + neck.start_level) for i in range(len(need))]
 
@@ -388,12 +401,21 @@ class BackwardEngine:
         backward state.  lat: what forward_laterals returned (one lateral sum, or one per regular FPN output level).
         extra_src: the last backbone stage's NHWC output, for a neck with add_extra_convs='on_input'."""
         from .layers import conv_gn
-        neck, head = self.model.neck, self.model.bbox_head
+        neck, head, bfp = _inner_neck(self.model.neck), self.model.bbox_head, _bfp_of(self.model.neck)
         lats = list(lat) if isinstance(lat, (tuple, list)) else [lat]
+        bfp_tape = []
+
+        def run_head(lazy):      # a BFP behind the neck: its gather / refine / scatter on the lazy levels, its records with the head's
+            if bfp is not None:
+                lazy = bfp.run(lazy, bfp_tape)
+            _, saved = self._forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
+            if bfp is not None:
+                saved['bfp_tape'] = bfp_tape
+            return saved
         if _is_pafpn(neck):      # the bottom-up path sits between the output convs and the head: the neck's own walk, one tape
             tape = []
             lazy = neck.run_outputs(lats, extra_src, True, tape)
-            _, saved = self._forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
+            saved = run_head(lazy)
             return saved[self.loss_vector_key], (dict(pafpn=tape), saved)
         recs = [dict(kind='out', level=i) for i in range(len(lats))]
         lazy = [conv_gn(neck._cache, neck.fpn_convs[i], t, materialize=False, save=rec) for i, (t, rec) in enumerate(zip(lats, recs))]
@@ -401,7 +423,7 @@ class BackwardEngine:
         if getattr(neck, 'extra_levels', 0):
             assert len(lats) == len(neck.lateral_convs) and (extra_src is not None) == (neck.add_extra_convs == 'on_input')
             lazy += neck.run_extras(lazy[-1], lats[-1], extra_src, True, extras)
-        _, saved = self._forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
+        saved = run_head(lazy)
         rec = recs if isinstance(lat, (tuple, list)) else recs[0]
         return saved[self.loss_vector_key], ((rec, saved, extras) if extras else (rec, saved))
 
@@ -410,12 +432,16 @@ class BackwardEngine:
         gradients, then the gradient wrt extra_src (None unless need_src)."""
         rec, saved = state[:2]
         dz = self._backward_head(self.model.bbox_head, saved, upstream=upstream)
+        if 'bfp_tape' in saved:
+            dz = self._backward_bfp(_bfp_of(self.model.neck), saved['bfp_tape'], dz)
+            if not (isinstance(rec, list) or len(state) == 3 or (isinstance(rec, dict) and 'pafpn' in rec)):
+                dz = dz[0]
         if isinstance(rec, dict) and 'pafpn' in rec:
-            neck = self.model.neck
+            neck = _inner_neck(self.model.neck)
             dlats, d_src = self._backward_pafpn(neck, rec['pafpn'], list(dz), need_src=need_src)
             return dlats + [d_src] if neck.add_extra_convs == 'on_input' and neck.extra_levels else dlats
         if len(state) == 3:
-            neck = self.model.neck
+            neck = _inner_neck(self.model.neck)
             dzs, d_lat, d_src = self._backward_extras(neck, state[2], list(dz), need_src=need_src)
             recs = rec if isinstance(rec, list) else [rec]
             dlats = [self._backward_out_conv(r, d) for r, d in zip(recs, dzs)]
@@ -745,10 +771,13 @@ class BackwardEngine:
     def _backward_neck(self, neck, neck_tape, dz):
         """Extra levels (last first), output convs, then the top-down chain from the finest lateral to the coarsest -> {stage: d(stage output)}.
         dz: gradient wrt the (normalised) FPN output -- one map (num_outs == 1), or a list with one per output level."""
+        dzs = list(dz) if isinstance(dz, (list, tuple)) else [dz]
+        if _bfp_of(neck) is not None:      # [FPN | PAFPN, BFP]: BFP's records are the tape's last; its backward comes first
+            dzs = self._backward_bfp(neck.bfp, [r for r in neck_tape if r['kind'].startswith('bfp_')], dzs)
+            neck, neck_tape = neck.inner, [r for r in neck_tape if not r['kind'].startswith('bfp_')]
         lat_recs = {r['level']: r for r in neck_tape if r['kind'] == 'lateral'}
         out_recs = {r['level']: r for r in neck_tape if r['kind'] == 'out'}
         extra_recs = [r for r in neck_tape if r['kind'] in ('extra', 'pool')]
-        dzs = list(dz) if isinstance(dz, (list, tuple)) else [dz]
         if _is_pafpn(neck):
             dlats, d_src = self._backward_pafpn(neck, [r for r in neck_tape if r['kind'] != 'lateral'], dzs)
             d_stage = self._backward_laterals(neck, lat_recs, dlats)
@@ -767,6 +796,20 @@ class BackwardEngine:
             stage = neck.backbone_end_level - 1
             d_stage[stage] = d_src if d_stage.get(stage) is None else ops.axpby(d_stage[stage], d_src, 1.0, 1.0)
         return d_stage
+
+    def _backward_bfp(self, bfp, recs, dzs):
+        """BFP in reverse (necks/bfp.py run; T/mmdet/models/necks/bfp.py:69-101): scatter backward -> the refine layer (conv + GN + ReLU)
+        -> gather backward, which also adds what reaches every level directly through the scatter's residual connection.
+        recs: the 'bfp_gather' / 'bfp_refine' / 'bfp_scatter' records.  dzs: one fp32 gradient per BFP output (a single map: one level).
+        -> the gradients wrt the materialised levels BFP read, one per level: the ``dzs`` of the neck in front of it."""
+        by = {r['kind']: r for r in recs}
+        gs = [g.contiguous() for g in (dzs if isinstance(dzs, (list, tuple)) else [dzs])]
+        assert len(gs) == bfp.num_levels and 'bfp_gather' in by and 'bfp_scatter' in by, (len(gs), bfp.num_levels, sorted(by))
+        d = ops.bfp_scatter_bwd(gs, bfp.refine_level, by['bfp_scatter']['args'])
+        if bfp.refine_type is not None:
+            d = self._gn_conv_backward(by['bfp_refine'], d, relu=True, need_dx=True)
+            self._done(bfp.refine.conv.weight)
+        return ops.bfp_gather_bwd(gs, bfp.refine_level, d, by['bfp_gather']['args'])
 
     def _backward_extras(self, neck, recs, dzs, need_src=None):
         """The extra pyramid levels, last first (T/mmdet/models/necks/fpn.py:195-217).  dzs: one gradient per output level, the extras'
@@ -1159,8 +1202,11 @@ class CprTrainer(BackwardEngine):
         optimizer: an mmcv-style dict (``type`` 'SGD', 'Adam' or 'AdamW' + torch.optim's keyword arguments, torch's
         defaults) in place of the positional SGD arguments ``lr`` / ``momentum`` / ``weight_decay``; None: SGD with those."""
         BackwardEngine.__init__(self, model, two_streams)
-        n_levels = min(len(model.neck.lateral_convs), model.neck.num_outs) + getattr(model.neck, 'extra_levels', 0)
-        if _is_pafpn(model.neck) and type(model.bbox_head).__name__ == 'CPRHead' and n_levels != 1:
+        if _bfp_of(model.neck) is not None and type(model.bbox_head).__name__ == 'CPRHead':
+            raise NotImplementedError(_BFP_UNDER_CPR)
+        inner = _inner_neck(model.neck)
+        n_levels = min(len(inner.lateral_convs), inner.num_outs) + getattr(inner, 'extra_levels', 0)
+        if _is_pafpn(inner) and type(model.bbox_head).__name__ == 'CPRHead' and n_levels != 1:
             raise NotImplementedError('CPRHead takes one pyramid level (cpr_head.py:487); this PAFPN has %d output levels' % n_levels)
         self.schedule = schedule
         if optimizer is None:
@@ -1373,7 +1419,7 @@ class CprTrainer(BackwardEngine):
     # ------------------------------------------------------------------ parameter order = gradient completion order
     def _backward_order(self):
         m = self.model
-        head, neck, bb = m.bbox_head, m.neck, m.backbone
+        head, neck, bb = m.bbox_head, _inner_neck(m.neck), m.backbone
         out = []
 
         def add(*ps):
@@ -1381,6 +1427,9 @@ class CprTrainer(BackwardEngine):
                 if p is not None and p.requires_grad and all(p is not q for q in out):
                     out.append(p)
         self._head_param_order(head, add)
+        bfp = _bfp_of(m.neck)
+        if bfp is not None and bfp.refine_type is not None:      # BFP's refine layer sits between the head and the neck (_backward_bfp)
+            add(bfp.refine.gn.weight, bfp.refine.gn.bias, bfp.refine.conv.weight)
         regular = min(len(neck.lateral_convs), neck.num_outs)
         for cm in reversed(list(neck.fpn_convs)[regular:]):      # the extra levels' convs, last first (_backward_extras)
             add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
@@ -1521,8 +1570,9 @@ class P2PHeadRules:
         concatenation (P2PHead.get_pred_points)."""
         assert len(lazy) == len(head.strides), 'one FPN output per head stride (%d outputs, strides %s)' % (len(lazy), head.strides)
         cls_outs, reg_outs, cls_tapes, reg_tapes, hws = [], [], [], [], []
-        for raw, (a, b) in lazy:
-            x = ops.gn_apply(raw, a, b, relu=False)               # FPN output, materialised once for the two towers
+        for lvl in lazy:
+            # FPN output, materialised once for the two towers (a BFP behind the neck has written it materialised)
+            x = lvl if torch.is_tensor(lvl) else ops.gn_apply(lvl[0], lvl[1][0], lvl[1][1], relu=False)
             cls_tape, reg_tape = [], []
             cls_outs.append(ops.as_nchw(head._tower(head.cls_convs, head.cls_out, x, tape=cls_tape)))
             reg_outs.append(ops.as_nchw(head._tower(head.reg_convs, head.reg_out, x, tape=reg_tape)))
