@@ -166,7 +166,8 @@ def get_bridge(model):
 # Thin: every Function calls one forward_* / backward_* pair of the engine (training.BackwardEngine).  An autograd OUTPUT must
 # not be reachable from its own ctx (ctx -> state -> output -> grad_fn -> ctx would be a reference cycle that keeps a batch of
 # maps alive until the garbage collector runs): the engine's state holds the output's storage under another tensor object
-# (``.detach()`` aliases), never the returned object itself.
+# (``.detach()`` aliases), never the returned object itself.  This is part of the segment contract, for every engine (also a caller's
+# own): the Functions do not look into a state, so ``forward_head_loss`` itself stores the loss vector's alias, not the vector.
 _CONSUMED = 'the recorded forward of this step was already consumed (a second backward / retain_graph is not supported)'
 
 
@@ -258,9 +259,6 @@ class _HeadLossFn(torch.autograd.Function):
         lat = bridge.real(lats[0]) if len(lats) == 1 else tuple(bridge.real(t) for t in lats)
         out, state = eng.forward_head_loss(lat, pack.img_metas, pack.gt_bboxes, pack.gt_labels,
                                            pack.gt_bboxes_ignore, pack.gt_true_bboxes, **kw)
-        saved = state[1] if isinstance(state, tuple) and len(state) in (2, 3) and isinstance(state[1], dict) else None
-        if saved is not None and saved.get(eng.loss_vector_key) is out:
-            saved[eng.loss_vector_key] = out.detach()
         ctx.bridge, ctx.state, ctx.params, ctx.n_lat = bridge, state, params, n_lat
         return out
 

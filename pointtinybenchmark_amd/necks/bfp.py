@@ -96,6 +96,11 @@ class NeckSequence(nn.Sequential):
     def bfp(self):
         return self[1]
 
+    # the backbone levels it reads and the number of its outputs are the inner neck's
+    start_level = property(lambda self: self.inner.start_level)
+    backbone_end_level = property(lambda self: self.inner.backbone_end_level)
+    num_outs = property(lambda self: self.inner.num_outs)
+
     def forward(self, inputs):
         return tuple(ops.as_nchw(t) for t in self.forward_lazy(inputs))
 
@@ -103,3 +108,12 @@ class NeckSequence(nn.Sequential):
         """-> the MATERIALISED NHWC levels (the scatter writes them): a consumer has no pending affine to apply.  tape: the inner
         neck's records followed by BFP's.  out_b8: accepted for the necks' common signature; the levels are plain NHWC."""
         return self.bfp.run(self.inner.forward_lazy(inputs, tape=tape), tape)
+
+    def run_laterals(self, xs, tape=None):
+        return self.inner.run_laterals(xs, tape)
+
+    def run_outputs(self, lat, src, lazy, tape=None, out_b8=False):
+        """The inner neck's lazy outputs behind its lateral sums (never materialised: BFP applies their affines on load), then BFP, on
+        one tape -> the materialised NHWC levels, as forward_lazy.  out_b8: accepted for the common signature, as there."""
+        assert lazy, 'BFP reads the inner neck\'s lazy outputs (forward and forward_lazy both do)'
+        return self.bfp.run(self.inner.run_outputs(lat, src, lazy, tape), tape)

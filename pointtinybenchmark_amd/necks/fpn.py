@@ -82,14 +82,12 @@ class FPN(nn.Module):
             lat[i] = conv_gn(c, self.lateral_convs[i], xs[i], up=up, save=rec)
         return lat
 
-    def _run(self, inputs, lazy, tape=None, out_b8=False):
-        assert len(inputs) == len(self.in_channels)
-        c = self._cache
-        xs = [ops.from_nchw(inputs[i + self.start_level]) for i in range(len(self.lateral_convs))]
-        lat = self.run_laterals(xs, tape)
-        used = min(len(lat), self.num_outs)
-        outs = []
-        for i in range(used):
+    def run_outputs(self, lat, src, lazy, tape=None, out_b8=False):
+        """The lateral sums ``lat`` (finest first; at least the ones the output convs read) and, for 'on_input' extra levels, the last
+        backbone map ``src`` -> every output level: lazy (raw, (a, b)) pairs, else materialised maps.  tape: training records -- kind
+        'out' (fpn_convs[level]), then the extra levels' own (run_extras)."""
+        c, outs = self._cache, []
+        for i in range(min(len(lat), self.num_outs)):
             rec = None
             if tape is not None:
                 rec = dict(kind='out', level=i)
@@ -97,9 +95,18 @@ class FPN(nn.Module):
             outs.append(conv_gn(c, self.fpn_convs[i], lat[i], materialize=not lazy, save=rec,
                                 out_b8=out_b8 and lazy and not self.extra_levels))
         if self.extra_levels:
-            src = None if self.add_extra_convs != 'on_input' else ops.from_nchw(inputs[self.backbone_end_level - 1])
+            assert len(lat) == len(self.lateral_convs) and (src is not None) == (self.add_extra_convs == 'on_input')
             outs += self.run_extras(outs[-1], lat[-1], src, lazy, tape)
         return outs
+
+    def _run(self, inputs, lazy, tape=None, out_b8=False):
+        assert len(inputs) == len(self.in_channels)
+        xs = [ops.from_nchw(inputs[i + self.start_level]) for i in range(len(self.lateral_convs))]
+        lat = self.run_laterals(xs, tape)
+        src = None
+        if self.extra_levels and self.add_extra_convs == 'on_input':
+            src = ops.from_nchw(inputs[self.backbone_end_level - 1])
+        return self.run_outputs(lat, src, lazy, tape, out_b8)
 
     def run_extras(self, last, lat_last, src, lazy, tape=None):
         """The extra pyramid levels (fpn.py:195-217) behind the last regular output ``last`` (lazy: (raw, (a, b)), else the
@@ -122,9 +129,10 @@ class FPN(nn.Module):
         cur = None      # the previous extra conv's (raw, (a, b))
         for k in range(self.extra_levels):
             relu = k > 0 and self.relu_before_extra_convs
-            if k == 0 and self.add_extra_convs == 'on_input':
+            reads = self.add_extra_convs if k == 0 else 'on_output'
+            if reads == 'on_input':
                 x = src
-            elif k == 0 and self.add_extra_convs == 'on_lateral':
+            elif reads == 'on_lateral':
                 x = lat_last
             elif k == 0 and not lazy:
                 x = last
@@ -133,7 +141,7 @@ class FPN(nn.Module):
                 x = ops.gn_apply(raw, a, b, relu=relu)
             rec = None
             if tape is not None:
-                rec = dict(kind='extra', level=used + k, index=k, relu_in=relu)
+                rec = dict(kind='extra', level=used + k, reads=reads, relu_in=relu)
                 tape.append(rec)
             cur = conv_gn(c, self.fpn_convs[used + k], x, materialize=False, save=rec)
             outs.append(cur if lazy else ops.gn_apply(cur[0], cur[1][0], cur[1][1]))

@@ -32,11 +32,13 @@ class PAFPN(FPN):
             self.pafpn_convs.append(ConvModule(out_channels, out_channels, 3, padding=1, norm_cfg=norm_cfg, act_cfg=None))
         self.init_weights()
 
-    def run_outputs(self, lat, src, lazy, tape=None):
+    def run_outputs(self, lat, src, lazy, tape=None, out_b8=False):
         """The lateral sums ``lat`` (finest first; FPN.run_laterals) and, for 'on_input' extra levels, the last backbone map ``src`` ->
         every output level: lazy (raw, (a, b)) pairs, else materialised maps.  tape: training records -- kind 'out' (fpn_convs[level]),
         'down' (downsample_convs[level]: inter[level] -> its share of inter[level + 1]), 'pa_out' (pafpn_convs[level - 1]), then the
         extra levels' own."""
+        if not len(self.downsample_convs):      # one used level: no bottom-up module, FPN itself
+            return super().run_outputs(lat, src, lazy, tape, out_b8)
         c, L = self._cache, len(lat)
         assert L == len(self.lateral_convs) and L > 1
 
@@ -58,14 +60,3 @@ class PAFPN(FPN):
         if self.extra_levels:
             outs += self.run_extras(outs[-1], lat[-1], src, lazy, tape)
         return outs
-
-    def _run(self, inputs, lazy, tape=None, out_b8=False):
-        if not len(self.downsample_convs):      # one used level: no bottom-up module, FPN itself
-            return super()._run(inputs, lazy, tape, out_b8)
-        assert len(inputs) == len(self.in_channels)
-        xs = [ops.from_nchw(inputs[i + self.start_level]) for i in range(len(self.lateral_convs))]
-        lat = self.run_laterals(xs, tape)
-        src = None
-        if self.extra_levels and self.add_extra_convs == 'on_input':
-            src = ops.from_nchw(inputs[self.backbone_end_level - 1])
-        return self.run_outputs(lat, src, lazy, tape)

@@ -285,6 +285,11 @@ def _bfp_of(neck):
     return getattr(neck, 'bfp', None)
 
 
+def _as_list(x):
+    """One map or a sequence of maps -> a list (the bridge's segments carry a single map bare; the engine works on lists)."""
+    return list(x) if isinstance(x, (list, tuple)) else [x]
+
+
 _BFP_UNDER_CPR = 'CPRHead takes one pyramid level without a BFP behind it: the BFP neck trains under P2PHead (neck=[FPN | PAFPN, BFP])'
 
 
@@ -385,74 +390,41 @@ class BackwardEngine:
         """-> (the lateral sums the FPN output convs read: the finest one alone when num_outs == 1, else a tuple finest first,
         the backward state)."""
         tape = []
-        neck = _inner_neck(self.model.neck)
+        neck = self.model.neck
         lat = neck.run_laterals(list(xs), tape)
         n = min(len(lat), neck.num_outs)        # the regular output convs (fpn_convs may hold extra levels behind them)
         return (lat[0] if n == 1 else tuple(lat[:n])), {r['level']: r for r in tape}
 
     def backward_laterals(self, recs, dlat, need):
         """dlat: gradient wrt the lateral sum(s) forward_laterals returned.  need[i]: whether the gradient wrt the i-th input (stage start_level + i) is wanted -> list of gradients / None."""
-        neck = _inner_neck(self.model.neck)
-        d_stage = self._backward_laterals(neck, recs, dlat, need_dx_of=lambda stage: need[stage - neck.start_level])
+        neck = self.model.neck
+        d_stage = self._backward_laterals(neck, recs, _as_list(dlat), need_dx_of=lambda stage: need[stage - neck.start_level])
         return [d_stage.get(i + neck.start_level) for i in range(len(need))]
 
     def forward_head_loss(self, lat, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_true_bboxes=None, extra_src=None):
-        """FPN output conv(s) (lazy) -> extra pyramid levels -> head -> losses: returns the loss vector of the loss kernels and the
-        backward state.  lat: what forward_laterals returned (one lateral sum, or one per regular FPN output level).
-        extra_src: the last backbone stage's NHWC output, for a neck with add_extra_convs='on_input'."""
-        from .layers import conv_gn
-        neck, head, bfp = _inner_neck(self.model.neck), self.model.bbox_head, _bfp_of(self.model.neck)
-        lats = list(lat) if isinstance(lat, (tuple, list)) else [lat]
-        bfp_tape = []
-
-        def run_head(lazy):      # a BFP behind the neck: its gather / refine / scatter on the lazy levels, its records with the head's
-            if bfp is not None:
-                lazy = bfp.run(lazy, bfp_tape)
-            _, saved = self._forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
-            if bfp is not None:
-                saved['bfp_tape'] = bfp_tape
-            return saved
-        if _is_pafpn(neck):      # the bottom-up path sits between the output convs and the head: the neck's own walk, one tape
-            tape = []
-            lazy = neck.run_outputs(lats, extra_src, True, tape)
-            saved = run_head(lazy)
-            return saved[self.loss_vector_key], (dict(pafpn=tape), saved)
-        recs = [dict(kind='out', level=i) for i in range(len(lats))]
-        lazy = [conv_gn(neck._cache, neck.fpn_convs[i], t, materialize=False, save=rec) for i, (t, rec) in enumerate(zip(lats, recs))]
-        extras = []
-        if getattr(neck, 'extra_levels', 0):
-            assert len(lats) == len(neck.lateral_convs) and (extra_src is not None) == (neck.add_extra_convs == 'on_input')
-            lazy += neck.run_extras(lazy[-1], lats[-1], extra_src, True, extras)
-        saved = run_head(lazy)
-        rec = recs if isinstance(lat, (tuple, list)) else recs[0]
-        return saved[self.loss_vector_key], ((rec, saved, extras) if extras else (rec, saved))
+        """Everything between the lateral sums and the losses -- the neck's ``run_outputs`` (lazy output convs, a PAFPN's bottom-up path,
+        extra pyramid levels, a BFP behind them), the head, the loss kernels: returns the loss vector and the backward state, always
+        ``(tape, saved)`` = (the neck's records behind the laterals, the head's).  lat: what forward_laterals returned (one lateral
+        sum, or one per regular FPN output level).  extra_src: the last backbone stage's NHWC output, for a neck with
+        add_extra_convs='on_input'."""
+        tape = []
+        lazy = self.model.neck.run_outputs(_as_list(lat), extra_src, True, tape)
+        _, saved = self._forward_head(self.model.bbox_head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
+        # the loss vector becomes an autograd output, which must not be reachable from the state its Function keeps (a reference cycle,
+        # autograd_bridge.py "Functions"): the state holds its storage under a detached alias
+        out = saved[self.loss_vector_key]
+        saved[self.loss_vector_key] = out.detach()
+        return out, (tape, saved)
 
     def backward_head_loss(self, state, upstream, need_src=True):
         """-> the gradient wrt the lateral sum(s) forward_head_loss read, in the same form; with an 'on_input' neck a list: those
         gradients, then the gradient wrt extra_src (None unless need_src)."""
-        rec, saved = state[:2]
+        tape, saved = state
         dz = self._backward_head(self.model.bbox_head, saved, upstream=upstream)
-        if 'bfp_tape' in saved:
-            dz = self._backward_bfp(_bfp_of(self.model.neck), saved['bfp_tape'], dz)
-            if not (isinstance(rec, list) or len(state) == 3 or (isinstance(rec, dict) and 'pafpn' in rec)):
-                dz = dz[0]
-        if isinstance(rec, dict) and 'pafpn' in rec:
-            neck = _inner_neck(self.model.neck)
-            dlats, d_src = self._backward_pafpn(neck, rec['pafpn'], list(dz), need_src=need_src)
-            return dlats + [d_src] if neck.add_extra_convs == 'on_input' and neck.extra_levels else dlats
-        if len(state) == 3:
-            neck = _inner_neck(self.model.neck)
-            dzs, d_lat, d_src = self._backward_extras(neck, state[2], list(dz), need_src=need_src)
-            recs = rec if isinstance(rec, list) else [rec]
-            dlats = [self._backward_out_conv(r, d) for r, d in zip(recs, dzs)]
-            if d_lat is not None:
-                dlats[-1] = ops.axpby(dlats[-1], d_lat, 1.0, 1.0)
-            if neck.add_extra_convs == 'on_input':
-                return dlats + [d_src]
-            return dlats if isinstance(rec, list) else dlats[0]
-        if isinstance(rec, list):
-            return [self._backward_out_conv(r, d) for r, d in zip(rec, dz)]
-        return self._backward_out_conv(rec, dz)
+        dlats, d_src = self._backward_outputs(self.model.neck, tape, _as_list(dz), need_src=need_src)
+        if any(r.get('reads') == 'on_input' for r in tape):
+            return dlats + [d_src]
+        return dlats[0] if len(dlats) == 1 else dlats
 
     loss_vector_key = 'out5'       # CPRHead: (gt_loss, pos_loss, bag_acc, neg_loss, num_sample)
 
@@ -769,41 +741,45 @@ class BackwardEngine:
 
     # ------------------------------------------------------------------ FPN, backbone
     def _backward_neck(self, neck, neck_tape, dz):
-        """Extra levels (last first), output convs, then the top-down chain from the finest lateral to the coarsest -> {stage: d(stage output)}.
-        dz: gradient wrt the (normalised) FPN output -- one map (num_outs == 1), or a list with one per output level."""
-        dzs = list(dz) if isinstance(dz, (list, tuple)) else [dz]
-        if _bfp_of(neck) is not None:      # [FPN | PAFPN, BFP]: BFP's records are the tape's last; its backward comes first
-            dzs = self._backward_bfp(neck.bfp, [r for r in neck_tape if r['kind'].startswith('bfp_')], dzs)
-            neck, neck_tape = neck.inner, [r for r in neck_tape if not r['kind'].startswith('bfp_')]
+        """Everything behind the lateral sums (_backward_outputs), then the top-down chain from the finest lateral to the coarsest
+        -> {stage: d(stage output)}.  dz: gradient wrt the (normalised) neck output -- one map (one level), or a list with one per level."""
         lat_recs = {r['level']: r for r in neck_tape if r['kind'] == 'lateral'}
-        out_recs = {r['level']: r for r in neck_tape if r['kind'] == 'out'}
-        extra_recs = [r for r in neck_tape if r['kind'] in ('extra', 'pool')]
-        if _is_pafpn(neck):
-            dlats, d_src = self._backward_pafpn(neck, [r for r in neck_tape if r['kind'] != 'lateral'], dzs)
-            d_stage = self._backward_laterals(neck, lat_recs, dlats)
-            if d_src is not None:
-                stage = neck.backbone_end_level - 1
-                d_stage[stage] = d_src if d_stage.get(stage) is None else ops.axpby(d_stage[stage], d_src, 1.0, 1.0)
-            return d_stage
-        assert sorted(out_recs) == list(range(len(dzs) - len(extra_recs))), 'one gradient per FPN output level (%d outputs, %d gradients)' \
-            % (len(out_recs) + len(extra_recs), len(dzs))
-        dzs, d_lat, d_src = self._backward_extras(neck, extra_recs, dzs)
-        dlats = [self._backward_out_conv(out_recs[i], d) for i, d in enumerate(dzs)]     # fpn_convs in the flat order
-        if d_lat is not None:
-            dlats[-1] = ops.axpby(dlats[-1], d_lat, 1.0, 1.0)
+        dlats, d_src = self._backward_outputs(neck, [r for r in neck_tape if r['kind'] != 'lateral'], _as_list(dz))
         d_stage = self._backward_laterals(neck, lat_recs, dlats)
         if d_src is not None:
             stage = neck.backbone_end_level - 1
             d_stage[stage] = d_src if d_stage.get(stage) is None else ops.axpby(d_stage[stage], d_src, 1.0, 1.0)
         return d_stage
 
+    def _backward_outputs(self, neck, recs, dzs, need_src=None):
+        """Everything between the lateral sums and the head, in reverse (the necks' ``run_outputs``): a BFP ([FPN | PAFPN, BFP]: its
+        records are the tape's last, its backward comes first), then a PAFPN's outputs, or FPN's extra levels (last first) and output convs.
+        recs: the tape without its 'lateral' records.  dzs: one gradient per output level.  -> (one gradient per lateral sum an output
+        conv read -- the last joined by an 'on_lateral' extra's --, the gradient an 'on_input' extra adds to the last backbone stage's
+        output | None)."""
+        bfp_recs = [r for r in recs if r['kind'].startswith('bfp_')]
+        if bfp_recs:
+            dzs = self._backward_bfp(neck.bfp, bfp_recs, dzs)
+            neck, recs = neck.inner, [r for r in recs if not r['kind'].startswith('bfp_')]
+        if any(r['kind'] == 'down' for r in recs):       # a bottom-up path was recorded
+            return self._backward_pafpn(neck, recs, dzs, need_src=need_src)
+        out_recs = {r['level']: r for r in recs if r['kind'] == 'out'}
+        extra_recs = [r for r in recs if r['kind'] in ('extra', 'pool')]
+        assert sorted(out_recs) == list(range(len(dzs) - len(extra_recs))), 'one gradient per FPN output level (%d outputs, %d gradients)' \
+            % (len(out_recs) + len(extra_recs), len(dzs))
+        dzs, d_lat, d_src = self._backward_extras(neck, extra_recs, dzs, need_src=need_src)
+        dlats = [self._backward_out_conv(out_recs[i], d) for i, d in enumerate(dzs)]     # fpn_convs in the flat order
+        if d_lat is not None:
+            dlats[-1] = ops.axpby(dlats[-1], d_lat, 1.0, 1.0)
+        return dlats, d_src
+
     def _backward_bfp(self, bfp, recs, dzs):
         """BFP in reverse (necks/bfp.py run; T/mmdet/models/necks/bfp.py:69-101): scatter backward -> the refine layer (conv + GN + ReLU)
         -> gather backward, which also adds what reaches every level directly through the scatter's residual connection.
-        recs: the 'bfp_gather' / 'bfp_refine' / 'bfp_scatter' records.  dzs: one fp32 gradient per BFP output (a single map: one level).
+        recs: the 'bfp_gather' / 'bfp_refine' / 'bfp_scatter' records.  dzs: one fp32 gradient per BFP output.
         -> the gradients wrt the materialised levels BFP read, one per level: the ``dzs`` of the neck in front of it."""
         by = {r['kind']: r for r in recs}
-        gs = [g.contiguous() for g in (dzs if isinstance(dzs, (list, tuple)) else [dzs])]
+        gs = [g.contiguous() for g in dzs]
         assert len(gs) == bfp.num_levels and 'bfp_gather' in by and 'bfp_scatter' in by, (len(gs), bfp.num_levels, sorted(by))
         d = ops.bfp_scatter_bwd(gs, bfp.refine_level, by['bfp_scatter']['args'])
         if bfp.refine_type is not None:
@@ -828,7 +804,7 @@ class BackwardEngine:
             if rec['kind'] == 'pool':
                 dzs[n + k - 1] = ops.subsample2_bwd_add(dzs[n + k - 1], d)
                 continue
-            src = neck.add_extra_convs if k == 0 else 'on_output'
+            src = rec['reads']
             need_dx = True
             if src == 'on_input':
                 need_dx = self._stage_trainable(neck.backbone_end_level - 1) if need_src is None else bool(need_src)
@@ -859,7 +835,7 @@ class BackwardEngine:
         assert sorted(by['out']) == list(range(L)) and sorted(by['down']) == list(range(L - 1)) and \
             sorted(by['pa_out']) == list(range(1, L)) and len(dzs) == L + len(extra_recs), \
             'one gradient per PAFPN output level (%d outputs, %d gradients)' % (L + len(extra_recs), len(dzs))
-        dzs, d_lat, d_src = self._backward_extras(neck, extra_recs, list(dzs), need_src=need_src)
+        dzs, d_lat, d_src = self._backward_extras(neck, extra_recs, dzs, need_src=need_src)
         dlats, above = [None] * L, None          # above: g_inter[i + 1]
         for i in range(L - 1, -1, -1):
             g = dzs[i]
@@ -881,14 +857,13 @@ class BackwardEngine:
         self._done(rec['module'].conv.weight)
         return dlat
 
-    def _backward_laterals(self, neck, lat_recs, dlat, need_dx_of=None):
+    def _backward_laterals(self, neck, lat_recs, douts, need_dx_of=None):
         """The top-down chain from the finest lateral to the coarsest -> {stage: d(stage output) or None}.
-        dlat: gradient wrt the finest lateral sum, or a list: wrt the lateral sums 0, 1, .. that FPN output convs read (each
-        added to what flows up from the finer level before that level's step).
+        douts: the gradients wrt the lateral sums 0, 1, .. that FPN output convs read (each added to what flows up from the finer
+        level before that level's step).
         need_dx_of(stage): whether the gradient wrt that backbone stage's output is wanted (default: the stage trains)."""
         d_stage = {}
         L = len(lat_recs)
-        douts = list(dlat) if isinstance(dlat, (list, tuple)) else [dlat]
         assert 1 <= len(douts) <= L, (len(douts), L)
         dlat = douts[0]
         for i in range(L):
