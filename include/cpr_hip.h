@@ -470,6 +470,40 @@ int cpr_conv_group_fwd(const float* x, const float* wp, float* out, const float*
 int cpr_conv_group_wgrad_workspace(int N, int OH, int OW, int C, int cg);
 int cpr_conv_group_wgrad(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int cg, int stride,
                          int accumulate, void* stream);
+/* ---- Res2Net slice kernels (Bottle2neck's 3x3 chain; csrc/res2net.hip), NHWC fp32, plain fp32 FMA ------------------------------
+ * A slice is the channels [off, off + width) of a map whose pixels are `pitch` floats apart.  width even, 2 .. 512; every offset and
+ * pitch even and every base pointer 8-byte aligned (the kernels move float2), off + width <= pitch: anything else is CPR_ERR_ARG before
+ * any launch, and so are a NULL map, a stride other than 1 / 2 and an `add` operand at stride 2.  More than 2^31 - 1 pixels or blocks:
+ * CPR_ERR_UNSUPPORTED.  Every kernel writes its own slice and nothing else.
+ * cpr_res2_pack_weights: the parameter (width, width, 3, 3) -> the kernel's image (9 * width * width floats): transpose 0 the forward
+ * pack, 1 the data-gradient pack (in / out channels swapped, taps flipped, scale[width] -- the forward conv's folded BatchNorm, or
+ * NULL -- multiplied in). */
+int cpr_res2_pack_weights(const float* w, const float* scale, float* out, int width, int transpose, void* stream);
+/* out slice (N,OH,OW) = relu?(conv3x3(x slice [+ add slice], wp) * scale[c] + bias[c]), padding 1; add (same resolution, stride 1 only),
+ * scale and bias may be NULL; x + add is rounded once to fp32 and a padding pixel contributes 0.  flags: CPR_CONV_RELU only.
+ * transposed 0: the conv, (IH, IW) -> (OH, OW) = ((IH - 1) / stride + 1, (IW - 1) / stride + 1).  transposed 1: the data gradient with the
+ * data-gradient pack: x is the gradient slice at (IH, IW) = ((OH - 1) / stride + 1, ...), out the layer's input size (OH, OW) -- a stride-2
+ * layer in gather form, so 17 x 23 and 18 x 23 inputs are told apart by (OH, OW).  9 * width FMAs per output, tap-major, input channel
+ * ascending: bit-repeatable, and an image of a batch equals its single-image run. */
+int cpr_res2_conv_fwd(const float* x, int x_pitch, int x_off, const float* add, int add_pitch, int add_off, const float* wp, float* out,
+                      int out_pitch, int out_off, const float* scale, const float* bias, int N, int IH, int IW, int OH, int OW, int width,
+                      int stride, int transposed, int flags, void* stream);
+/* grad_w (width, width, 3, 3) (+)= dy slice (N,OH,OW) against the x slice [+ add slice] (N,H,W).  The pixels are split over workgroups whose
+ * partials (ws: cpr_res2_conv_wgrad_workspace(...) floats) are added in ascending order by a second kernel -- no atomics. */
+int cpr_res2_conv_wgrad_workspace(int N, int OH, int OW, int width);
+int cpr_res2_conv_wgrad(const float* dy, int dy_pitch, int dy_off, const float* x, int x_pitch, int x_off, const float* add, int add_pitch,
+                        int add_off, float* grad_w, float* ws, int N, int H, int W, int width, int stride, int accumulate, void* stream);
+/* Backward of a slice's ReLU, in place: g slice = (g slice (+ carry slice)) * (y slice > 0) over M pixels, and colsum[width] = the
+ * per-channel sums of the result (chunk partials in ws, ceil(M / 256) * width floats, added in ascending order: no atomics).
+ * carry may be NULL. */
+int cpr_res2_relu_bwd_colsum(float* g, int g_pitch, int g_off, const float* carry, int c_pitch, int c_off, const float* y, int y_pitch,
+                             int y_off, float* colsum, float* ws, long long M, int width, void* stream);
+/* The last slice of a stage block: stride 2: AvgPool2d(3, 2, padding 1) with the divisor always 9 (count_include_pad), (H, W) ->
+ * ((H - 1) / 2 + 1, (W - 1) / 2 + 1); stride 1: the slice copied.  _bwd: dx slice (N,H,W) = its adjoint over the dy slice. */
+int cpr_res2_pool_fwd(const float* x, int x_pitch, int x_off, float* out, int out_pitch, int out_off, int N, int H, int W, int width,
+                      int stride, void* stream);
+int cpr_res2_pool_bwd(const float* dy, int dy_pitch, int dy_off, float* dx, int dx_pitch, int dx_off, int N, int H, int W, int width,
+                      int stride, void* stream);
 /* FPN extra pyramid levels (fpn.py:195-217; csrc/fpn_extra.hip), NHWC, 16 bytes of channels per lane.
  * cpr_subsample2: out (N,(H+1)/2,(W+1)/2,C) = y[:, ::2, ::2, :] with y = x, or x*a[n,c] + b[n,c] when a/b (N,C) are given (the producer's
  * pending GroupNorm affine, cpr_gn_apply's arithmetic) -- F.max_pool2d(y, 1, stride=2) bit for bit.  x/out fp32 (C%4==0) or bf16

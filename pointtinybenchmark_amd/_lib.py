@@ -125,6 +125,13 @@ SIGNATURES = {
     'cpr_conv_group_fwd': [_p] * 5 + [_i] * 7 + [_p],
     'cpr_conv_group_wgrad_workspace': [_i] * 5,
     'cpr_conv_group_wgrad': [_p] * 4 + [_i] * 7 + [_p],
+    'cpr_res2_pack_weights': [_p, _p, _p, _i, _i, _p],
+    'cpr_res2_conv_fwd': [_p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _p, _p] + [_i] * 9 + [_p],
+    'cpr_res2_conv_wgrad_workspace': [_i] * 4,
+    'cpr_res2_conv_wgrad': [_p, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p] + [_i] * 6 + [_p],
+    'cpr_res2_pool_fwd': [_p, _i, _i, _p, _i, _i] + [_i] * 5 + [_p],
+    'cpr_res2_relu_bwd_colsum': [_p, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _l, _i, _p],
+    'cpr_res2_pool_bwd': [_p, _i, _i, _p, _i, _i] + [_i] * 5 + [_p],
     'cpr_spin': [ctypes.c_longlong, _p],
     'cpr_bn_fold': [_p, _p, _p, _p, _f, _p, _p, _p, _i, _p],
     'cpr_bn_train_ws': [_l, _i],

@@ -1,1 +1,2 @@
 from .resnet import ResNet, ResNeXt  # noqa: F401
+from .res2net import Res2Net  # noqa: F401

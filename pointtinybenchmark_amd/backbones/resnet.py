@@ -268,7 +268,7 @@ class ResNet(nn.Module):
                                            nn.Conv2d(inplanes, planes * exp, 1, 1, bias=False), norm(planes * exp))
                     else:
                         ds = nn.Sequential(nn.Conv2d(inplanes, planes * exp, 1, stride, bias=False), norm(planes * exp))
-                layer.append(_Block(kind, inplanes, planes, stride, ds, norm, style, self.groups, self.base_width, base_channels))
+                layer.append(self._make_block(kind, inplanes, planes, stride, ds, norm, style, base_channels, first=bi == 0))
                 inplanes = planes * exp
             name = 'layer%d' % (i + 1)
             self.add_module(name, nn.Sequential(*layer))
@@ -279,6 +279,10 @@ class ResNet(nn.Module):
         self.zero_init_residual = zero_init_residual
         self.init_weights()
         self._freeze_stages()
+
+    def _make_block(self, kind, inplanes, planes, stride, downsample, norm, style, base_channels, first):
+        """One residual block of a stage (``first``: its first block); Res2Net builds its own kind."""
+        return _Block(kind, inplanes, planes, stride, downsample, norm, style, self.groups, self.base_width, base_channels)
 
     def _freeze_stages(self):  # resnet.py:612-628
         if self.frozen_stages >= 0:
@@ -340,7 +344,7 @@ class ResNet(nn.Module):
         if self.zero_init_residual:
             for name in self.res_layers:
                 for blk in getattr(self, name):
-                    nn.init.constant_((blk.bn3 if blk.kind == 'bottleneck' else blk.bn2).weight, 0)
+                    nn.init.constant_((blk.bn2 if blk.kind == 'basic' else blk.bn3).weight, 0)
         bump_weight_epoch()
 
     def stem_train_reason(self):

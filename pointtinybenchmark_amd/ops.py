@@ -2109,3 +2109,111 @@ def scale_clip_flip_boxes(boxes, img_of, flips, img_hw, scale4, clip=True):
     _lib.call('cpr_scale_clip_flip_boxes', _ptr(boxes), _ptr(img_of), _ptr(flips), _ptr(img_hw), _ptr(scale4), n, int(bool(clip)),
               _stream())
     return boxes
+
+
+# ---- Res2Net slice kernels (csrc/res2net.hip): the Bottle2neck 3x3 chain on channel slices of the block's two internal maps.
+# A slice is the channels [off, off + width) of a contiguous NHWC fp32 map; the C entry points check widths, offsets, pitches and strides
+# (include/cpr_hip.h) and raise CprHipError('... invalid argument') before any launch.
+RES2_MAX_WIDTH = 512       # widths the slice kernels take: even, 2 .. 512
+RES2_MAX_SCALES = 8
+
+
+def res2_width_ok(width):
+    return 2 <= width <= RES2_MAX_WIDTH and width % 2 == 0
+
+
+class Res2Pack:
+    """A (width, width, 3, 3) parameter in the slice conv's own image (cpr_res2_pack_weights): 9 * width * width floats
+    [tap][width / 2][2][width / 2][2].  transpose: the data-gradient pack -- in / out channels swapped, taps flipped, ``scale`` (the forward
+    conv's folded BatchNorm) multiplied in."""
+
+    def __init__(self, weight, scale=None, transpose=False):
+        O, I, KH, KW = weight.shape
+        assert weight.is_cuda, 'the slice-conv pack is built on the device'
+        assert O == I and (KH, KW) == (3, 3), 'slice conv: a (width, width, 3, 3) weight, got %s' % (tuple(weight.shape),)
+        src = weight.detach()
+        if src.dtype != torch.float32 or not src.is_contiguous():
+            src = src.float().contiguous()
+        self.width, self.transpose = O, bool(transpose)
+        self.w = torch.empty((9 * O * O,), device=weight.device, dtype=torch.float32)
+        _lib.call('cpr_res2_pack_weights', _ptr(src), _ptr(scale), _ptr(self.w), O, int(self.transpose), _stream())
+        self.ready = record_ready()
+
+
+def _res2_map(t):
+    N, H, W, pitch = _check(t).shape
+    return N, H, W, pitch
+
+
+def res2_conv(x, x_off, pack, out, out_off, stride=1, add=None, add_off=0, scale=None, bias=None, relu=False, transposed=False):
+    """out[..., out_off : out_off + width] = relu?(conv3x3(x[..., x_off : x_off + width] (+ add[..., add_off : ...]), pack) * scale + bias),
+    padding 1, stride 1 or 2; nothing else of ``out`` is written.  transposed: the data gradient of such a layer -- ``x`` is the gradient
+    map, ``pack`` the data-gradient Res2Pack, and ``out`` has the layer's input size (a stride-2 layer in gather form)."""
+    pack_ready(pack)
+    N, IH, IW, xp = _res2_map(x)
+    No, OH, OW, op = _res2_map(out)
+    assert No == N, (x.shape, out.shape)
+    ap = 0
+    if add is not None:
+        assert tuple(add.shape[:3]) == (N, IH, IW), (x.shape, add.shape)
+        ap = _res2_map(add)[3]
+    _lib.call('cpr_res2_conv_fwd', _ptr(x), xp, x_off, _ptr(add), ap, add_off, _ptr(pack.w), _ptr(out), op, out_off, _ptr(scale),
+              _ptr(bias), N, IH, IW, OH, OW, pack.width, stride, int(bool(transposed)), CONV_RELU if relu else 0, _stream())
+    if TRACE_CONV_VARIANT[0]:
+        TRACE_CONV_VARIANT[1] = ('res2', pack.width)
+    return out
+
+
+def res2_wgrad(dy, dy_off, x, x_off, width, stride=1, add=None, add_off=0, grad=None, out=None):
+    """grad_w (width, width, 3, 3) of the slice conv: the dy slice against the x slice (+ add slice).  Accumulated into ``grad`` when
+    given, written into ``out`` when given, else a new tensor.  The split over pixels is added up in a fixed order."""
+    N, H, W, xp = _res2_map(x)
+    Nd, OH, OW, dp = _res2_map(dy)
+    assert Nd == N and (OH, OW) == ((H - 1) // max(stride, 1) + 1, (W - 1) // max(stride, 1) + 1), (dy.shape, x.shape, stride)
+    ap = 0
+    if add is not None:
+        assert tuple(add.shape[:3]) == (N, H, W), (x.shape, add.shape)
+        ap = _res2_map(add)[3]
+    n = _lib.call('cpr_res2_conv_wgrad_workspace', N, OH, OW, width, positive=True)
+    ws = torch.empty((n,), device=x.device, dtype=torch.float32)
+    acc = grad is not None
+    if grad is None:
+        grad = out if out is not None else torch.empty((width, width, 3, 3), device=x.device, dtype=torch.float32)
+    assert tuple(grad.shape) == (width, width, 3, 3) and grad.is_contiguous() and grad.dtype == torch.float32
+    _lib.call('cpr_res2_conv_wgrad', _ptr(dy), dp, dy_off, _ptr(x), xp, x_off, _ptr(add), ap, add_off, _ptr(grad), _ptr(ws), N, H, W,
+              width, stride, int(acc), _stream())
+    return grad
+
+
+def res2_pool(x, x_off, out, out_off, width, stride):
+    """The last slice of a Bottle2neck: stride 2 -- AvgPool2d(3, 2, padding 1), divisor always 9 -- or stride 1 -- the copy -- of
+    x[..., x_off : x_off + width] into out[..., out_off : out_off + width]."""
+    N, H, W, xp = _res2_map(x)
+    No, OH, OW, op = _res2_map(out)
+    assert No == N and (OH, OW) == ((H - 1) // max(stride, 1) + 1, (W - 1) // max(stride, 1) + 1), (x.shape, out.shape, stride)
+    _lib.call('cpr_res2_pool_fwd', _ptr(x), xp, x_off, _ptr(out), op, out_off, N, H, W, width, stride, _stream())
+    return out
+
+
+def res2_pool_bwd(dy, dy_off, dx, dx_off, width, stride):
+    """Its adjoint: dx[..., dx_off : dx_off + width] (the layer's input size) from dy[..., dy_off : dy_off + width]."""
+    N, H, W, xp = _res2_map(dx)
+    Nd, OH, OW, dp = _res2_map(dy)
+    assert Nd == N and (OH, OW) == ((H - 1) // max(stride, 1) + 1, (W - 1) // max(stride, 1) + 1), (dy.shape, dx.shape, stride)
+    _lib.call('cpr_res2_pool_bwd', _ptr(dy), dp, dy_off, _ptr(dx), xp, dx_off, N, H, W, width, stride, _stream())
+    return dx
+
+
+def res2_relu_bwd(g, g_off, y, y_off, width, carry=None, carry_off=0):
+    """In place g[..., g_off : g_off + width] = (that slice (+ carry[..., carry_off : ...])) * (y[..., y_off : ...] > 0): the backward of a
+    slice conv's ReLU with the gradient of the next conv's summed operand joining; returns the (width,) column sums of the result."""
+    N, H, W, gp = _res2_map(g)
+    assert tuple(y.shape[:3]) == (N, H, W) and (carry is None or tuple(carry.shape[:3]) == (N, H, W)), (g.shape, y.shape)
+    yp = _res2_map(y)[3]
+    cp = _res2_map(carry)[3] if carry is not None else 0
+    M = N * H * W
+    cs = torch.empty((width,), device=g.device, dtype=torch.float32)
+    ws = torch.empty(((M + 255) // 256 * max(width, 0),), device=g.device, dtype=torch.float32)
+    _lib.call('cpr_res2_relu_bwd_colsum', _ptr(g), gp, g_off, _ptr(carry), cp, carry_off, _ptr(y), yp, y_off, _ptr(cs), _ptr(ws), M, width,
+              _stream())
+    return cs

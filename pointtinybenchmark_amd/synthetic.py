@@ -96,6 +96,38 @@ def resnet_state_dict(depth=50, seed=0, prefix='backbone.', deep_stem=False, avg
     return sd
 
 
+def res2net_state_dict(depth=50, scales=4, base_width=26, seed=0, prefix='backbone.'):
+    """The keys and shapes of mmdet's Res2Net (res2net.py), in its state-dict order: the deep stem, then per block conv1, bn1, conv3,
+    bn3, downsample.1 / .2 (behind the parameter-free pool at index 0), convs.i, bns.i with slices of floor(planes * base_width / 64)
+    channels.  Its own generator: no other call's random stream moves."""
+    g = torch.Generator().manual_seed(seed)
+    _, blocks = ARCH[depth]
+    assert depth in (50, 101, 152), depth
+    sd = {}
+    for i, (co, ci) in zip((0, 3, 6), ((32, 3), (32, 32), (64, 32))):
+        sd['%sstem.%d.weight' % (prefix, i)] = _kaiming((co, ci, 3, 3), g)
+        _bn(sd, '%sstem.%d' % (prefix, i + 1), co, g)
+    inplanes = 64
+    for li, nb in enumerate(blocks):
+        planes = 64 * 2 ** li
+        width = int(math.floor(planes * (base_width / 64)))
+        for bi in range(nb):
+            p = '%slayer%d.%d.' % (prefix, li + 1, bi)
+            sd[p + 'conv1.weight'] = _kaiming((width * scales, inplanes, 1, 1), g)
+            _bn(sd, p + 'bn1', width * scales, g)
+            sd[p + 'conv3.weight'] = _kaiming((planes * 4, width * scales, 1, 1), g)
+            _bn(sd, p + 'bn3', planes * 4, g)
+            if bi == 0:
+                sd[p + 'downsample.1.weight'] = _kaiming((planes * 4, inplanes, 1, 1), g)
+                _bn(sd, p + 'downsample.2', planes * 4, g)
+            for i in range(scales - 1):
+                sd['%sconvs.%d.weight' % (p, i)] = _kaiming((width, width, 3, 3), g)
+            for i in range(scales - 1):
+                _bn(sd, '%sbns.%d' % (p, i), width, g)
+            inplanes = planes * 4
+    return sd
+
+
 def fpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=1, seed=1, prefix='neck.', add_extra_convs=False,
                    extra_convs_on_inputs=True):
     """add_extra_convs (False / True / 'on_input' / 'on_lateral' / 'on_output', as FPN takes it): the stride-2 convs of the

@@ -307,6 +307,10 @@ class BackwardEngine:
         if getattr(bb, 'compute_dtype', torch.float32) != torch.float32 and getattr(bb, 'groups', 1) > 1:
             raise NotImplementedError('a grouped backbone (ResNeXt groups=%d) trains in the fp32 compute mode only: the bf16 compute mode '
                                       'has no grouped convolution' % bb.groups)
+        if getattr(bb, 'scales', 0):      # a Res2Net backbone (backbones/res2net.py)
+            if getattr(bb, 'compute_dtype', torch.float32) != torch.float32:
+                raise NotImplementedError('a Res2Net backbone (scales=%d) trains in the fp32 compute mode only: the bf16 compute mode has '
+                                          'no slice convolution' % bb.scales)
         dev = next(model.parameters()).device
         self._mixed, self._wide = False, {}     # set per step (bf16 compute mode = mixed precision)
         self._sink = None                       # None: p.grad (CprTrainer); dict: id(p) -> fresh tensor (autograd bridge)
@@ -1060,6 +1064,8 @@ class BackwardEngine:
         # recorded map up front -- 5.6 % of the step's kernel time in torch copy kernels)
         if rec.get('batch_stats'):
             return self._block_backward_batch_stats(cache, blk, rec, dout, need_dx)
+        if blk.kind == 'bottle2neck':
+            return self._bottle2neck_backward(cache, blk, rec, dout, need_dx)
         mixed = self._mixed
         x = rec['x']
         if isinstance(dout, tuple):
@@ -1101,6 +1107,98 @@ class BackwardEngine:
             tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
         else:
             dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3, g16=g1h)
+            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
+        self._done(tail)
+        return dx
+
+    # ------------------------------------------------------------------ Res2Net (backbones/res2net.py; fp32, eval-mode BatchNorm)
+    def _r2_pointwise_backward(self, cache, conv, bn, g, colsum, x, need_dx, add=None):
+        """A 1x1 conv -> folded eval-BN of a Bottle2neck whose output (conv1) or input (conv3) map sits at the padded pitch: g =
+        d(pre-activation output) and x are maps as the kernels wrote them (pad channels exact zeros), ``colsum`` the column sums of g's
+        real channels.  The weight gradient is taken at the padded shape into a scratch tensor and its real rows / columns copied to the
+        parameter's gradient -- pad channels reach no parameter and no statistic; the data gradient runs through a pack with zero
+        rows / columns (and a zero folded scale) in the pad."""
+        w = conv.weight
+        O, I = w.shape[:2]
+        Op, Ip = g.shape[-1], x.shape[-1]
+        padded = (Op, Ip) != (O, I)
+        scale, _ = folded_bn(cache, bn)
+        inv_sigma = bn_inv_sigma(cache, bn)
+        if w.requires_grad:
+            aff = bn.weight.requires_grad
+
+            def param_grads():
+                gw = self._g(w)
+                if padded:
+                    gw.copy_(ops.conv2d_wgrad(g, x, (Op, Ip, 1, 1), 1, 0)[:O, :I])
+                else:
+                    ops.conv2d_wgrad(g, x, w.shape, 1, 0, out=gw)
+                ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, colsum,
+                                out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
+            self._param_side(param_grads, g, colsum, x)
+        if not need_dx:
+            return None
+        if padded:
+            def make():
+                wp = torch.zeros((Op, Ip, 1, 1), device=w.device, dtype=torch.float32)
+                wp[:O, :I].copy_(w.detach())
+                sp = scale.new_zeros((Op,))
+                sp[:O].copy_(scale)
+                return ops.dgrad_pack(wp, 1, 0, scale=sp)
+            pt = cache.get(('r2_dgrad', id(conv), Op, Ip), [w, bn.weight, bn.running_var], make)      # (lapses with the weight epoch)
+        else:
+            pt = dgrad_packed(cache, conv, bn)
+        return ops.conv2d_dgrad(g, pt, (x.shape[1], x.shape[2]), 1, add=add)
+
+    def _bottle2neck_backward(self, cache, blk, rec, dout, need_dx):
+        """The Bottle2neck rule.  G = d(concatenated map) out of conv3's data gradient; walking i = scales-2 .. 0: g_i = (G[slice i] +
+        carry) * (y[i] > 0) in place with its column sums (ops.res2_relu_bwd; carry = the data gradient of conv i+1, which read y[i] in
+        a 'normal' block), weight gradient and bn_fold_bwd of convs[i] / bns[i] on the side stream, data gradient into d(conv1
+        output)[slice i]; the last slice's gradient passes through (or through the pool's backward); then conv1's rule."""
+        x, o1, cat = rec['x'], rec['o1'], rec['cat']
+        if isinstance(dout, tuple):
+            g3, cs3 = dout[0], dout[1]
+        else:
+            g3, cs3 = ops.relu_bwd_colsum(dout, rec['out'])          # also the shortcut gradient
+        s, w, stride = blk.scales, blk.width, blk.stride
+        Wd, Cp = s * w, o1.shape[-1]
+        normal = blk.stage_type == 'normal'
+        G = self._r2_pointwise_backward(cache, blk.conv3, blk.bn3, g3, cs3, cat, True)
+        d1 = (torch.zeros if Cp != Wd else torch.empty)(tuple(o1.shape), device=o1.device, dtype=torch.float32)
+        for i in range(s - 2, -1, -1):
+            conv, bn = blk.convs[i], blk.bns[i]
+            carry = normal and i < s - 2
+            cs = ops.res2_relu_bwd(G, i * w, cat, i * w, w, carry=d1 if carry else None, carry_off=(i + 1) * w)
+            scale, _ = folded_bn(cache, bn)
+            summed = normal and i > 0                 # the forward conv read o1[slice i] + y[i - 1]
+            if conv.weight.requires_grad:
+                aff = bn.weight.requires_grad
+
+                def param_grads(i=i, conv=conv, bn=bn, cs=cs, scale=scale, summed=summed, aff=aff):
+                    gw = self._g(conv.weight)
+                    ops.res2_wgrad(G, i * w, o1, i * w, w, stride, add=cat if summed else None, add_off=(i - 1) * w if summed else 0, out=gw)
+                    ops.bn_fold_bwd(gw, conv.weight, scale, bn.running_mean, bn_inv_sigma(cache, bn), cs,
+                                    out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
+                self._param_side(param_grads, G, o1, cat, cs)
+            pt = cache.get(('r2_packT', id(conv)), [conv.weight, bn.weight, bn.running_var],
+                           lambda conv=conv, scale=scale: ops.Res2Pack(conv.weight, scale=scale, transpose=True))
+            ops.res2_conv(G, i * w, pt, d1, i * w, stride=stride, transposed=True)
+        ops.res2_pool_bwd(G, (s - 1) * w, d1, (s - 1) * w, w, stride)
+        g1, cs1 = ops.relu_bwd_colsum(d1, o1)                        # conv1's ReLU; the pad channels stay 0
+        cs1 = cs1[:Wd]
+        del G, d1
+        if blk.downsample is not None:
+            dx = self._r2_pointwise_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx)
+            pool = blk.ds_pool
+            if pool:
+                dxp = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, rec['xp'], need_dx)
+                if need_dx:
+                    dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
+            else:
+                dx = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx)
+            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
+        else:
+            dx = self._r2_pointwise_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3)
             tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
         self._done(tail)
         return dx
@@ -1419,6 +1517,14 @@ class CprTrainer(BackwardEngine):
             add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
         for name in reversed(bb.res_layers):
             for blk in reversed(list(getattr(bb, name))):
+                if blk.kind == 'bottle2neck':       # (Res2Net, _bottle2neck_backward: conv3, the slice convs last first, conv1)
+                    add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
+                    for conv, bn in reversed(list(zip(blk.convs, blk.bns))):
+                        add(conv.weight, bn.weight, bn.bias)
+                    add(blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
+                    if blk.downsample is not None:
+                        add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
+                    continue
                 if blk.kind == 'bottleneck':
                     add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
                 add(blk.conv2.weight, blk.bn2.weight, blk.bn2.bias, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)

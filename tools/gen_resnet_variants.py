@@ -30,23 +30,24 @@ ADMIT_OUT, ADMIT_GRAD = RV.BAR_OUT / 4, RV.BAR_GRAD / 4
 PERTURB_TRIALS = 8
 
 
-def build_reference(R, cfg, dtype):
-    kw = RV.resnet_kwargs(cfg)
+def build_reference(R, cfg, dtype, kwargs=None, state_dict=None):
+    """kwargs / state_dict: the case table's own constructor-argument and weight functions (default: this tool's table)."""
+    kw = (kwargs or RV.resnet_kwargs)(cfg)
     if kw['deep_stem'] and kw['avg_down']:
         kw.pop('deep_stem'), kw.pop('avg_down')
         cls = sys.modules[R.ResNet.__module__].ResNetV1d
     else:
         cls = R.ResNet
     m = cls(**kw).to(dtype)
-    m.load_state_dict(RV.case_state_dict(cfg, dtype), strict=True)
+    m.load_state_dict((state_dict or RV.case_state_dict)(cfg, dtype), strict=True)
     m.train()          # norm_eval=True: every BatchNorm stays in eval mode, the frozen stages keep requires_grad=False
     assert not any(mod.training for mod in m.modules() if isinstance(mod, torch.nn.BatchNorm2d))
     return m
 
 
-def run_reference(R, cfg, dtype, noise_seed=None):
+def run_reference(R, cfg, dtype, noise_seed=None, kwargs=None, state_dict=None):
     """noise_seed: admission rule (b) -- every conv output + normal noise of one fp32 ulp (2^-23) of the map's rms."""
-    m = build_reference(R, cfg, dtype)
+    m = build_reference(R, cfg, dtype, kwargs, state_dict)
     if noise_seed is not None:
         g = torch.Generator().manual_seed(noise_seed)
 
@@ -64,9 +65,9 @@ def run_reference(R, cfg, dtype, noise_seed=None):
     return m, [o.detach() for o in outs], grads
 
 
-def reference_case(R, name, cfg):
-    m, outs, grads = run_reference(R, cfg, torch.float64)
-    _, outs32, grads32 = run_reference(R, cfg, torch.float32)
+def reference_case(R, name, cfg, kwargs=None, state_dict=None):
+    m, outs, grads = run_reference(R, cfg, torch.float64, None, kwargs, state_dict)
+    _, outs32, grads32 = run_reference(R, cfg, torch.float32, None, kwargs, state_dict)
     out = {'keys:' + name: np.array(json.dumps([[k, list(v.shape)] for k, v in m.state_dict().items()]))}
     err_out = []
     for l, (o, o32) in enumerate(zip(outs, outs32)):
@@ -97,7 +98,7 @@ def reference_case(R, name, cfg):
     out[name + ':fp32:grad'] = err_grad
     err_pert = np.zeros(len(names))
     for t in range(PERTURB_TRIALS):
-        _, _, gp = run_reference(R, cfg, torch.float64, noise_seed=1000 + t)
+        _, _, gp = run_reference(R, cfg, torch.float64, 1000 + t, kwargs, state_dict)
         err_pert = np.maximum(err_pert, [rel_l2(gp[n].flatten(), grads[n].detach().flatten()) for n in names])
     out[name + ':perturbed:grad'] = err_pert
     print('%-12s stages %s  %d trainable tensors  fp32-vs-fp64: outputs %.2e (admit %.1e)  gradients %.2e (admit %.1e)  min grad norm '
