@@ -173,6 +173,15 @@ int cpr_maxpool3x3s2(const float* in, float* out, int N, int H, int W, int C, vo
 int cpr_stem_deep_fwd(const float* in, const float* w1, const float* s1, const float* b1, const float* w2, const float* s2,
                       const float* b2, const float* w3, const float* s3, const float* b3, float* mid1, float* mid2, void* out, int N,
                       int H, int W, int layout, int out_bf16, void* stream);
+/* The RegNet stem (regnet.py:237-249): conv 3x3 / 2 / pad 1, 3 -> 32, + folded BatchNorm + ReLU, no max-pool -- the first launch of
+ * cpr_stem_deep_fwd alone (same layouts, same pack w (32, 64)) -> out (N, OH, OW, 32) fp32.
+ * cpr_stem3x3s2_wgrad (csrc/stem3x3_bwd.hip): gw (32, 3, 3, 3) = its weight gradient given dy (N, OH, OW, 32) and the image as the
+ * forward read it; the pixels are split into slices whose partials (ws: cpr_stem3x3s2_wgrad_workspace(N, H, W) floats) are added in
+ * ascending order by a second kernel -- no atomics. */
+int cpr_stem3x3s2_fwd(const float* in, const float* w, const float* scale, const float* bias, float* out, int N, int H, int W,
+                      int layout, void* stream);
+int cpr_stem3x3s2_wgrad_workspace(int N, int H, int W);
+int cpr_stem3x3s2_wgrad(const float* dy, const float* in, float* gw, float* ws, int N, int H, int W, int layout, void* stream);
 /* nn.AvgPool2d(s, s, ceil_mode=True, count_include_pad=False) on NHWC maps (the avg_down shortcut, res_layer.py:39-60): in (N,H,W,C) ->
  * out (N,ceil(H/s),ceil(W/s),C); a last window of an odd map divides by its in-map elements.  bf16 = 0: fp32 maps (C % 4 == 0),
  * 1: bf16 maps (C % 8 == 0); fp32 accumulation in a fixed order; s >= 2. */
@@ -451,7 +460,8 @@ int cpr_phase_scatter_add(const float* src, float* dst, int N, int Hs, int Ws, i
  * stride-1 conv over the dilated gradient) */
 int cpr_zero_insert(const float* dy, float* out, int N, int OH, int OW, int C, int H, int W, int s, void* stream);
 /* ---- grouped 3x3 convolution (ResNeXt conv2; csrc/conv_group.hip), NHWC fp32, plain fp32 FMA -------------------------------
- * C input and output channels in C / cg groups, cg in {4, 8, 16, 32}, padding 1, stride 1 or 2; the parameter is (C, cg, 3, 3).
+ * C input and output channels in C / cg groups, cg in {4, 8, 16, 24, 32, 40, 48, 56}, padding 1, stride 1 or 2; the parameter is
+ * (C, cg, 3, 3).
  * An output channel is multiplied against the cg input channels of its own group and nothing else (9 * cg FMAs per output, tap-major,
  * input channel ascending): bit-repeatable, and an image of a batch equals its single-image run.
  * cpr_pack_weights_grouped: the parameter -> the kernel's image (9 * cg * C floats): transpose 0 the forward pack, 1 the data-gradient
@@ -470,6 +480,14 @@ int cpr_conv_group_fwd(const float* x, const float* wp, float* out, const float*
 int cpr_conv_group_wgrad_workspace(int N, int OH, int OW, int C, int cg);
 int cpr_conv_group_wgrad(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int cg, int stride,
                          int accumulate, void* stream);
+/* The same two over maps whose pixels are Cp floats apart (RegNet: widths that are no multiple of 32 live at Cp = roundup(C, 32);
+ * Cp >= C, Cp % 4 == 0).  The pad channels [C, Cp) of x / dy are never read (NaN there changes no output bit); the forward writes the pad
+ * channels of out as +0.0 itself.  Pack, workspace and grad_w are those of C and cg.  Cp == C with cg in {4, 8, 16, 32} launches what
+ * cpr_conv_group_fwd / _wgrad launch. */
+int cpr_conv_group_fwd_pitch(const float* x, const float* wp, float* out, const float* scale, const float* bias, int N, int H, int W,
+                             int C, int Cp, int cg, int stride, int flags, void* stream);
+int cpr_conv_group_wgrad_pitch(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int Cp, int cg,
+                               int stride, int accumulate, void* stream);
 /* ---- Res2Net slice kernels (Bottle2neck's 3x3 chain; csrc/res2net.hip), NHWC fp32, plain fp32 FMA ------------------------------
  * A slice is the channels [off, off + width) of a map whose pixels are `pitch` floats apart.  width even, 2 .. 512; every offset and
  * pitch even and every base pointer 8-byte aligned (the kernels move float2), off + width <= pitch: anything else is CPR_ERR_ARG before

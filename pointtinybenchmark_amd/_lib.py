@@ -47,6 +47,9 @@ SIGNATURES = {
     'cpr_stem7x7s2_pool_f32': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     'cpr_maxpool3x3s2': [_p, _p, _i, _i, _i, _i, _p],
     'cpr_stem_deep_fwd': [_p] * 13 + [_i] * 5 + [_p],
+    'cpr_stem3x3s2_fwd': [_p] * 5 + [_i] * 4 + [_p],
+    'cpr_stem3x3s2_wgrad_workspace': [_i, _i, _i],
+    'cpr_stem3x3s2_wgrad': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     'cpr_avgpool_fwd': [_p, _p] + [_i] * 6 + [_p],
     'cpr_avgpool_bwd': [_p, _p, _p] + [_i] * 6 + [_p],
     'cpr_maxpool3x3s2_rec': [_p, _p, _p, _i, _i, _i, _i, _p],
@@ -125,6 +128,8 @@ SIGNATURES = {
     'cpr_conv_group_fwd': [_p] * 5 + [_i] * 7 + [_p],
     'cpr_conv_group_wgrad_workspace': [_i] * 5,
     'cpr_conv_group_wgrad': [_p] * 4 + [_i] * 7 + [_p],
+    'cpr_conv_group_fwd_pitch': [_p] * 5 + [_i] * 8 + [_p],
+    'cpr_conv_group_wgrad_pitch': [_p] * 4 + [_i] * 8 + [_p],
     'cpr_res2_pack_weights': [_p, _p, _p, _i, _i, _p],
     'cpr_res2_conv_fwd': [_p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _p, _p] + [_i] * 9 + [_p],
     'cpr_res2_conv_wgrad_workspace': [_i] * 4,

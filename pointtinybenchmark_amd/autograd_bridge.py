@@ -117,6 +117,8 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     if getattr(bb, 'scales', 0):          # a Res2Net backbone (backbones/res2net.py)
         if bb.compute_dtype != torch.float32:
             return 'a Res2Net backbone (scales=%d) runs in the fp32 compute mode only, not with the bf16 compute mode' % bb.scales
+    if getattr(bb, 'fp32_only', None) and bb.compute_dtype != torch.float32:      # a RegNet backbone (backbones/regnet.py)
+        return bb.fp32_only
     if bb.compute_dtype != torch.float32 and bb.batch_stats_active():
         return 'BatchNorm batch statistics (ResNet norm_eval=False) run in the fp32 compute mode only, not with the bf16 compute mode'
     if bb.compute_dtype != torch.float32 and type(head).__name__ not in ('CPRHead', 'P2PHead'):

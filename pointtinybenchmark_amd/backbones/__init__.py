@@ -1,2 +1,3 @@
 from .resnet import ResNet, ResNeXt  # noqa: F401
 from .res2net import Res2Net  # noqa: F401
+from .regnet import RegNet  # noqa: F401

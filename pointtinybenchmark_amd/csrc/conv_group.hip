@@ -2,8 +2,8 @@
 // gradient (the same kernel over dy with the data-gradient pack) and weight gradient.
 //
 // Plain fp32 FMA, the exact work and nothing else: an output channel is multiplied against the cg input channels of its own group, 9 * cg
-// FMAs per output (cg in {4, 8, 16, 32}: never more than 32 input channels per tap, and never another group's -- group isolation holds
-// by construction, not by zero weights).  A block-diagonal 32-wide MFMA tile would execute 32 / cg times the multiplies (8x at the
+// FMAs per output (cg in {4, 8, 16, 24, 32, 40, 48, 56}: never another group's input channels -- group isolation holds by construction,
+// not by zero weights).  A block-diagonal 32-wide MFMA tile would execute 32 / cg times the multiplies (8x at the
 // 32x4d layer1 width).  Measured (profiles/resnext_bench.json): 0.6 .. 0.9 ms per layer of a 64 x 640^2 x50_32x4d forward,
 // 17 .. 25 TFLOP/s executed -- bound by the vector pipe behind its loads, not by HBM.
 //
@@ -18,6 +18,12 @@
 // Weight gradient: thread <-> (4 output channels) x (4 input channels of their group) x 9 taps = 144 accumulators, over a slice of
 // the flattened output pixels; slice partials go to the workspace in the thread's own (coalesced) order and a second kernel adds the
 // slices up in ascending order (no atomics) and scatters to the parameter layout (C, cg, 3, 3).
+//
+// Channel pitch (RegNet: stage widths such as 72, 168, 432 that are no multiple of 32): the PITCH instances read and write maps whose
+// pixels are Cp >= C floats apart (Cp = roundup(C, 32) in the product).  The pad channels [C, Cp) of an input are never read -- the
+// threads of the pad quads take no part in the sums, so NaN there changes no output bit -- and the pad channels of the output are
+// written as +0.0 by the kernel itself.  The pack, the workspace and the parameter gradient know nothing of the pitch.  Cp == C with
+// one of the widths 4 / 8 / 16 / 32 launches the instances without the pitch argument, as before.
 #include "common.h"
 
 namespace {
@@ -69,17 +75,25 @@ __global__ void pack_group_multi_kernel(const GroupPackJob* __restrict__ jobs, i
     pack_group_body(j.w, j.scale, j.out, j.C, j.cg, j.transpose, (int)blockIdx.x - j.block0, j.nblocks);
 }
 
-template <int CG>
+template <int CG, bool PITCH>
 __global__ __launch_bounds__(256) void conv_group_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wp,
                                                              float* __restrict__ out, const float* __restrict__ scale,
                                                              const float* __restrict__ bias, long long M, int H, int W, int OH, int OW,
-                                                             int C, int stride, int relu) {
+                                                             int C, int pitch, int stride, int relu) {
     constexpr int CH = CG / 4, UNR = CH > 2 ? 2 : CH;
-    const int C4 = C >> 2;
+    const int C4 = C >> 2;                            // quads of the pack: the real channels
+    const int Cp = PITCH ? pitch : C;                 // floats between the pixels of x and of out
+    const int Q = Cp >> 2;
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int quad = (int)(gid % C4);
-    const long long p0 = gid / C4 * GC_PX;
+    const int quad = (int)(gid % Q);
+    const long long p0 = gid / Q * GC_PX;
     if (p0 >= M) return;
+    if (PITCH && quad >= C4) {                        // a pad quad: exact zeros out, nothing read
+#pragma unroll
+        for (int i = 0; i < GC_PX; ++i)
+            if (p0 + i < M) *reinterpret_cast<f32x4*>(out + (size_t)(p0 + i) * Cp + quad * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
     const int g0 = quad * 4 / CG * CG;                // first input channel of this thread's group
     const float* xb[GC_PX];
     int ih0[GC_PX], iw0[GC_PX];
@@ -95,7 +109,7 @@ __global__ __launch_bounds__(256) void conv_group_fwd_kernel(const float* __rest
         const long long n = t / OH;
         ih0[i] = oh * stride - 1;
         iw0[i] = ow * stride - 1;
-        xb[i] = x + (size_t)n * H * W * C + g0;
+        xb[i] = x + (size_t)n * H * W * Cp + g0;
     }
     f32x4 acc[GC_PX];
 #pragma unroll
@@ -110,7 +124,7 @@ __global__ __launch_bounds__(256) void conv_group_fwd_kernel(const float* __rest
         for (int i = 0; i < GC_PX; ++i) {
             const int ih = ih0[i] + kh, iw = iw0[i] + kw;
             ok[i] = live[i] && ih >= 0 && ih < H && iw >= 0 && iw < W;
-            src[i] = xb[i] + ((size_t)(ok[i] ? ih : 0) * W + (ok[i] ? iw : 0)) * C;
+            src[i] = xb[i] + ((size_t)(ok[i] ? ih : 0) * W + (ok[i] ? iw : 0)) * Cp;
         }
 #pragma unroll UNR
         for (int ch = 0; ch < CH; ++ch) {
@@ -140,7 +154,7 @@ __global__ __launch_bounds__(256) void conv_group_fwd_kernel(const float* __rest
         if (scale) { v.x *= s.x; v.y *= s.y; v.z *= s.z; v.w *= s.w; }
         if (bias) { v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
         if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        *reinterpret_cast<f32x4*>(out + (size_t)(p0 + i) * C + c) = v;
+        *reinterpret_cast<f32x4*>(out + (size_t)(p0 + i) * Cp + c) = v;
     }
 }
 
@@ -158,10 +172,12 @@ static inline WgPlan wg_plan(long long M, int C, int cg) {
     return pl;
 }
 
+template <bool PITCH>
 __global__ __launch_bounds__(256, 2) void conv_group_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                float* __restrict__ ws, long long M, int H, int W, int OH, int OW, int C,
-                                                               int cg, int stride, int T, int S, long long P) {
+                                                               int pitch, int cg, int stride, int T, int S, long long P) {
     const int C4 = C >> 2;
+    const int Cp = PITCH ? pitch : C;                 // floats between the pixels of dy and of x; the threads cover real channels only
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     const int t = (int)(gid % T);
     const int s = (int)(gid / T);
@@ -181,14 +197,14 @@ __global__ __launch_bounds__(256, 2) void conv_group_wgrad_kernel(const float* _
     int oh = (int)(r % OH);
     long long n = r / OH;
     for (long long p = pbeg; p < pend; ++p) {
-        const f32x4 d = ldg4(dy + (size_t)p * C + co0);
-        const float* xn = x + (size_t)n * H * W * C + ci0;
+        const f32x4 d = ldg4(dy + (size_t)p * Cp + co0);
+        const float* xn = x + (size_t)n * H * W * Cp + ci0;
         const int ihb = oh * stride - 1, iwb = ow * stride - 1;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int ih = ihb + tap / 3, iw = iwb + tap % 3;
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (ih >= 0 && ih < H && iw >= 0 && iw < W) v = ldg4(xn + ((size_t)ih * W + iw) * C);
+            if (ih >= 0 && ih < H && iw >= 0 && iw < W) v = ldg4(xn + ((size_t)ih * W + iw) * Cp);
             f32x4* a = acc[tap];
             a[0].x = fmaf(d.x, v.x, a[0].x); a[0].y = fmaf(d.x, v.y, a[0].y); a[0].z = fmaf(d.x, v.z, a[0].z); a[0].w = fmaf(d.x, v.w, a[0].w);
             a[1].x = fmaf(d.y, v.x, a[1].x); a[1].y = fmaf(d.y, v.y, a[1].y); a[1].z = fmaf(d.y, v.z, a[1].z); a[1].w = fmaf(d.y, v.w, a[1].w);
@@ -227,7 +243,45 @@ __global__ void conv_group_wgrad_reduce_kernel(const float* __restrict__ ws, flo
 }
 
 inline bool group_shape_ok(int C, int cg) {
-    return (cg == 4 || cg == 8 || cg == 16 || cg == 32) && C > 0 && C % cg == 0 && C / 4 <= (1 << 20);
+    return (cg == 4 || (cg >= 8 && cg <= 56 && cg % 8 == 0)) && C > 0 && C % cg == 0 && C / 4 <= (1 << 20);
+}
+inline bool group_pitch_ok(int C, int Cp) { return Cp >= C && Cp % 4 == 0 && Cp / 4 <= (1 << 20); }
+inline bool group_plain(int C, int Cp, int cg) { return Cp == C && (cg == 4 || cg == 8 || cg == 16 || cg == 32); }
+
+int group_fwd(const float* x, const float* wp, float* out, const float* scale, const float* bias, int N, int H, int W, int C, int Cp,
+              int cg, int stride, int flags, hipStream_t stream) {
+    CPR_CHECK_ARG(x && wp && out && N > 0 && H > 0 && W > 0 && group_shape_ok(C, cg) && group_pitch_ok(C, Cp) &&
+                  (stride == 1 || stride == 2));
+    CPR_CHECK_ARG((flags & ~CPR_CONV_RELU) == 0);      // no residual, no GroupNorm statistics, no bf16 output: ReLU is the only flag
+    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+    const long long M = (long long)N * OH * OW;
+    const long long blocks = cdivll(cdivll(M, GC_PX) * (Cp / 4), 256);
+    if (blocks > 0x7fffffffll) return CPR_ERR_UNSUPPORTED;
+    const int relu = flags & CPR_CONV_RELU;
+#define GC_LAUNCH(CG, PITCH)                                                                                                       \
+    hipLaunchKernelGGL((conv_group_fwd_kernel<CG, PITCH>), dim3((unsigned)blocks), dim3(256), 0, stream, x, wp, out, scale, bias, M, H, \
+                       W, OH, OW, C, Cp, stride, relu)
+    if (group_plain(C, Cp, cg)) {
+        switch (cg) {
+            case 4: GC_LAUNCH(4, false); break;
+            case 8: GC_LAUNCH(8, false); break;
+            case 16: GC_LAUNCH(16, false); break;
+            default: GC_LAUNCH(32, false); break;
+        }
+    } else {
+        switch (cg) {
+            case 4: GC_LAUNCH(4, true); break;
+            case 8: GC_LAUNCH(8, true); break;
+            case 16: GC_LAUNCH(16, true); break;
+            case 24: GC_LAUNCH(24, true); break;
+            case 32: GC_LAUNCH(32, true); break;
+            case 40: GC_LAUNCH(40, true); break;
+            case 48: GC_LAUNCH(48, true); break;
+            default: GC_LAUNCH(56, true); break;
+        }
+    }
+#undef GC_LAUNCH
+    CPR_LAUNCH_STATUS();
 }
 
 }  // namespace
@@ -249,24 +303,12 @@ extern "C" int cpr_pack_weights_grouped_multi(const void* jobs_dev, int n, int t
 
 extern "C" int cpr_conv_group_fwd(const float* x, const float* wp, float* out, const float* scale, const float* bias, int N, int H,
                                   int W, int C, int cg, int stride, int flags, hipStream_t stream) {
-    CPR_CHECK_ARG(x && wp && out && N > 0 && H > 0 && W > 0 && group_shape_ok(C, cg) && (stride == 1 || stride == 2));
-    CPR_CHECK_ARG((flags & ~CPR_CONV_RELU) == 0);      // no residual, no GroupNorm statistics, no bf16 output: ReLU is the only flag
-    const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
-    const long long M = (long long)N * OH * OW;
-    const long long blocks = cdivll(cdivll(M, GC_PX) * (C / 4), 256);
-    if (blocks > 0x7fffffffll) return CPR_ERR_UNSUPPORTED;
-    const int relu = flags & CPR_CONV_RELU;
-#define GC_LAUNCH(CG)                                                                                                                 \
-    hipLaunchKernelGGL(conv_group_fwd_kernel<CG>, dim3((unsigned)blocks), dim3(256), 0, stream, x, wp, out, scale, bias, M, H, W, OH, \
-                       OW, C, stride, relu)
-    switch (cg) {
-        case 4: GC_LAUNCH(4); break;
-        case 8: GC_LAUNCH(8); break;
-        case 16: GC_LAUNCH(16); break;
-        default: GC_LAUNCH(32); break;
-    }
-#undef GC_LAUNCH
-    CPR_LAUNCH_STATUS();
+    return group_fwd(x, wp, out, scale, bias, N, H, W, C, C, cg, stride, flags, stream);
+}
+// the same over maps whose pixels are Cp floats apart (Cp >= C, Cp % 4 == 0): pad channels never read, written as +0.0
+extern "C" int cpr_conv_group_fwd_pitch(const float* x, const float* wp, float* out, const float* scale, const float* bias, int N, int H,
+                                        int W, int C, int Cp, int cg, int stride, int flags, hipStream_t stream) {
+    return group_fwd(x, wp, out, scale, bias, N, H, W, C, Cp, cg, stride, flags, stream);
 }
 
 extern "C" int cpr_conv_group_wgrad_workspace(int N, int OH, int OW, int C, int cg) {
@@ -276,17 +318,32 @@ extern "C" int cpr_conv_group_wgrad_workspace(int N, int OH, int OW, int C, int 
     return n < (1ll << 31) ? (int)n : CPR_ERR_UNSUPPORTED;
 }
 
-extern "C" int cpr_conv_group_wgrad(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int cg,
-                                    int stride, int accumulate, hipStream_t stream) {
-    CPR_CHECK_ARG(dy && x && grad_w && ws && N > 0 && H > 0 && W > 0 && group_shape_ok(C, cg) && (stride == 1 || stride == 2));
+static int group_wgrad(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int Cp, int cg, int stride,
+                       int accumulate, hipStream_t stream) {
+    CPR_CHECK_ARG(dy && x && grad_w && ws && N > 0 && H > 0 && W > 0 && group_shape_ok(C, cg) && group_pitch_ok(C, Cp) &&
+                  (stride == 1 || stride == 2));
     const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
     const long long M = (long long)N * OH * OW;
     const WgPlan pl = wg_plan(M, C, cg);
     if ((long long)pl.S * pl.T * 144 >= (1ll << 31)) return CPR_ERR_UNSUPPORTED;
     const long long threads = (long long)pl.S * pl.T;
-    hipLaunchKernelGGL(conv_group_wgrad_kernel, dim3((unsigned)cdivll(threads, 256)), dim3(256), 0, stream, dy, x, ws, M, H, W, OH, OW,
-                       C, cg, stride, pl.T, pl.S, pl.P);
+    if (Cp == C)
+        hipLaunchKernelGGL(conv_group_wgrad_kernel<false>, dim3((unsigned)cdivll(threads, 256)), dim3(256), 0, stream, dy, x, ws, M, H, W,
+                           OH, OW, C, Cp, cg, stride, pl.T, pl.S, pl.P);
+    else
+        hipLaunchKernelGGL(conv_group_wgrad_kernel<true>, dim3((unsigned)cdivll(threads, 256)), dim3(256), 0, stream, dy, x, ws, M, H, W,
+                           OH, OW, C, Cp, cg, stride, pl.T, pl.S, pl.P);
     hipLaunchKernelGGL(conv_group_wgrad_reduce_kernel, dim3(cdiv(144 * pl.T, 256)), dim3(256), 0, stream, ws, grad_w, C, cg, pl.T, pl.S,
                        accumulate);
     CPR_LAUNCH_STATUS();
+}
+
+extern "C" int cpr_conv_group_wgrad(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int cg,
+                                    int stride, int accumulate, hipStream_t stream) {
+    return group_wgrad(dy, x, grad_w, ws, N, H, W, C, C, cg, stride, accumulate, stream);
+}
+// the same with dy and x at pitch Cp; workspace and grad_w as for cpr_conv_group_wgrad (they depend on C and cg alone)
+extern "C" int cpr_conv_group_wgrad_pitch(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int Cp,
+                                          int cg, int stride, int accumulate, hipStream_t stream) {
+    return group_wgrad(dy, x, grad_w, ws, N, H, W, C, Cp, cg, stride, accumulate, stream);
 }

@@ -323,6 +323,22 @@ extern "C" int cpr_stem_deep_fwd(const float* in, const float* w1, const float* 
     return stem_deep_bc_launch<64, true>(q, stream);
 }
 
+// Launch A alone: the RegNet stem (T/mmdet/models/backbones/regnet.py:237-249: conv 3x3 / 2 / pad 1, 3 -> 32, + BatchNorm + ReLU, no
+// max-pool).  in: layout 0 (N, H, W, 4) / 1 (N, 3, H, W) planes; w (32, 64): the fp32 implicit-GEMM pack; out (N, OH, OW, 32) fp32.
+extern "C" int cpr_stem3x3s2_fwd(const float* in, const float* w, const float* scale, const float* bias, float* out, int N, int H, int W,
+                                 int layout, hipStream_t stream) {
+    CPR_CHECK_ARG(in && w && scale && bias && out && N > 0 && H > 0 && W > 0 && (layout == 0 || layout == 1));
+    StemDeepAParams a;
+    a.in = in; a.wgt = w; a.scale = scale; a.bias = bias; a.out = out;
+    a.N = N; a.H = H; a.W = W; a.OH = (H - 1) / 2 + 1; a.OW = (W - 1) / 2 + 1; a.layout = layout; a.wstride = 64;
+    a.tilesY = cdiv(a.OH, SDA_TR);
+    a.tilesX = cdiv(a.OW, SDA_TC);
+    const long long blocks = (long long)N * a.tilesY * a.tilesX;
+    if (blocks >= (1ll << 31)) return CPR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(stem_deep_a_kernel, dim3((unsigned)blocks), dim3(512), 0, stream, a);
+    CPR_LAUNCH_STATUS();
+}
+
 // ------------------------------------------------------------------------------------------------- average pool (avg_down shortcut)
 // nn.AvgPool2d(s, s, ceil_mode=True, count_include_pad=False) on NHWC maps: OH = ceil(H / s); a last window of an odd map holds fewer
 // rows / columns and divides by the number of in-map elements.  16 bytes per lane (4 fp32 / 8 bf16 channels), fp32 accumulation row

@@ -41,6 +41,8 @@ class BasicLocator(nn.Module):
         if dt != torch.float32 and scales:
             raise NotImplementedError('a Res2Net backbone (scales=%d) runs in the fp32 compute mode only: the bf16 compute mode has no '
                                       'slice convolution' % scales)
+        if dt != torch.float32 and getattr(self.backbone, 'fp32_only', None):      # a RegNet backbone (backbones/regnet.py)
+            raise NotImplementedError(self.backbone.fp32_only)
         self.backbone.compute_dtype = dt
         return self
 

@@ -99,7 +99,7 @@ class GroupPackJob(PackJob):
 
     def row(self, ptrs, block0):
         pc, nb = self.value, self.nblocks
-        return self._ROWG.pack(*ptrs, pc.Cout, pc.cg, self.transpose, block0, nb, 0), block0 + nb
+        return self._ROWG.pack(*ptrs, pc.C, pc.cg, self.transpose, block0, nb, 0), block0 + nb
 
 
 def _pack_job(pc, weight, transpose=0, fold=None):
@@ -199,6 +199,20 @@ def packed_conv(cache, conv, dtype=torch.float32):
                      lambda pc: _pack_job(pc, conv.weight))
 
 
+def packed_conv_padded_in(cache, conv, Ip):
+    """The fp32 pack of ``conv`` for an input map kept at the channel pitch Ip = roundup(in_channels, 32) with exact-zero pad channels (a
+    RegNet stage output read in place, ops.as_nchw_padded): zero columns [in_channels, Ip).  (No refresh job: the entry lapses with the
+    weight epoch and rebuilds from the refreshed parameter.)"""
+    O, I = conv.weight.shape[:2]
+    assert Ip == ops.pad32(I) and Ip != I, (Ip, I)
+
+    def pack():
+        w = torch.zeros((O, Ip) + tuple(conv.weight.shape[2:]), device=conv.weight.device, dtype=torch.float32)
+        w[:, :I].copy_(conv.weight.detach())
+        return ops.PackedConv(w, conv.stride[0], conv.padding[0])
+    return cache.get(('pc_padin', id(conv), Ip), [conv.weight], pack)
+
+
 def folded_bn(cache, bn):
     """Eval-mode BatchNorm as a per-channel affine for the conv epilogue:
     scale = gamma / sqrt(var + eps), shift = beta - mean * scale."""
@@ -222,10 +236,22 @@ def bn_inv_sigma(cache, bn):
                      lambda: ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, True)[2])
 
 
-def dgrad_packed(cache, conv, bn=None, dtype=torch.float32):
+def dgrad_packed(cache, conv, bn=None, dtype=torch.float32, pitch=None):
     """The packed weights of the data gradient of ``conv`` (ops.dgrad_pack; bf16 stride 1: PackedConv.for_dgrad_bf16) with the
-    folded scale of the eval-mode ``bn`` multiplied in -- or the raw weights (bn None: a batch-statistics layer)."""
+    folded scale of the eval-mode ``bn`` multiplied in -- or the raw weights (bn None: a batch-statistics layer).  pitch (a grouped
+    layer with eval-mode ``bn``): the channel pitch of its gradient maps."""
     w, stride, pad = conv.weight, conv.stride[0], conv.padding[0]
+    if pitch is not None and pitch != w.shape[0]:
+        assert bn is not None and conv.groups > 1 and dtype == torch.float32
+
+        def make_p():
+            scale, _ = folded_bn(cache, bn)
+            return ops.dgrad_pack(w, stride, pad, scale=scale, groups=conv.groups, pitch=pitch)
+
+        def job_p(pc):
+            fold = cache._jobs.get(('bn', id(bn)))
+            return None if fold is None else _pack_job(pc, w, 1, fold)
+        return cache.get(('dgrad', id(conv), dtype, pitch), [w, bn.weight, bn.running_var], make_p, job_p)
     if bn is None:
         return cache.get(('dgrad_raw', id(conv)), [w], lambda: ops.dgrad_pack(w, stride, pad, groups=conv.groups),
                          lambda pc: _pack_job(pc, w, 1))
@@ -297,9 +323,13 @@ def conv_gn(cache, m, x, in_ab=None, in_relu=False, materialize=True, up=None, s
     160x160, B=16: 3.52 ms fused vs 3.30 ms plain) while gn_apply touches it once at HBM speed (0.14 ms): those take the
     materialised input in forward-only mode, 1x1 consumers fuse.
     """
-    pc = packed_conv(cache, m.conv, x.dtype)
     gn = m.norm
     blocked = ops.is_b8(x)
+    if not blocked and x.shape[-1] != m.conv.in_channels:      # a backbone map at its padded pitch (the caller vouches for the zeros)
+        assert x.dtype == torch.float32 and in_ab is None
+        pc = packed_conv_padded_in(cache, m.conv, x.shape[-1])
+    else:
+        pc = packed_conv(cache, m.conv, x.dtype)
     if blocked:
         N, _, H, W, _ = x.shape
     else:

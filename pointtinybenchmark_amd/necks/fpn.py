@@ -101,11 +101,12 @@ class FPN(nn.Module):
 
     def _run(self, inputs, lazy, tape=None, out_b8=False):
         assert len(inputs) == len(self.in_channels)
-        xs = [ops.from_nchw(inputs[i + self.start_level]) for i in range(len(self.lateral_convs))]
+        # (ops.neck_input: a backbone map kept at a padded channel pitch -- RegNet -- is read in place by a pack with zero columns)
+        xs = [ops.neck_input(inputs[i + self.start_level]) for i in range(len(self.lateral_convs))]
         lat = self.run_laterals(xs, tape)
         src = None
         if self.extra_levels and self.add_extra_convs == 'on_input':
-            src = ops.from_nchw(inputs[self.backbone_end_level - 1])
+            src = ops.neck_input(inputs[self.backbone_end_level - 1])
         return self.run_outputs(lat, src, lazy, tape, out_b8)
 
     def run_extras(self, last, lat_last, src, lazy, tape=None):

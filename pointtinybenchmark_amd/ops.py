@@ -39,12 +39,58 @@ def as_nchw(x_nhwc):
     return x_nhwc.permute(0, 3, 1, 2)
 
 
+def pad32(c):
+    return (c + 31) // 32 * 32
+
+
+def as_nchw_padded(buf, C):
+    """A map kept at a channel pitch -- buf (N,H,W,Cp), Cp = pad32(C), channels [C, Cp) exact zeros as its producer wrote them -> the
+    NCHW-shaped view (N,C,H,W) of its real channels (no copy).  The producer vouches for the pad: the view carries the buffer, and
+    ``padded_buffer`` hands it to a consumer that reads the pitch in place (a 1x1 pack with zero columns in the pad)."""
+    if buf.shape[-1] == C:
+        return as_nchw(buf)
+    view = buf[..., :C].permute(0, 3, 1, 2)
+    view._cpr_padded = buf
+    return view
+
+
+def padded_buffer(x):
+    """The (N,H,W,Cp) buffer behind a view made by as_nchw_padded, or None.  Only that very view qualifies: a tensor derived from it (a
+    slice, a copy, a user's own view of a wider tensor) carries no voucher and takes the copying route (from_nchw)."""
+    buf = getattr(x, '_cpr_padded', None)
+    if buf is None:
+        return None
+    N, C, H, W = x.shape
+    ok = buf.dim() == 4 and tuple(buf.shape[:3]) == (N, H, W) and buf.shape[3] == pad32(C) and buf.is_contiguous() and \
+        x.data_ptr() == buf.data_ptr() and x.stride() == (H * W * buf.shape[3], 1, W * buf.shape[3], buf.shape[3])
+    return buf if ok else None
+
+
 def from_nchw(x):
     """NCHW-shaped tensor -> contiguous (N,H,W,C) buffer; free when x is already channels_last."""
     y = x.permute(0, 2, 3, 1)
     if y.is_contiguous():
         return y
     return nchw_to_nhwc(x)
+
+
+NECK_INPUT_COPIES = [0]      # maps of a width that is no multiple of 32 that reached neck_input without a voucher and were copied
+
+
+def neck_input(x):
+    """What a neck reads of one backbone output (N,C,H,W): the NHWC buffer.  C % 32 == 0: from_nchw.  Else the dense kernels need the
+    pitch roundup(C, 32) with zeros behind the real channels: a view the backbone made (as_nchw_padded) hands over its buffer as it is;
+    any other tensor -- a user's slice of a wider tensor, whatever lies behind it -- is copied into a zeroed buffer of that pitch."""
+    C = x.shape[1]
+    if C % 32 == 0 or C <= 4:
+        return from_nchw(x)
+    buf = padded_buffer(x)
+    if buf is None:
+        N, _, H, W = x.shape
+        buf = torch.zeros((N, H, W, pad32(C)), device=x.device, dtype=torch.float32)
+        buf[..., :C].copy_(x.permute(0, 2, 3, 1))      # layout copy only (not on the benchmarked path: the counter shows a view that lost
+        NECK_INPUT_COPIES[0] += 1                      # its voucher on the way -- .detach(), a hook that re-wraps the outputs)
+    return buf
 
 
 def nchw_to_nhwc(x):
@@ -73,16 +119,18 @@ class PackedConv:
     ready = None    # record_ready() behind the last pack kernel (weights / Winograd image); see pack_ready()
     groups = 1      # > 1: a grouped 3x3 layer (ResNeXt conv2) in the layout of csrc/conv_group.hip, see _init_grouped
     cg = None       # ... its group width (channels per group)
+    C = None        # ... its real channels; Cin = Cout = the pitch of the maps it reads and writes (>= C, RegNet)
 
     def _packed(self):
         """A pack kernel was just enqueued on the current stream: consumers on OTHER streams (CPR_STREAMS > 1 sub-batches)
         must order themselves behind it."""
         self.ready = record_ready()
 
-    def __init__(self, weight, stride=1, padding=0, dtype=torch.float32, groups=1):
+    def __init__(self, weight, stride=1, padding=0, dtype=torch.float32, groups=1, pitch=None):
         if groups > 1:
-            self._init_grouped(weight, stride, padding, dtype, groups, None, 0)
+            self._init_grouped(weight, stride, padding, dtype, groups, None, 0, pitch)
             return
+        assert pitch is None, 'a channel pitch is the grouped kernels\' (dense layers pad their packs)'
         Cout, Cin, KH, KW = weight.shape
         w = weight.detach().to(torch.float32).permute(0, 2, 3, 1)  # OHWI
         self.dtype = dtype
@@ -119,19 +167,22 @@ class PackedConv:
         packed[:, :K] = wp.reshape(Cout, K)
         self.w = packed.contiguous()
 
-    def _init_grouped(self, weight, stride, padding, dtype, groups, scale, transpose):
+    def _init_grouped(self, weight, stride, padding, dtype, groups, scale, transpose, pitch=None):
         """A grouped 3x3 / padding 1 conv, weight (C, cg, 3, 3) with cg = C / groups in GROUP_WIDTHS (csrc/conv_group.hip): self.w is the
         kernel's own image, 9 * cg * C floats [tap][cg / 4][4][C / 4][4] (cpr_pack_weights_grouped), not the dense [Cout][Kpad] rows.
-        transpose: the data-gradient pack -- per group in / out channels swapped, taps flipped, ``scale`` multiplied in.  fp32 only."""
+        transpose: the data-gradient pack -- per group in / out channels swapped, taps flipped, ``scale`` multiplied in.  fp32 only.
+        pitch: floats between the pixels of the maps the layer reads and writes (>= C, a multiple of 4; None: C) -- the pack is the same."""
         C, cg, KH, KW = weight.shape
+        pitch = C if pitch is None else int(pitch)
+        assert pitch >= C and pitch % 4 == 0, 'grouped conv: the channel pitch %d must be a multiple of 4 and >= C = %d' % (pitch, C)
         if dtype != torch.float32:
             raise NotImplementedError('a grouped convolution (groups=%d) runs in the fp32 compute mode only, not in %s' % (groups, dtype))
         assert weight.is_cuda, 'the grouped pack is built on the device'
         assert cg * groups == C and cg in GROUP_WIDTHS and (KH, KW) == (3, 3) and padding == 1 and stride in (1, 2), \
             'grouped conv: 3x3 / padding 1 / stride 1 or 2 with a group width in %s, got weight %s groups %d stride %d padding %d' \
             % (GROUP_WIDTHS, tuple(weight.shape), groups, stride, padding)
-        self.dtype, self.groups, self.cg = torch.float32, groups, cg
-        self.Cout, self.Cin, self.KH, self.KW, self.Kpad = C, C, 3, 3, 9 * cg
+        self.dtype, self.groups, self.cg, self.C = torch.float32, groups, cg, C
+        self.Cout, self.Cin, self.KH, self.KW, self.Kpad = pitch, pitch, 3, 3, 9 * cg
         self.stride, self.padding = stride, 1
         src = weight.detach()
         if src.dtype != torch.float32 or not src.is_contiguous():
@@ -141,11 +192,11 @@ class PackedConv:
         self._packed()
 
     @classmethod
-    def for_dgrad_grouped(cls, weight, groups, scale=None):
+    def for_dgrad_grouped(cls, weight, groups, scale=None, pitch=None):
         """The grouped pack of the stride-1 grouped conv over dy (zero-inserted first for a stride-2 layer, conv2d_dgrad) that yields
         the data gradient of a grouped 3x3 / padding 1 conv: what for_dgrad is to the dense layers."""
         self = cls.__new__(cls)
-        self._init_grouped(weight, 1, 1, torch.float32, groups, scale, 1)
+        self._init_grouped(weight, 1, 1, torch.float32, groups, scale, 1, pitch)
         return self
 
     def _pack_bf16(self, weight, scale, transpose):
@@ -221,7 +272,7 @@ class PackedConv:
 
 
 CONV_RELU, CONV_OUT_BF16, CONV_RES_MASK, CONV_COLSUM = 1, 2, 4, 8      # include/cpr_hip.h CPR_CONV_*
-GROUP_WIDTHS = (4, 8, 16, 32)      # channels per group the grouped 3x3 kernels are built for (csrc/conv_group.hip)
+GROUP_WIDTHS = (4, 8, 16, 24, 32, 40, 48, 56)      # channels per group the grouped 3x3 kernels are built for (csrc/conv_group.hip)
 # bf16 mode: hand the fragment-order weight image to the conv launcher (the 256 x 256 tile then loads its weight operand
 # straight into registers, csrc/conv_bf16_dma.hip BD instance).  False keeps both operands on the LDS-DMA path (tests).
 WFRAG = [True]
@@ -397,8 +448,14 @@ def conv2d(x, pc, scale=None, bias=None, residual=None, relu=False, in_ab=None, 
         if out is None:
             out = torch.empty((N, OH, OW, pc.Cout), device=x.device, dtype=torch.float32)
         assert tuple(out.shape) == (N, OH, OW, pc.Cout) and out.is_contiguous()
-        _lib.call('cpr_conv_group_fwd', _ptr(x), _ptr(pc.w), _ptr(out), _ptr(scale), _ptr(bias), N, H, W, Cin, pc.cg, pc.stride,
-                  CONV_RELU if relu else 0, _stream())
+        if scale is not None or bias is not None:
+            assert (scale is None or _check(scale).numel() >= pc.C) and (bias is None or _check(bias).numel() >= pc.C)
+        if Cin == pc.C:
+            _lib.call('cpr_conv_group_fwd', _ptr(x), _ptr(pc.w), _ptr(out), _ptr(scale), _ptr(bias), N, H, W, Cin, pc.cg, pc.stride,
+                      CONV_RELU if relu else 0, _stream())
+        else:      # maps at a channel pitch: pad channels never read, written as +0.0
+            _lib.call('cpr_conv_group_fwd_pitch', _ptr(x), _ptr(pc.w), _ptr(out), _ptr(scale), _ptr(bias), N, H, W, pc.C, Cin, pc.cg,
+                      pc.stride, CONV_RELU if relu else 0, _stream())
         if TRACE_CONV_VARIANT[0]:
             TRACE_CONV_VARIANT[1] = ('group', pc.cg)
         return out
@@ -884,6 +941,32 @@ def stem_deep(x, packs, folds, planar=None, out_dtype=torch.float32):
     _lib.call('cpr_stem_deep_fwd', _ptr(x), _ptr(p1.w), _ptr(_check(s1)), _ptr(_check(b1)), _ptr(p2.w), _ptr(_check(s2)), _ptr(_check(b2)),
               _ptr(p3.w), _ptr(_check(s3)), _ptr(_check(b3)), _ptr(mid1), _ptr(mid2), _ptr(out), N, H, W, layout,
               int(out_dtype == torch.bfloat16), _stream())
+    return out
+
+
+def stem3x3s2(x, pc, scale, bias, planar=None):
+    """The RegNet stem (conv 3x3 / 2 / pad 1, 3 -> 32, + folded BatchNorm + ReLU, no max-pool): the deep stem's first launch alone
+    (csrc/stem_deep.hip), exact fp32 on the matrix cores.  x (N,H,W,4) NHWC4 or the (N,3,H,W) network input -> (N,OH,OW,32) fp32; both
+    input forms give the same bits.  pc: the conv's fp32 PackedConv."""
+    N, H, W, layout = _stem_input(_check(x), planar)
+    assert pc.dtype == torch.float32 and (pc.Cout, pc.Cin, pc.Kpad, pc.stride) == (32, 4, 64, 2) and (pc.KH, pc.KW, pc.padding) == (3, 3, 1), \
+        'stem3x3s2: conv3x3 3 -> 32 / stride 2 / padding 1'
+    pack_ready(pc)
+    out = torch.empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 32), device=x.device, dtype=torch.float32)
+    _lib.call('cpr_stem3x3s2_fwd', _ptr(x), _ptr(pc.w), _ptr(_check(scale)), _ptr(_check(bias)), _ptr(out), N, H, W, layout, _stream())
+    return out
+
+
+def stem3x3s2_wgrad(dy, x, planar=None, out=None):
+    """Weight gradient of that conv: dy (N,OH,OW,32) fp32 and the stem's input as the forward read it -> (32,3,3,3) fp32 (written into
+    ``out`` when given); the split over pixels is added up in a fixed order (csrc/stem3x3_bwd.hip)."""
+    N, H, W, layout = _stem_input(_check(x), planar)
+    assert _check(dy).shape == (N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 32), (tuple(dy.shape), tuple(x.shape))
+    if out is None:
+        out = torch.empty((32, 3, 3, 3), device=x.device, dtype=torch.float32)
+    assert _check(out).shape == (32, 3, 3, 3), tuple(out.shape)
+    ws = torch.empty((_lib.call('cpr_stem3x3s2_wgrad_workspace', N, H, W, positive=True),), device=x.device, dtype=torch.float32)
+    _lib.call('cpr_stem3x3s2_wgrad', _ptr(dy), _ptr(x), _ptr(out), _ptr(ws), N, H, W, layout, _stream())
     return out
 
 
@@ -1538,17 +1621,19 @@ def match_cost(pred, logits, gt, labels, cls_terms, reg_terms):
 
 
 # ------------------------------------------------------------------------------------------------ backward / optimizer
-def dgrad_pack(weight, stride, padding, scale=None, dtype=torch.float32, groups=1):
+def dgrad_pack(weight, stride, padding, scale=None, dtype=torch.float32, groups=1, pitch=None):
     """PackedConv that computes the data gradient of ``conv2d(x, weight, stride, padding)`` as a stride-1 forward conv
     over dy (zero-inserted first when stride > 1): channels swapped, taps flipped, padding K-1-p; ``scale`` (Cout,) is
     the forward conv's folded-BatchNorm scale, multiplied into the weights.  Stride-2 convs with k in {1, 3} and
     padding k//2 (every strided conv of the ResNet body) get the phase-decomposed form (PhasedDgrad).  groups > 1 (a grouped 3x3 layer):
-    the grouped data-gradient pack at either stride -- conv2d_dgrad zero-inserts a strided layer's gradient."""
+    the grouped data-gradient pack at either stride -- conv2d_dgrad zero-inserts a strided layer's gradient; ``pitch``: the channel pitch
+    of its gradient maps (PackedConv)."""
     if groups > 1:
         if dtype != torch.float32:
             raise NotImplementedError('a grouped convolution (groups=%d) runs in the fp32 compute mode only, not in %s' % (groups, dtype))
         assert padding == 1 and stride in (1, 2)
-        return PackedConv.for_dgrad_grouped(weight, groups, scale)
+        return PackedConv.for_dgrad_grouped(weight, groups, scale, pitch)
+    assert pitch is None
     if stride == 2 and weight.shape[2] == weight.shape[3] and weight.shape[2] in (1, 3) and padding == weight.shape[2] // 2 \
             and _PHASED[0]:
         return PhasedDgrad(weight, stride, padding, scale, dtype)
@@ -1701,22 +1786,27 @@ def conv3x3_wino_wgrad(dy, x, weight_shape, in_ab=None, in_relu=False, grad=None
 def conv2d_wgrad(dy, x, weight_shape, stride, padding, in_ab=None, in_relu=False, grad=None, out=None, groups=1):
     """grad_w [Cout][Cin][KH][KW]: accumulated into ``grad`` when given, written into ``out`` when given, else a new
     tensor.  in_ab: fused GroupNorm affine (+ReLU) of the input.  groups > 1: a grouped 3x3 / padding 1 layer, grad_w (C, C / groups, 3, 3)
-    (csrc/conv_group.hip; the split over pixels is added up in a fixed order)."""
+    (csrc/conv_group.hip; the split over pixels is added up in a fixed order); dy and x may sit at a channel pitch >= C (their last
+    dimension), whose pad channels are not read."""
     N, H, W, Cin = _check(x).shape
     _, OH, OW, Cout = _check(dy).shape
     KH, KW = weight_shape[2], weight_shape[3]
     if groups > 1:
-        cg = weight_shape[1]
-        assert Cout == Cin == weight_shape[0] == cg * groups and cg in GROUP_WIDTHS and (KH, KW) == (3, 3) and padding == 1 and \
+        cg, C = weight_shape[1], weight_shape[0]
+        assert Cout == Cin >= C == cg * groups and Cin % 4 == 0 and cg in GROUP_WIDTHS and (KH, KW) == (3, 3) and padding == 1 and \
             in_ab is None and not in_relu and x.dtype == torch.float32 and dy.dtype == torch.float32, (weight_shape, groups, Cin, Cout)
         assert (OH, OW) == ((H - 1) // stride + 1, (W - 1) // stride + 1), (dy.shape, x.shape, stride)
-        n = _lib.call('cpr_conv_group_wgrad_workspace', N, OH, OW, Cin, cg, positive=True)
+        n = _lib.call('cpr_conv_group_wgrad_workspace', N, OH, OW, C, cg, positive=True)
         ws = torch.empty((n,), device=x.device, dtype=torch.float32)
         acc = grad is not None
         if grad is None:
             grad = out if out is not None else torch.empty(tuple(weight_shape), device=x.device, dtype=torch.float32)
         assert tuple(grad.shape) == tuple(weight_shape) and grad.is_contiguous()
-        _lib.call('cpr_conv_group_wgrad', _ptr(dy), _ptr(x), _ptr(grad), _ptr(ws), N, H, W, Cin, cg, stride, int(acc), _stream())
+        if Cin == C:
+            _lib.call('cpr_conv_group_wgrad', _ptr(dy), _ptr(x), _ptr(grad), _ptr(ws), N, H, W, Cin, cg, stride, int(acc), _stream())
+        else:
+            _lib.call('cpr_conv_group_wgrad_pitch', _ptr(dy), _ptr(x), _ptr(grad), _ptr(ws), N, H, W, C, Cin, cg, stride, int(acc),
+                      _stream())
         return grad
     assert weight_shape[0] == Cout and weight_shape[1] == Cin, (weight_shape, Cout, Cin)
     if WINOGRAD[0] and KH == 3 and KW == 3 and stride == 1 and padding == 1 and Cin % 64 == 0 and Cout % 64 == 0 and \

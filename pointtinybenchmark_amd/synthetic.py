@@ -128,6 +128,35 @@ def res2net_state_dict(depth=50, scales=4, base_width=26, seed=0, prefix='backbo
     return sd
 
 
+def regnet_state_dict(arch='regnetx_3.2gf', seed=0, prefix='backbone.', avg_down=False, strides=(2, 2, 2, 2)):
+    """The keys and shapes of mmdet's RegNet (regnet.py), in its state-dict order: conv1 (32, 3, 3, 3) / bn1, then per block of stage
+    width W in groups of group_w channels conv1 (W, inplanes, 1, 1), conv2 (W, group_w, 3, 3), conv3 (W, W, 1, 1) with their norms and
+    the first block's downsample.0 / .1 (avg_down: .1 / .2).  ``arch``: a name of RegNet.arch_settings or the parameter dict.  Its own
+    generator: no other call's random stream moves."""
+    from .backbones.regnet import RegNet, stage_layout
+    g = torch.Generator().manual_seed(seed)
+    widths, group_widths, blocks = stage_layout(RegNet.arch_settings[arch] if isinstance(arch, str) else arch)
+    sd = {prefix + 'conv1.weight': _kaiming((32, 3, 3, 3), g)}
+    _bn(sd, prefix + 'bn1', 32, g)
+    ds = (1, 2) if avg_down else (0, 1)
+    inplanes = 32
+    for li, nb in enumerate(blocks):
+        W, gw = widths[li], group_widths[li]
+        for bi in range(nb):
+            p = '%slayer%d.%d.' % (prefix, li + 1, bi)
+            sd[p + 'conv1.weight'] = _kaiming((W, inplanes, 1, 1), g)
+            _bn(sd, p + 'bn1', W, g)
+            sd[p + 'conv2.weight'] = _kaiming((W, gw, 3, 3), g)
+            _bn(sd, p + 'bn2', W, g)
+            sd[p + 'conv3.weight'] = _kaiming((W, W, 1, 1), g)
+            _bn(sd, p + 'bn3', W, g)
+            if bi == 0 and (strides[li] != 1 or inplanes != W):
+                sd[p + 'downsample.%d.weight' % ds[0]] = _kaiming((W, inplanes, 1, 1), g)
+                _bn(sd, p + 'downsample.%d' % ds[1], W, g)
+            inplanes = W
+    return sd
+
+
 def fpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=1, seed=1, prefix='neck.', add_extra_convs=False,
                    extra_convs_on_inputs=True):
     """add_extra_convs (False / True / 'on_input' / 'on_lateral' / 'on_output', as FPN takes it): the stride-2 convs of the
@@ -239,9 +268,16 @@ def p2p_head_state_dict(num_classes=1, num_points=1, in_channels=256, feat_chann
 
 def locator_state_dict(depth=50, num_classes=1, start_level=0, head='cpr', seed=0, head_std=0.01, num_points=1,
                        num_cls_fcs=0, fc_out_channels=1024, binary_ins=False, ins_tower=False, out_bg_cls=False, deep_stem=False,
-                       avg_down=False, groups=1, base_width=4):
-    sd = resnet_state_dict(depth, seed, deep_stem=deep_stem, avg_down=avg_down, groups=groups, base_width=base_width)
-    sd.update(fpn_state_dict(backbone_out_channels(depth), 256, start_level, 1, seed + 1))
+                       avg_down=False, groups=1, base_width=4, arch=None):
+    """arch: a RegNet backbone (regnet_state_dict) in place of the ResNet of ``depth``; the FPN then reads its stage widths."""
+    if arch is not None:
+        from .backbones.regnet import RegNet, stage_layout
+        sd = regnet_state_dict(arch, seed, avg_down=avg_down)
+        chans = stage_layout(RegNet.arch_settings[arch] if isinstance(arch, str) else arch)[0]
+    else:
+        sd = resnet_state_dict(depth, seed, deep_stem=deep_stem, avg_down=avg_down, groups=groups, base_width=base_width)
+        chans = backbone_out_channels(depth)
+    sd.update(fpn_state_dict(chans, 256, start_level, 1, seed + 1))
     if head == 'cpr':
         sd.update(cpr_head_state_dict(num_classes, seed=seed + 2, std=head_std, num_cls_fcs=num_cls_fcs,
                                       fc_out_channels=fc_out_channels, binary_ins=binary_ins, ins_tower=ins_tower,

@@ -311,6 +311,8 @@ class BackwardEngine:
             if getattr(bb, 'compute_dtype', torch.float32) != torch.float32:
                 raise NotImplementedError('a Res2Net backbone (scales=%d) trains in the fp32 compute mode only: the bf16 compute mode has '
                                           'no slice convolution' % bb.scales)
+        if getattr(bb, 'fp32_only', None) and getattr(bb, 'compute_dtype', torch.float32) != torch.float32:
+            raise NotImplementedError(bb.fp32_only)      # (a RegNet backbone: backbones/regnet.py, naming ``arch``)
         dev = next(model.parameters()).device
         self._mixed, self._wide = False, {}     # set per step (bf16 compute mode = mixed precision)
         self._sink = None                       # None: p.grad (CprTrainer); dict: id(p) -> fresh tensor (autograd bridge)
@@ -486,6 +488,8 @@ class BackwardEngine:
         cm = rec['module']
         w, gn = cm.conv.weight, cm.gn
         assert cm.conv.bias is None
+        padded_in = rec['x'].dim() == 4 and rec['x'].shape[-1] != w.shape[1]
+        assert not padded_in or (rec['x'].dtype == torch.float32 and rec['in_ab'] is None)
         # mixed precision: ONE bf16 copy of the gradient map feeds the bf16 weight and data gradients
         dgrad16 = need_dx and MIXED_BF16['dgrad'] and rec['raw'].dtype == torch.bfloat16 and cm.conv.stride[0] == 1 and \
             w.shape[0] % 64 == 0
@@ -518,10 +522,26 @@ class BackwardEngine:
         else:
             x = self._f32(rec['x'])
             gw = self._g(w)
-            self._param_side(lambda: ops.conv2d_wgrad(draw, x, w.shape, cm.conv.stride[0], cm.conv.padding[0],
-                                                      in_ab=rec['in_ab'], in_relu=rec['in_relu'], out=gw), draw, x)
+            if padded_in:
+                # the input is a backbone map at its padded pitch (layers.packed_conv_padded_in): the weight gradient at the padded
+                # shape into scratch, the real columns copied out
+                self._param_side(lambda: gw.copy_(ops.conv2d_wgrad(draw, x, (w.shape[0], x.shape[-1]) + tuple(w.shape[2:]), cm.conv.stride[0],
+                                                                   cm.conv.padding[0])[:, :w.shape[1]]), draw, x)
+            else:
+                self._param_side(lambda: ops.conv2d_wgrad(draw, x, w.shape, cm.conv.stride[0], cm.conv.padding[0],
+                                                          in_ab=rec['in_ab'], in_relu=rec['in_relu'], out=gw), draw, x)
         if not need_dx:
             return None
+        if padded_in:      # the data gradient through a pack with zero columns in the pad: it arrives padded, pad channels exact zeros
+            Ip = rec['x'].shape[-1]
+
+            def make():
+                wp = torch.zeros((w.shape[0], Ip) + tuple(w.shape[2:]), device=w.device, dtype=torch.float32)
+                wp[:, :w.shape[1]].copy_(w.detach())
+                return ops.dgrad_pack(wp, cm.conv.stride[0], cm.conv.padding[0])
+            # (kept in the neck's pack cache beside the forward's packed_conv_padded_in; lapses with the weight epoch)
+            pt = _inner_neck(self.model.neck)._cache.get(('pc_padin_dgrad', id(cm.conv), Ip), [w], make)
+            return ops.conv2d_dgrad(draw, pt, (rec['x'].shape[1], rec['x'].shape[2]), cm.conv.stride[0], add=add)
         if dgrad16:
             assert add is None, 'the bf16 data gradient has no summed operand'
             # dx_bf16 (round 6): the caller hands the result to another bf16 GroupNorm backward, which reads a bf16 gradient map as it is
@@ -921,8 +941,23 @@ class BackwardEngine:
         # any subset of (conv1.weight, bn1.weight, bn1.bias) may train: each gradient is written only where its parameter trains
         dg_out = self._g(bn.weight) if bn.weight.requires_grad else None
         db_out = self._g(bn.bias) if bn.bias.requires_grad else None
-        dy, part = ops.stem_pool_bwd(dp, rec['arg'], rec['conv_hw'])
         x, planar = rec['x'], rec['planar']
+        if rec.get('regnet'):
+            # the RegNet stem (conv1 3x3/2 -> bn1 -> ReLU, no pool; eval-mode bn1 only): ReLU backward + column sums in one pass, the
+            # weight gradient of csrc/stem3x3_bwd.hip, then bn_fold_bwd as below
+            dy, cs = ops.relu_bwd_colsum(dp, rec['out'])
+            cache = bb._cache
+            scale, _ = folded_bn(cache, bn)
+            inv_sigma = bn_inv_sigma(cache, bn)
+
+            def regnet_param_grads():
+                gw = self._g(w) if w.requires_grad else torch.empty(tuple(w.shape), device=dy.device, dtype=torch.float32)
+                ops.stem3x3s2_wgrad(dy, x, planar=planar, out=gw)
+                ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, cs, want_affine=False, out_dgamma=dg_out, out_dbeta=db_out)
+            self._param_side(regnet_param_grads, dy, cs, x)
+            self._done([p for p in (w, bn.weight, bn.bias) if p.requires_grad][-1])
+            return
+        dy, part = ops.stem_pool_bwd(dp, rec['arg'], rec['conv_hw'])
         if rec.get('batch_stats'):
             st = rec['stats']
             dconv, _, _ = ops.bn_train_bwd(dy, rec['y'], st.cmean, st.rstd, bn.weight, center=st.center, out_dgamma=dg_out,
@@ -1066,6 +1101,8 @@ class BackwardEngine:
             return self._block_backward_batch_stats(cache, blk, rec, dout, need_dx)
         if blk.kind == 'bottle2neck':
             return self._bottle2neck_backward(cache, blk, rec, dout, need_dx)
+        if blk.kind == 'regnet':
+            return self._regnet_block_backward(cache, blk, rec, dout, need_dx)
         mixed = self._mixed
         x = rec['x']
         if isinstance(dout, tuple):
@@ -1199,6 +1236,94 @@ class BackwardEngine:
             tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
         else:
             dx = self._r2_pointwise_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3)
+            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
+        self._done(tail)
+        return dx
+
+    # ------------------------------------------------------------------ RegNet (backbones/regnet.py; fp32, eval-mode BatchNorm)
+    def _padded_conv_bn_backward(self, cache, conv, bn, g, colsum, x, need_dx, add=None):
+        """A dense conv (1x1 at either stride, or the 3x3 of a one-group block) -> folded eval-BN of a RegNet block whose maps sit at a
+        padded pitch: _r2_pointwise_backward with the layer's own kernel size, stride and padding.  g = d(pre-activation output) and
+        x are maps as the kernels wrote them (pad channels exact zeros), ``colsum`` the column sums of g's real channels.  Weight
+        gradient at the padded shape into scratch, real rows / columns copied out; data gradient through a pack with zero rows /
+        columns (and a zero folded scale) in the pad, so its pad channels are exact zeros."""
+        w = conv.weight
+        O, I = w.shape[:2]
+        Op, Ip = g.shape[-1], x.shape[-1]
+        stride, pad = conv.stride[0], conv.padding[0]
+        if (Op, Ip) == (O, I):
+            return self._conv_bn_backward(cache, conv, bn, g, colsum, x, need_dx, add=add)
+        scale, _ = folded_bn(cache, bn)
+        inv_sigma = bn_inv_sigma(cache, bn)
+        if w.requires_grad:
+            aff = bn.weight.requires_grad
+
+            def param_grads():
+                gw = self._g(w)
+                gw.copy_(ops.conv2d_wgrad(g, x, (Op, Ip) + tuple(w.shape[2:]), stride, pad)[:O, :I])
+                ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, colsum,
+                                out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
+            self._param_side(param_grads, g, colsum, x)
+        if not need_dx:
+            return None
+
+        def make():
+            wp = torch.zeros((Op, Ip) + tuple(w.shape[2:]), device=w.device, dtype=torch.float32)
+            wp[:O, :I].copy_(w.detach())
+            sp = scale.new_zeros((Op,))
+            sp[:O].copy_(scale)
+            return ops.dgrad_pack(wp, stride, pad, scale=sp)
+        pt = cache.get(('rg_dgrad', id(conv), Op, Ip), [w, bn.weight, bn.running_var], make)      # (lapses with the weight epoch)
+        return ops.conv2d_dgrad(g, pt, (x.shape[1], x.shape[2]), stride, add=add)
+
+    def _regnet_block_backward(self, cache, blk, rec, dout, need_dx):
+        """The rule of a padded RegNet block (kind 'regnet'): the bottleneck's walk conv3 -> conv2 -> conv1 (+ shortcut) on maps at the
+        padded pitch.  Every gradient map keeps exact zeros in its pad channels: a ReLU mask there is 0, the dense data gradients run
+        through packs with zero rows, the grouped data gradient writes them itself; column sums are cut to the real channels."""
+        x, o1, o2 = rec['x'], rec['o1'], rec['o2']
+        W, P = blk.width, blk.planes
+        if isinstance(dout, tuple):
+            g3, cs3 = dout[0], dout[1]
+        else:
+            g3, cs3 = ops.relu_bwd_colsum(dout, rec['out'])          # also the shortcut gradient
+        cs3 = cs3[:P]
+        d2 = self._padded_conv_bn_backward(cache, blk.conv3, blk.bn3, g3, cs3, o2, True)
+        g2, cs2 = ops.relu_bwd_colsum(d2, o2)
+        cs2 = cs2[:W]
+        del d2
+        conv, bn = blk.conv2, blk.bn2
+        if conv.groups == 1:
+            d1 = self._padded_conv_bn_backward(cache, conv, bn, g2, cs2, o1, True)
+        else:
+            w = conv.weight
+            scale, _ = folded_bn(cache, bn)
+            if w.requires_grad:
+                aff = bn.weight.requires_grad
+
+                def param_grads():
+                    gw = self._g(w)
+                    ops.conv2d_wgrad(g2, o1, w.shape, conv.stride[0], 1, out=gw, groups=conv.groups)
+                    ops.bn_fold_bwd(gw, w, scale, bn.running_mean, bn_inv_sigma(cache, bn), cs2,
+                                    out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
+                self._param_side(param_grads, g2, cs2, o1)
+            pt = dgrad_packed(cache, conv, bn, pitch=o1.shape[-1])
+            d1 = ops.conv2d_dgrad(g2, pt, (o1.shape[1], o1.shape[2]), conv.stride[0])
+        g1, cs1 = ops.relu_bwd_colsum(d1, o1)
+        cs1 = cs1[:W]
+        del d1
+        self._done(blk.bn3.bias if blk.bn3.bias.requires_grad else blk.conv2.weight)
+        if blk.downsample is not None:
+            dx = self._padded_conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx)
+            pool = blk.ds_pool
+            if pool:
+                dxp = self._padded_conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, rec['xp'], need_dx)
+                if need_dx:
+                    dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
+            else:
+                dx = self._padded_conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx)
+            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
+        else:
+            dx = self._padded_conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3)
             tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
         self._done(tail)
         return dx
@@ -1525,7 +1650,7 @@ class CprTrainer(BackwardEngine):
                     if blk.downsample is not None:
                         add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
                     continue
-                if blk.kind == 'bottleneck':
+                if blk.kind in ('bottleneck', 'regnet'):       # ('regnet': a padded RegNet block, _regnet_block_backward -- the same walk)
                     add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
                 add(blk.conv2.weight, blk.bn2.weight, blk.bn2.bias, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
                 if blk.downsample is not None:

@@ -1,0 +1,328 @@
+"""-m gpu: the RegNet backbone (backbones/regnet.py) on the grouped 3x3 kernels at a channel pitch, the 3x3 stem and its weight gradient.
+
+  fixture    tests/golden/regnet.npz (the reference's own RegNet in fp64, tools/gen_regnet.py): stage outputs <= 2e-4 max|level|,
+             parameter gradients of the fixture's linear functional through BackwardEngine._backward_backbone <= 2e-3 rel-L2; the
+             recorded forward has the forward-only bits; pad channels of every stage output buffer and of every stage-input gradient
+             are bit-zero
+  neck       FPN(num_outs=5, add_extra_convs='on_input') on the padded x1.6gf outputs read in place, against fp64 autograd of
+             tests/fpn_extra_ref.fpn_forward on the compact outputs; a user's slice of a wider tensor with NaN behind it takes the
+             copying route and gives its contiguous copy's outputs
+  locator    P2PTrainer / CprTrainer on x1.6gf with frozen_stages=-1 at 70 x 90: gradients bit-equal to loss.backward() through the
+             autograd bridge; after one optimizer step a fresh model holding the stepped weights gives the same forward bit for bit
+             (the packs, padded ones included, were refreshed); the bf16 compute mode raises, naming ``arch``"""
+import pytest
+import torch
+
+from pointtinybenchmark_amd import synthetic
+from tests import fpn_extra_ref as FR
+from tests import regnet_ref as RG
+
+pytestmark = pytest.mark.gpu
+
+
+def _rel_l2(a, b):
+    a, b = a.detach().double().flatten().cpu(), b.detach().double().flatten().cpu()
+    return float((a - b).norm() / max(float(b.norm()), 1e-30))
+
+
+def _bit_zero(t):
+    return t.numel() == 0 or int(torch.count_nonzero(t.contiguous().view(torch.int32))) == 0
+
+
+def _case_model(name):
+    import pointtinybenchmark_amd as P
+    cfg = RG.CASES[name]
+    m = P.build_backbone(dict(type='RegNet', **RG.regnet_kwargs(cfg))).cuda()
+    m.load_state_dict(RG.case_state_dict(cfg), strict=True)
+    m.train()
+    return cfg, m
+
+
+def _pads_are_zero(m, outs):
+    """Every stage output: the reference's shape; a padded stage's view carries its buffer, whose pad channels are bit-zero."""
+    from pointtinybenchmark_amd import ops
+    for i, o in enumerate(outs):
+        C = m.stage_widths[i]
+        assert o.shape[1] == C
+        buf = ops.padded_buffer(o)
+        assert (buf is not None) == (C % 32 != 0), (i, C)
+        if buf is not None:
+            assert buf.shape[-1] == ops.pad32(C) and _bit_zero(buf[..., C:]) and torch.equal(buf[..., :C].permute(0, 3, 1, 2), o)
+
+
+@pytest.mark.parametrize('name', RG.CASE_NAMES)
+def test_stage_outputs_vs_reference(name):
+    cfg, m = _case_model(name)
+    img = RG.case_input(cfg).cuda()
+    with torch.no_grad():
+        outs = m(img)
+        again = m(img)
+    torch.cuda.synchronize()
+    assert len(outs) == 4
+    _pads_are_zero(m, outs)
+    failed = []
+    for l, o in enumerate(outs):
+        e = RG.output_error(name, l, o)
+        print('ERR forward %-20s stage %d %-10s max|diff|/max|level| %.2e (bar 2e-4)' % (name, l, tuple(o.shape[1:]), e), flush=True)
+        if not e <= RG.BAR_OUT:
+            failed.append((l, e))
+        assert torch.equal(o, again[l])
+    assert not failed, failed
+
+
+@pytest.mark.parametrize('name', RG.CASE_NAMES)
+def test_parameter_gradients_vs_reference(name):
+    """The recorded forward + BackwardEngine._backward_backbone on the fixture's linear functional (the gradient of stage l's output
+    = w_l, zero in the pad channels) against the reference class's fp64 autograd: rel-L2 <= 2e-3 per tensor, on the norm and on the
+    strided sample.  The gradient every block hands down keeps bit-zero pad channels."""
+    from pointtinybenchmark_amd import ops
+    from pointtinybenchmark_amd.training import BackwardEngine
+    cfg, m = _case_model(name)
+    eng = BackwardEngine(m)
+    eng._sink = {}
+    tape = []
+    outs = m(RG.case_input(cfg).cuda(), tape=tape)
+    with torch.no_grad():       # the forward-only path (fused projection shortcut) gives the recorded one's bits
+        plain = m(RG.case_input(cfg).cuda())
+    for a, b in zip(outs, plain):
+        assert torch.equal(a, b)
+    _pads_are_zero(m, outs)
+    d_stage = {}
+    for l, o in enumerate(outs):
+        if l + 1 > cfg['frozen_stages']:
+            w = RG.functional_weight(cfg, l, o.shape).permute(0, 2, 3, 1)
+            d = torch.zeros(tuple(w.shape[:3]) + (ops.pad32(w.shape[3]),))
+            d[..., :w.shape[3]] = w
+            d_stage[l] = d.cuda()
+    rule, handed = eng._block_backward, []
+
+    def spy(cache, blk, rec, dout, need_dx, **kw):
+        dx = rule(cache, blk, rec, dout, need_dx, **kw)
+        if dx is not None:
+            handed.append((blk.inplanes, dx[0] if isinstance(dx, tuple) else dx))
+        return dx
+    eng._block_backward = spy
+    eng._backward_backbone(m, tape, d_stage)
+    named = [(k, p) for k, p in m.named_parameters() if p.requires_grad]
+    assert [k for k, _ in named] == RG.grad_names(name)
+    grads = dict(zip([k for k, _ in named], eng.collect([p for _, p in named])))
+    torch.cuda.synchronize()
+    assert handed
+    for C, dx in handed:
+        assert dx.shape[-1] == ops.pad32(C) and _bit_zero(dx[..., C:]), (C, tuple(dx.shape))
+    failed, worst = [], 0.0
+    for k, g in grads.items():
+        assert g is not None and bool(torch.isfinite(g).all()), k
+        en, es = RG.grad_errors(name, k, g)
+        worst = max(worst, en, es)
+        if not (en <= RG.BAR_GRAD and es <= RG.BAR_GRAD):
+            failed.append((k, en, es))
+    print('ERR backward %-20s %d tensors, worst of norm / sample rel-L2 %.2e (bar 2e-3)' % (name, len(grads), worst), flush=True)
+    assert not failed, failed[:8]
+
+
+# ------------------------------------------------------------------------------------------------ the neck on padded maps
+class _BackboneNeck(torch.nn.Module):
+    def __init__(self, backbone, neck):
+        super().__init__()
+        self.backbone, self.neck, self.bbox_head = backbone, neck, None
+
+
+def _neck(seed=11):
+    import pointtinybenchmark_amd as P
+    neck = P.build_neck(dict(type='FPN', in_channels=[72, 168, 408, 912], out_channels=64, num_outs=5, add_extra_convs='on_input',
+                             norm_cfg=dict(type='GN', num_groups=32))).cuda()
+    sd = synthetic.fpn_state_dict([72, 168, 408, 912], 64, 0, 5, seed, prefix='', add_extra_convs='on_input')
+    neck.load_state_dict(sd, strict=True)
+    return neck, sd
+
+
+def test_fpn_reads_the_padded_maps_in_place_vs_fp64_autograd(monkeypatch):
+    """x1.6gf (every stage padded): FPN with an 'on_input' extra level on the backbone's own views.  Reference: fp64 autograd of
+    fpn_extra_ref.fpn_forward on the compact (contiguous, fp64) copies of the same stage outputs, functional sum_l <w_l, out_l>."""
+    from pointtinybenchmark_amd import ops
+    from pointtinybenchmark_amd.training import BackwardEngine
+    cfg, bb = _case_model('x1.6gf')
+    neck, sd = _neck()
+    copies, n_copied = [], ops.NECK_INPUT_COPIES[0]
+    real = ops.nchw_to_nhwc
+    monkeypatch.setattr(ops, 'nchw_to_nhwc', lambda x: copies.append(tuple(x.shape)) or real(x))
+    with torch.no_grad():
+        feats = bb(RG.case_input(cfg).cuda())
+    eng = BackwardEngine(_BackboneNeck(bb, neck))
+    eng._sink = {}
+    eng.begin_step()
+    tape = []
+    lazy = neck.forward_lazy(feats, tape=tape)
+    assert not copies and ops.NECK_INPUT_COPIES[0] == n_copied, copies   # no map took the copying route
+    for r in tape:
+        if r['kind'] in ('lateral', 'extra'):
+            assert r['x'].shape[-1] % 32 == 0 and r['x'].data_ptr() in {ops.padded_buffer(f).data_ptr() for f in feats}
+    with torch.no_grad():
+        outs = neck(feats)
+    assert len(outs) == len(lazy) == 5
+    for l, (raw, (a, b)) in enumerate(lazy):
+        assert torch.equal(ops.as_nchw(ops.gn_apply(raw, a, b)), outs[l])
+    ws = [FR.functional_weight(dict(seed=cfg['seed']), l, o.shape) for l, o in enumerate(outs)]
+    dzs = [w.float().permute(0, 2, 3, 1).contiguous().cuda() for w in ws]
+    d_stage = eng._backward_neck(neck, tape, dzs)
+    params = dict(neck.named_parameters())
+    grads = dict(zip(params, eng.collect(list(params.values()))))
+    torch.cuda.synchronize()
+    # fp64 autograd on the compact copies
+    sd64 = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    x64 = [f.detach().double().cpu().contiguous().requires_grad_(True) for f in feats]
+    ref = FR.fpn_forward(sd64, x64, 5, add_extra_convs='on_input')
+    sum((w * o).sum() for w, o in zip(ws, ref)).backward()
+    failed = []
+    for l, o in enumerate(outs):
+        e = float((o.double().cpu() - ref[l].detach()).abs().max() / ref[l].detach().abs().max())
+        print('ERR neck forward level %d %-10s max|diff|/max|level| %.2e (bar 2e-4)' % (l, tuple(o.shape[2:]), e), flush=True)
+        if not e <= RG.BAR_OUT:
+            failed.append(('out%d' % l, e))
+    names = ['lateral_convs.%d.conv.weight' % j for j in range(4)] + ['fpn_convs.4.conv.weight']
+    for k in sorted(grads):
+        assert grads[k] is not None and bool(torch.isfinite(grads[k]).all()), k
+        e = _rel_l2(grads[k], sd64[k].grad)
+        if k in names:
+            print('ERR neck backward %-32s rel-L2 %.2e (bar 2e-3)' % (k, e), flush=True)
+        if not e <= RG.BAR_GRAD:
+            failed.append((k, e))
+    assert set(names) <= set(grads) and tuple(grads['fpn_convs.4.conv.weight'].shape) == (64, 912, 3, 3)
+    # the gradients handed to the trainable stages arrive padded, pad channels bit-zero, real channels as autograd's
+    assert sorted(d_stage) == [0, 1, 2, 3] and d_stage[0] is None
+    for i in (1, 2, 3):
+        C = bb.stage_widths[i]
+        assert d_stage[i].shape[-1] == ops.pad32(C) and _bit_zero(d_stage[i][..., C:])
+        e = _rel_l2(d_stage[i][..., :C].permute(0, 3, 1, 2), x64[i].grad)
+        if not e <= RG.BAR_GRAD:
+            failed.append(('in%d' % i, e))
+    assert not failed, failed
+
+
+def test_a_users_slice_with_nan_behind_it_takes_the_copying_route():
+    from pointtinybenchmark_amd import ops
+    cfg, bb = _case_model('x1.6gf')
+    neck, _ = _neck()
+    with torch.no_grad():
+        feats = bb(RG.case_input(cfg).cuda())
+        want = neck(feats)
+        sliced, compact = [], []
+        for f in feats:
+            N, C, H, W = f.shape
+            wide = torch.full((N, H, W, ops.pad32(C) + 8), float('nan'), device='cuda')
+            wide[..., :C] = f.permute(0, 2, 3, 1)
+            v = wide[..., :C].permute(0, 3, 1, 2)
+            assert ops.padded_buffer(v) is None and bool(torch.isnan(wide[..., C:]).all())
+            sliced.append(v)
+            compact.append(f.contiguous())
+            assert ops.padded_buffer(compact[-1]) is None
+        n_copied = ops.NECK_INPUT_COPIES[0]
+        got, got_c = neck(sliced), neck(compact)
+        assert ops.NECK_INPUT_COPIES[0] == n_copied + 10         # four laterals + the on_input source, twice: every map that came without a voucher
+        lazy = neck.forward_lazy(sliced)
+    torch.cuda.synchronize()
+    for l in range(5):
+        assert bool(torch.isfinite(got[l]).all())
+        assert torch.equal(got[l], got_c[l]) and torch.equal(got[l], want[l]), l
+        raw, (a, b) = lazy[l]
+        assert torch.equal(ops.as_nchw(ops.gn_apply(raw, a, b)), want[l])
+
+
+# ------------------------------------------------------------------------------------------------ locator
+ARCH = 'regnetx_1.6gf'
+
+
+def _locator(head, seed=3):
+    import pointtinybenchmark_amd as P
+    from bench import model_cfg, p2p_model_cfg
+    cfg = model_cfg(50, 1) if head == 'cpr' else p2p_model_cfg(50, 1)
+    cfg['backbone'] = dict(type='RegNet', arch=ARCH, out_indices=(0, 1, 2, 3), frozen_stages=-1, norm_cfg=dict(type='BN', requires_grad=True),
+                           norm_eval=True, style='pytorch')
+    cfg['neck'] = dict(cfg['neck'], in_channels=[72, 168, 408, 912])
+    m = P.build_detector(cfg).cuda()
+    m.load_state_dict(synthetic.locator_state_dict(num_classes=1, head=head, seed=seed, head_std=0.3, arch=ARCH), strict=True)
+    m.train()
+    return m
+
+
+def _data():
+    batch = synthetic.synthetic_batch(2, 70, 90, 5, 1, seed=3, ragged=True)
+    return dict(img=batch['img'].cuda(), img_metas=batch['img_metas'], gt_bboxes=[b.cuda() for b in batch['gt_bboxes']],
+                gt_labels=[l.cuda() for l in batch['gt_labels']])
+
+
+def _trainer(head):
+    from pointtinybenchmark_amd.training import CprTrainer, P2PTrainer
+    return CprTrainer if head == 'cpr' else P2PTrainer
+
+
+@pytest.mark.parametrize('head', ['p2p', 'cpr'])
+def test_bridge_is_bit_equal_to_the_trainer(head):
+    data = _data()
+    ma = _locator(head)
+    tr = _trainer(head)(ma)
+    la = tr.forward_backward(**data)
+    torch.cuda.synchronize()
+    want = {k: p.grad.clone() for k, p in ma.named_parameters() if p.requires_grad}
+    for k, shape in (('backbone.conv1.weight', (32, 3, 3, 3)), ('backbone.layer2.0.conv2.weight', (168, 24, 3, 3)),
+                     ('backbone.layer1.0.downsample.0.weight', (72, 32, 1, 1)), ('neck.lateral_convs.3.conv.weight', (256, 912, 1, 1))):
+        assert tuple(want[k].shape) == shape and float(want[k].abs().max()) > 0 and bool(torch.isfinite(want[k]).all()), k
+    assert 'backbone.bn1.weight' in want and 'backbone.bn1.bias' in want
+    mb = _locator(head)
+    out = mb.train_step(dict(data))
+    assert out['loss'].requires_grad
+    out['loss'].backward()
+    torch.cuda.synchronize()
+    n = 0
+    for k, p in mb.named_parameters():
+        if p.requires_grad:
+            assert p.grad is not None and torch.equal(p.grad, want[k]), k
+            n += 1
+        else:
+            assert p.grad is None, k
+    assert n == len(want) and n > 0
+    for v in la.values():
+        for t in (v if isinstance(v, (list, tuple)) else [v]):
+            assert bool(torch.isfinite(t).all())
+
+
+def test_optimizer_step_refreshes_the_packs_padded_ones_included():
+    from pointtinybenchmark_amd import layers
+    data = _data()
+    m = _locator('p2p')
+    tr = _trainer('p2p')(m, lr=0.05)
+    with torch.no_grad():
+        m.eval()
+        before = [o.clone() for o in m.backbone(data['img'])]     # builds the packs the step must refresh
+        m.train()
+    out = tr.train_step(dict(data))
+    torch.cuda.synchronize()
+    assert all(v == v and abs(v) < float('inf') for v in out['log_vars'].values()), out['log_vars']
+    jobs = [j for j in m.backbone._cache._jobs.values() if isinstance(j, layers.GroupPackJob)]
+    assert len(jobs) >= 18 and {j.transpose for j in jobs} == {0, 1}     # forward and data-gradient packs of the grouped layers
+    assert all(j.value.C % 32 != 0 and j.value.Cin == (j.value.C + 31) // 32 * 32 for j in jobs)
+    m.eval()
+    fresh = _locator('p2p')
+    fresh.load_state_dict({k: v.detach().clone() for k, v in m.state_dict().items()}, strict=True)
+    fresh.eval()
+    with torch.no_grad():
+        a, b = m.backbone(data['img']), fresh.backbone(data['img'])
+        la, lb = m.extract_feat(data['img']), fresh.extract_feat(data['img'])
+    torch.cuda.synchronize()
+    assert not torch.equal(a[0], before[0])                       # frozen_stages=-1: everything moved
+    for x, y in zip(list(a) + list(la), list(b) + list(lb)):
+        assert torch.equal(x, y), 'forward after the step differs from a fresh model in %d entries' % int((x != y).sum())
+
+
+def test_bf16_mode_raises_naming_arch():
+    from pointtinybenchmark_amd import autograd_bridge
+    m = _locator('p2p')
+    with pytest.raises(NotImplementedError, match="arch='regnetx_1.6gf'"):
+        m.set_compute_dtype('bf16')
+    m.backbone.compute_dtype = torch.bfloat16
+    assert "arch='regnetx_1.6gf'" in autograd_bridge.unsupported_reason(m)
+    with pytest.raises(NotImplementedError, match="arch='regnetx_1.6gf'"):
+        m.backbone(torch.zeros((1, 3, 64, 64), device='cuda'))
+    with pytest.raises(NotImplementedError, match="arch='regnetx_1.6gf'"):
+        _trainer('p2p')(m)
