@@ -45,6 +45,17 @@ int cpr_conv2d_fwd(const float* in, const float* wgt, float* out, const float* s
                    const float* residual, const float* in_a, const float* in_b, float* gn_part, int N, int H, int W,
                    int Cin, int Cout, int KH, int KW, int stride, int pad, int Kpad, int flags, int in_relu,
                    int* variant_out, void* stream);
+/* The same with dilated taps: the 3x3 conv2 of a dilated ResNet stage (T/mmdet/models/backbones/resnet.py:36-47, 175-200: padding =
+ * dilation) and, over dy with the data-gradient pack (padding 2 dil - dil = dil), its data gradient.  KH = KW = 3, stride 1, pad == dil,
+ * Cin % 32 == 0, Kpad = 9 Cin; tap (kh, kw) reads pixel (oy + (kh - 1) dil, ox + (kw - 1) dil), OH = H, OW = W.  wgt is the pack of
+ * cpr_conv2d_fwd, unchanged.  Epilogue: scale, bias, residual, CPR_CONV_RELU, CPR_CONV_RES_MASK, CPR_CONV_COLSUM (gn_part then holds the
+ * column-sum partials and must be given; without the flag it must be NULL).  in_a / in_b, in_relu, GroupNorm partials,
+ * CPR_CONV_OUT_BF16, another stride or pad != dil: CPR_ERR_ARG before any launch.  dil == 1 is cpr_conv2d_fwd, bit for bit.  Direct
+ * kernel only (no Winograd, streamed or dual form). */
+int cpr_conv2d_fwd_dil(const float* in, const float* wgt, float* out, const float* scale, const float* bias,
+                       const float* residual, const float* in_a, const float* in_b, float* gn_part, int N, int H, int W,
+                       int Cin, int Cout, int KH, int KW, int stride, int pad, int dil, int Kpad, int flags, int in_relu,
+                       int* variant_out, void* stream);
 
 /* First block of a ResNet stage (Bottleneck.forward, T/mmdet/models/backbones/resnet.py:262-302 with the projection shortcut
  * built by ResLayer, T/mmdet/models/utils/res_layer.py / resnet.py:564-610): out = relu?((conv(in, wgt) * scale + bias)
@@ -405,6 +416,11 @@ int cpr_conv2d_wgrad_workspace(int N, int OH, int OW, int Cin, int Cout, int KH,
 int cpr_conv2d_wgrad(const float* dy, const float* x, const float* in_a, const float* in_b, float* grad_w, float* ws,
                      int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int in_relu,
                      int accumulate, void* stream);
+/* The same weight gradient with dilated taps (tap step dil >= 1): x is read at (oy stride + kh dil - pad, ox stride + kw dil - pad),
+ * OH = (H + 2 pad - dil (KH - 1) - 1) / stride + 1.  No fused input transform.  ws: cpr_conv2d_wgrad_workspace of the same shapes; the
+ * slabs are summed in the same fixed order (no atomics).  dil == 1 is cpr_conv2d_wgrad, bit for bit. */
+int cpr_conv2d_wgrad_dil(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int Cin, int Cout, int KH,
+                         int KW, int stride, int pad, int dil, int accumulate, void* stream);
 /* The same weight gradient for 3x3 / stride 1 / pad 1 layers as fused Winograd F(2x2,3x3) (the adjoint of
  * cpr_conv3x3_wino_fwd with respect to the weights: 2.25x fewer multiplies; csrc/conv_wino_wgrad.hip).  Cin % 64 == 0,
  * Cout % 64 == 0; ws: cpr_conv3x3_wino_wgrad_workspace(...) floats (split-K partials, reduced inside the call). */
@@ -488,6 +504,14 @@ int cpr_conv_group_fwd_pitch(const float* x, const float* wp, float* out, const 
                              int C, int Cp, int cg, int stride, int flags, void* stream);
 int cpr_conv_group_wgrad_pitch(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int Cp, int cg,
                                int stride, int accumulate, void* stream);
+/* The grouped 3x3 with dilated taps (a dilated ResNeXt stage: stride 1, padding = tap step = dil >= 1, OH = H, OW = W), unpitched maps:
+ * forward -- over dy with the data-gradient pack, the data gradient -- and weight gradient.  Packs and workspace query are those of
+ * cpr_conv_group_fwd / _wgrad; still 9 * cg FMAs per output, tap-major: bit-repeatable and batch independent.  dil == 1 launches what
+ * the undilated entries launch at stride 1. */
+int cpr_conv_group_fwd_dil(const float* x, const float* wp, float* out, const float* scale, const float* bias, int N, int H, int W,
+                           int C, int cg, int dil, int flags, void* stream);
+int cpr_conv_group_wgrad_dil(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int cg, int dil,
+                             int accumulate, void* stream);
 /* ---- Res2Net slice kernels (Bottle2neck's 3x3 chain; csrc/res2net.hip), NHWC fp32, plain fp32 FMA ------------------------------
  * A slice is the channels [off, off + width) of a map whose pixels are `pitch` floats apart.  width even, 2 .. 512; every offset and
  * pitch even and every base pointer 8-byte aligned (the kernels move float2), off + width <= pitch: anything else is CPR_ERR_ARG before

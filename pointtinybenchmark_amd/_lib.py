@@ -19,6 +19,7 @@ _d = ctypes.c_double
 SIGNATURES = {
     'cpr_version': [],
     'cpr_conv2d_fwd': [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
+    'cpr_conv2d_fwd_dil': [_p] * 9 + [_i] * 13 + [_p, _p],
     'cpr_conv2d_dual_fwd': [_p] * 9 + [_i] * 16 + [_p, _p],
     'cpr_conv1x1_stream_fwd': [_p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _p],
     'cpr_conv_wgrad_bf16_workspace_s': [_i] * 9,
@@ -89,6 +90,7 @@ SIGNATURES = {
     # training step: backward + optimizer
     'cpr_conv2d_wgrad_workspace': [_i] * 7,
     'cpr_conv2d_wgrad': [_p] * 6 + [_i] * 11 + [_p],
+    'cpr_conv2d_wgrad_dil': [_p] * 4 + [_i] * 11 + [_p],
     'cpr_gn_bwd': [_p] * 12 + [_i] * 7 + [_p],
     'cpr_gn_bwd_bf16': [_p] * 13 + [_i] * 7 + [_p],
     'cpr_gn_bwd_bf16_dz16': [_p] * 13 + [_i] * 7 + [_p],
@@ -130,6 +132,8 @@ SIGNATURES = {
     'cpr_conv_group_wgrad': [_p] * 4 + [_i] * 7 + [_p],
     'cpr_conv_group_fwd_pitch': [_p] * 5 + [_i] * 8 + [_p],
     'cpr_conv_group_wgrad_pitch': [_p] * 4 + [_i] * 8 + [_p],
+    'cpr_conv_group_fwd_dil': [_p] * 5 + [_i] * 7 + [_p],
+    'cpr_conv_group_wgrad_dil': [_p] * 4 + [_i] * 7 + [_p],
     'cpr_res2_pack_weights': [_p, _p, _p, _i, _i, _p],
     'cpr_res2_conv_fwd': [_p, _i, _i, _p, _i, _i, _p, _p, _i, _i, _p, _p] + [_i] * 9 + [_p],
     'cpr_res2_conv_wgrad_workspace': [_i] * 4,

@@ -114,6 +114,8 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
         return 'needs an FPN neck with num_outs == 1 (every shipped CPR config; CPRHead asserts one level, cpr_head.py:487)'
     if bb.compute_dtype != torch.float32 and getattr(bb, 'groups', 1) > 1:
         return 'a grouped backbone (ResNeXt groups=%d) runs in the fp32 compute mode only, not with the bf16 compute mode' % bb.groups
+    if bb.compute_dtype != torch.float32 and any(d != 1 for d in getattr(bb, 'dilations', ())):
+        return 'a dilated backbone (dilations=%r) runs in the fp32 compute mode only, not with the bf16 compute mode' % (tuple(bb.dilations),)
     if getattr(bb, 'scales', 0):          # a Res2Net backbone (backbones/res2net.py)
         if bb.compute_dtype != torch.float32:
             return 'a Res2Net backbone (scales=%d) runs in the fp32 compute mode only, not with the bf16 compute mode' % bb.scales

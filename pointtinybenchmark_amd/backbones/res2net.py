@@ -11,8 +11,9 @@ there is no split / contiguous / cat copy.  The last slice is copied, or in a st
 
 Built here: the forward (eval-mode BatchNorm, fp32 compute mode), through ``forward`` and the locators' lazy path, with the forward-only
 fused shortcut (ops.conv2d_dual), and the recorded forward (``tape=``) whose backward rule is training.BackwardEngine._bottle2neck_backward.
-Refused, each naming its key: the bf16 compute mode (``scales``), BatchNorm batch statistics inside the blocks (``norm_eval``), and what
-ResNet refuses (dilations, dcn, plugins, with_cp, a trainable deep stem)."""
+Refused, each naming its key: the bf16 compute mode (``scales``), BatchNorm batch statistics inside the blocks (``norm_eval``), any
+``dilations`` other than 1 (the slice kernels have no dilated form), and what ResNet refuses (dcn, plugins, with_cp, a trainable deep
+stem)."""
 import math
 
 import torch
@@ -162,11 +163,14 @@ class Res2Net(ResNet):
         why = unsupported_reason(scales, base_width, kwargs.get('base_channels', 64), kwargs.get('num_stages', 4))
         if why is not None:
             raise NotImplementedError(why)
+        dil = tuple(kwargs.get('dilations', (1, 1, 1, 1)))[:kwargs.get('num_stages', 4)]
+        assert all(d == 1 for d in dil), \
+            'Res2Net dilations=%r is not built: the slice kernels (csrc/res2net.hip) have no dilated form -- every stage runs at dilation 1' % (dil,)
         self.scales = scales
         self.base_width = base_width
         super().__init__(style='pytorch', deep_stem=True, avg_down=True, **kwargs)
 
-    def _make_block(self, kind, inplanes, planes, stride, downsample, norm, style, base_channels, first):
+    def _make_block(self, kind, inplanes, planes, stride, downsample, norm, style, base_channels, first, dilation=1):
         return _Bottle2neck(inplanes, planes, stride, downsample, norm, self.scales, self.base_width, base_channels,
                             'stage' if first else 'normal')
 

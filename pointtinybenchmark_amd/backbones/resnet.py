@@ -8,6 +8,9 @@ non-frozen stages are in training mode (the reference's ``train()``) and normali
 normalise / residual / ReLU pass (csrc/bn_train.hip), running statistics updated on the device.  norm_cfg type 'SyncBN' (or
 torch.nn.SyncBatchNorm.convert_sync_batchnorm) builds nn.SyncBatchNorm modules -- same names and state-dict keys -- whose batch statistics
 run over the rows of every rank of their process group (``sync_group``); on one rank they are BatchNorm bit for bit.
+``dilations[i] > 1`` in a stage with ``strides[i] == 1`` (DC5: strides (1, 2, 2, 1), dilations (1, 1, 1, 2)) puts every block's 3x3 of that stage
+at padding = dilation (resnet.py:36-47, 175-200), on the dilated instances of the direct conv kernels (fp32 compute mode; ops.PackedConv
+``dilation``); a stage that is dilated and strided is refused.
 The backward of the trainable stages -- and of a trainable stem (frozen_stages=-1) -- is driven by training.CprTrainer from the records
 of ``forward(tape=)``."""
 import math
@@ -41,6 +44,11 @@ def _grouped_not_mixed(groups):
                                'precision) has no grouped convolution' % groups)
 
 
+def _dilated_not_mixed(dilations):
+    return NotImplementedError('a dilated backbone (dilations=%r) runs in the fp32 compute mode only: the bf16 compute mode (mixed '
+                               'precision) has no dilated convolution' % (tuple(dilations),))
+
+
 def block_width(planes, groups=1, base_width=4, base_channels=64):
     """Channels of a bottleneck's conv1 output / conv2 (T/mmdet/models/backbones/resnext.py:28-32): ``planes`` for a ResNet,
     floor(planes * base_width / base_channels) * groups for a ResNeXt."""
@@ -56,9 +64,12 @@ def _bn_not_mixed():
 
 class _Block(nn.Module):
     def __init__(self, kind, inplanes, planes, stride, downsample, norm=nn.BatchNorm2d, style='pytorch', groups=1, base_width=4,
-                 base_channels=64):
+                 base_channels=64, dilation=1):
         super().__init__()
         self.kind = kind
+        # every block of a dilated stage: the 3x3 that carries the stride slot -- bottleneck conv2, BasicBlock conv1 -- runs at
+        # padding = dilation (resnet.py:36-47, 175-200; resnext.py:55-75); BasicBlock conv2 stays padding 1 / dilation 1
+        d = dilation
         assert groups == 1 or kind == 'bottleneck', 'grouped blocks are bottlenecks (resnext.py:11)'
         if kind == 'bottleneck':  # style='pytorch': the stride sits on the 3x3, 'caffe': on the first 1x1 (resnet.py:153-158)
             s1, s2 = (1, stride) if style == 'pytorch' else (stride, 1)
@@ -67,12 +78,12 @@ class _Block(nn.Module):
             width = block_width(planes, groups, base_width, base_channels)
             self.conv1 = nn.Conv2d(inplanes, width, 1, s1, bias=False)
             self.bn1 = norm(width)
-            self.conv2 = nn.Conv2d(width, width, 3, s2, 1, groups=groups, bias=False)
+            self.conv2 = nn.Conv2d(width, width, 3, s2, d, dilation=d, groups=groups, bias=False)
             self.bn2 = norm(width)
             self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
             self.bn3 = norm(planes * 4)
         else:
-            self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
+            self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, d, dilation=d, bias=False)
             self.bn1 = norm(planes)
             self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
             self.bn2 = norm(planes)
@@ -220,7 +231,13 @@ class ResNet(nn.Module):
             raise KeyError('invalid depth %s for resnet' % depth)
         assert style in ('pytorch', 'caffe'), style
         assert dcn is None and plugins is None and not with_cp, 'dcn, plugins and with_cp are not built (SURVEY.md §2a row 5)'
-        assert tuple(dilations[:num_stages]) == (1,) * num_stages
+        assert len(strides) >= num_stages and len(dilations) >= num_stages
+        self.strides, self.dilations = tuple(strides[:num_stages]), tuple(int(d) for d in dilations[:num_stages])
+        for i, (s, d) in enumerate(zip(self.strides, self.dilations)):
+            # a dilated stage keeps its resolution: the data gradient of a strided dilated 3x3 (zero insertion at a dilated extent) is
+            # not built, and no shipped config asks for it (DC5: strides (1, 2, 2, 1), dilations (1, 1, 1, 2))
+            assert d >= 1 and (d == 1 or s == 1), \
+                'stage %d: dilations[%d]=%d needs strides[%d]=1, got strides=%r dilations=%r' % (i + 1, i, d, i, self.strides, self.dilations)
         if norm_cfg.get('type') not in ('BN', 'SyncBN'):
             raise NotImplementedError("norm_cfg type %r is not built: the backbone norms are 'BN' (nn.BatchNorm2d) or 'SyncBN' "
                                       "(nn.SyncBatchNorm)" % (norm_cfg.get('type'),))
@@ -268,7 +285,8 @@ class ResNet(nn.Module):
                                            nn.Conv2d(inplanes, planes * exp, 1, 1, bias=False), norm(planes * exp))
                     else:
                         ds = nn.Sequential(nn.Conv2d(inplanes, planes * exp, 1, stride, bias=False), norm(planes * exp))
-                layer.append(self._make_block(kind, inplanes, planes, stride, ds, norm, style, base_channels, first=bi == 0))
+                layer.append(self._make_block(kind, inplanes, planes, stride, ds, norm, style, base_channels, first=bi == 0,
+                                              dilation=self.dilations[i]))
                 inplanes = planes * exp
             name = 'layer%d' % (i + 1)
             self.add_module(name, nn.Sequential(*layer))
@@ -280,9 +298,9 @@ class ResNet(nn.Module):
         self.init_weights()
         self._freeze_stages()
 
-    def _make_block(self, kind, inplanes, planes, stride, downsample, norm, style, base_channels, first):
+    def _make_block(self, kind, inplanes, planes, stride, downsample, norm, style, base_channels, first, dilation=1):
         """One residual block of a stage (``first``: its first block); Res2Net builds its own kind."""
-        return _Block(kind, inplanes, planes, stride, downsample, norm, style, self.groups, self.base_width, base_channels)
+        return _Block(kind, inplanes, planes, stride, downsample, norm, style, self.groups, self.base_width, base_channels, dilation)
 
     def _freeze_stages(self):  # resnet.py:612-628
         if self.frozen_stages >= 0:
@@ -321,9 +339,14 @@ class ResNet(nn.Module):
     def stem_parameters(self):
         return list(self.stem.parameters()) if self.deep_stem else list(self.conv1.parameters()) + list(self.bn1.parameters())
 
+    def dilated(self):
+        return any(d != 1 for d in self.dilations)
+
     def _check_mode(self):
         if self.compute_dtype != torch.float32 and self.groups > 1:
             raise _grouped_not_mixed(self.groups)
+        if self.compute_dtype != torch.float32 and self.dilated():
+            raise _dilated_not_mixed(self.dilations)
         if self.compute_dtype != torch.float32 and self.batch_stats_active():
             raise _bn_not_mixed()
 

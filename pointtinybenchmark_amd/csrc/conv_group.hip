@@ -24,6 +24,10 @@
 // threads of the pad quads take no part in the sums, so NaN there changes no output bit -- and the pad channels of the output are
 // written as +0.0 by the kernel itself.  The pack, the workspace and the parameter gradient know nothing of the pitch.  Cp == C with
 // one of the widths 4 / 8 / 16 / 32 launches the instances without the pitch argument, as before.
+//
+// Dilation (a dilated ResNeXt stage: stride 1, padding d, tap step d): the DIL instances start at ih0 = oh - d and step d pixels per tap;
+// nothing else changes -- 9 * cg FMAs per output in the same tap-major order, so the bit-repeatability and batch independence above hold.
+// Unpitched maps only.  The tap step is a compile-time 1 in every other instance.
 #include "common.h"
 
 namespace {
@@ -75,12 +79,14 @@ __global__ void pack_group_multi_kernel(const GroupPackJob* __restrict__ jobs, i
     pack_group_body(j.w, j.scale, j.out, j.C, j.cg, j.transpose, (int)blockIdx.x - j.block0, j.nblocks);
 }
 
-template <int CG, bool PITCH>
+template <int CG, bool PITCH, bool DIL = false>
 __global__ __launch_bounds__(256) void conv_group_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wp,
                                                              float* __restrict__ out, const float* __restrict__ scale,
                                                              const float* __restrict__ bias, long long M, int H, int W, int OH, int OW,
-                                                             int C, int pitch, int stride, int relu) {
+                                                             int C, int pitch, int stride, int relu, int dil) {
+    static_assert(!(DIL && PITCH), "the dilated instances read unpitched maps");
     constexpr int CH = CG / 4, UNR = CH > 2 ? 2 : CH;
+    const int dl = DIL ? dil : 1;                     // tap step = padding
     const int C4 = C >> 2;                            // quads of the pack: the real channels
     const int Cp = PITCH ? pitch : C;                 // floats between the pixels of x and of out
     const int Q = Cp >> 2;
@@ -107,8 +113,8 @@ __global__ __launch_bounds__(256) void conv_group_fwd_kernel(const float* __rest
         const long long t = q / OW;
         const int oh = (int)(t % OH);
         const long long n = t / OH;
-        ih0[i] = oh * stride - 1;
-        iw0[i] = ow * stride - 1;
+        ih0[i] = oh * stride - dl;
+        iw0[i] = ow * stride - dl;
         xb[i] = x + (size_t)n * H * W * Cp + g0;
     }
     f32x4 acc[GC_PX];
@@ -122,7 +128,7 @@ __global__ __launch_bounds__(256) void conv_group_fwd_kernel(const float* __rest
         bool ok[GC_PX];
 #pragma unroll
         for (int i = 0; i < GC_PX; ++i) {
-            const int ih = ih0[i] + kh, iw = iw0[i] + kw;
+            const int ih = ih0[i] + kh * dl, iw = iw0[i] + kw * dl;
             ok[i] = live[i] && ih >= 0 && ih < H && iw >= 0 && iw < W;
             src[i] = xb[i] + ((size_t)(ok[i] ? ih : 0) * W + (ok[i] ? iw : 0)) * Cp;
         }
@@ -172,10 +178,12 @@ static inline WgPlan wg_plan(long long M, int C, int cg) {
     return pl;
 }
 
-template <bool PITCH>
+template <bool PITCH, bool DIL = false>
 __global__ __launch_bounds__(256, 2) void conv_group_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                float* __restrict__ ws, long long M, int H, int W, int OH, int OW, int C,
-                                                               int pitch, int cg, int stride, int T, int S, long long P) {
+                                                               int pitch, int cg, int stride, int T, int S, long long P, int dil) {
+    static_assert(!(DIL && PITCH), "the dilated instance reads unpitched maps");
+    const int dl = DIL ? dil : 1;                     // tap step = padding
     const int C4 = C >> 2;
     const int Cp = PITCH ? pitch : C;                 // floats between the pixels of dy and of x; the threads cover real channels only
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -199,10 +207,10 @@ __global__ __launch_bounds__(256, 2) void conv_group_wgrad_kernel(const float* _
     for (long long p = pbeg; p < pend; ++p) {
         const f32x4 d = ldg4(dy + (size_t)p * Cp + co0);
         const float* xn = x + (size_t)n * H * W * Cp + ci0;
-        const int ihb = oh * stride - 1, iwb = ow * stride - 1;
+        const int ihb = oh * stride - dl, iwb = ow * stride - dl;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            const int ih = ihb + tap / 3, iw = iwb + tap % 3;
+            const int ih = ihb + (tap / 3) * dl, iw = iwb + (tap % 3) * dl;
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
             if (ih >= 0 && ih < H && iw >= 0 && iw < W) v = ldg4(xn + ((size_t)ih * W + iw) * Cp);
             f32x4* a = acc[tap];
@@ -249,7 +257,8 @@ inline bool group_pitch_ok(int C, int Cp) { return Cp >= C && Cp % 4 == 0 && Cp 
 inline bool group_plain(int C, int Cp, int cg) { return Cp == C && (cg == 4 || cg == 8 || cg == 16 || cg == 32); }
 
 int group_fwd(const float* x, const float* wp, float* out, const float* scale, const float* bias, int N, int H, int W, int C, int Cp,
-              int cg, int stride, int flags, hipStream_t stream) {
+              int cg, int stride, int flags, hipStream_t stream, int dil = 1) {
+    CPR_CHECK_ARG(dil >= 1 && (dil == 1 || (stride == 1 && Cp == C)));      // dilated: stride 1 (OH = H with padding dil), unpitched
     CPR_CHECK_ARG(x && wp && out && N > 0 && H > 0 && W > 0 && group_shape_ok(C, cg) && group_pitch_ok(C, Cp) &&
                   (stride == 1 || stride == 2));
     CPR_CHECK_ARG((flags & ~CPR_CONV_RELU) == 0);      // no residual, no GroupNorm statistics, no bf16 output: ReLU is the only flag
@@ -260,8 +269,23 @@ int group_fwd(const float* x, const float* wp, float* out, const float* scale, c
     const int relu = flags & CPR_CONV_RELU;
 #define GC_LAUNCH(CG, PITCH)                                                                                                       \
     hipLaunchKernelGGL((conv_group_fwd_kernel<CG, PITCH>), dim3((unsigned)blocks), dim3(256), 0, stream, x, wp, out, scale, bias, M, H, \
-                       W, OH, OW, C, Cp, stride, relu)
-    if (group_plain(C, Cp, cg)) {
+                       W, OH, OW, C, Cp, stride, relu, dil)
+    if (dil > 1) {
+#define GC_LAUNCH_DIL(CG)                                                                                                          \
+    hipLaunchKernelGGL((conv_group_fwd_kernel<CG, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, x, wp, out, scale, bias, \
+                       M, H, W, OH, OW, C, Cp, stride, relu, dil)
+        switch (cg) {
+            case 4: GC_LAUNCH_DIL(4); break;
+            case 8: GC_LAUNCH_DIL(8); break;
+            case 16: GC_LAUNCH_DIL(16); break;
+            case 24: GC_LAUNCH_DIL(24); break;
+            case 32: GC_LAUNCH_DIL(32); break;
+            case 40: GC_LAUNCH_DIL(40); break;
+            case 48: GC_LAUNCH_DIL(48); break;
+            default: GC_LAUNCH_DIL(56); break;
+        }
+#undef GC_LAUNCH_DIL
+    } else if (group_plain(C, Cp, cg)) {
         switch (cg) {
             case 4: GC_LAUNCH(4, false); break;
             case 8: GC_LAUNCH(8, false); break;
@@ -319,7 +343,8 @@ extern "C" int cpr_conv_group_wgrad_workspace(int N, int OH, int OW, int C, int 
 }
 
 static int group_wgrad(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int Cp, int cg, int stride,
-                       int accumulate, hipStream_t stream) {
+                       int accumulate, hipStream_t stream, int dil = 1) {
+    CPR_CHECK_ARG(dil >= 1 && (dil == 1 || (stride == 1 && Cp == C)));
     CPR_CHECK_ARG(dy && x && grad_w && ws && N > 0 && H > 0 && W > 0 && group_shape_ok(C, cg) && group_pitch_ok(C, Cp) &&
                   (stride == 1 || stride == 2));
     const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
@@ -327,12 +352,15 @@ static int group_wgrad(const float* dy, const float* x, float* grad_w, float* ws
     const WgPlan pl = wg_plan(M, C, cg);
     if ((long long)pl.S * pl.T * 144 >= (1ll << 31)) return CPR_ERR_UNSUPPORTED;
     const long long threads = (long long)pl.S * pl.T;
-    if (Cp == C)
+    if (dil > 1)
+        hipLaunchKernelGGL((conv_group_wgrad_kernel<false, true>), dim3((unsigned)cdivll(threads, 256)), dim3(256), 0, stream, dy, x, ws, M,
+                           H, W, OH, OW, C, Cp, cg, stride, pl.T, pl.S, pl.P, dil);
+    else if (Cp == C)
         hipLaunchKernelGGL(conv_group_wgrad_kernel<false>, dim3((unsigned)cdivll(threads, 256)), dim3(256), 0, stream, dy, x, ws, M, H, W,
-                           OH, OW, C, Cp, cg, stride, pl.T, pl.S, pl.P);
+                           OH, OW, C, Cp, cg, stride, pl.T, pl.S, pl.P, 1);
     else
         hipLaunchKernelGGL(conv_group_wgrad_kernel<true>, dim3((unsigned)cdivll(threads, 256)), dim3(256), 0, stream, dy, x, ws, M, H, W,
-                           OH, OW, C, Cp, cg, stride, pl.T, pl.S, pl.P);
+                           OH, OW, C, Cp, cg, stride, pl.T, pl.S, pl.P, 1);
     hipLaunchKernelGGL(conv_group_wgrad_reduce_kernel, dim3(cdiv(144 * pl.T, 256)), dim3(256), 0, stream, ws, grad_w, C, cg, pl.T, pl.S,
                        accumulate);
     CPR_LAUNCH_STATUS();
@@ -346,4 +374,16 @@ extern "C" int cpr_conv_group_wgrad(const float* dy, const float* x, float* grad
 extern "C" int cpr_conv_group_wgrad_pitch(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int Cp,
                                           int cg, int stride, int accumulate, hipStream_t stream) {
     return group_wgrad(dy, x, grad_w, ws, N, H, W, C, Cp, cg, stride, accumulate, stream);
+}
+
+// Dilated grouped 3x3 (stride 1, padding = tap step = dil >= 1, unpitched maps; a dilated ResNeXt stage): forward -- and, with the
+// data-gradient pack over dy, the data gradient -- and weight gradient.  Same packs, same workspace query, same accumulation order as
+// the undilated entries; dil == 1 launches exactly what they launch.
+extern "C" int cpr_conv_group_fwd_dil(const float* x, const float* wp, float* out, const float* scale, const float* bias, int N, int H,
+                                      int W, int C, int cg, int dil, int flags, hipStream_t stream) {
+    return group_fwd(x, wp, out, scale, bias, N, H, W, C, C, cg, 1, flags, stream, dil);
+}
+extern "C" int cpr_conv_group_wgrad_dil(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int cg,
+                                        int dil, int accumulate, hipStream_t stream) {
+    return group_wgrad(dy, x, grad_w, ws, N, H, W, C, C, cg, 1, accumulate, stream, dil);
 }

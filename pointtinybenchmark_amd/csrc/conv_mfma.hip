@@ -47,6 +47,7 @@ struct ConvParams {
     const float* scale2;    // [Cout] or null
     const float* bias2;     // [Cout] or null
     int H2, W2, Cin2, stride2, Kpad2;
+    int dil;                // tap step in pixels (DIL instances only; the others never read it)
 };
 
 constexpr int BK = 32;
@@ -56,9 +57,12 @@ constexpr int LDSW = 36;  // padded row (floats)
 // XF: fused per-(image, channel) affine (+ReLU) on the input = GroupNorm-apply of the producing layer.
 // ABL (benchmark-only ablations of the pipelined loop, results are then WRONG): bit0 = no global loads / LDS writes,
 // bit1 = no fragment reads, bit2 = no barrier.  ABL = 0 in every product launch.
-template <int BM, int BN, int MODE, bool XF, int PIPE, int ABL = 0, bool DUAL = false>
+// DIL: dilated taps (3x3 / stride 1 / pad == dil: tap (kh, kw) reads pixel (oy + (kh - 1) dil, ox + (kw - 1) dil)); the tap step is a
+// compile-time 1 in every other instance, which therefore compiles to what it compiled to without the flag.
+template <int BM, int BN, int MODE, bool XF, int PIPE, int ABL = 0, bool DUAL = false, bool DIL = false>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvParams p) {
     static_assert(!DUAL || (MODE == 0 && !XF && PIPE == 1 && ABL == 0), "the dual-source form exists for the plain pipelined instances");
+    static_assert(!DIL || (MODE == 0 && !XF && PIPE == 1 && ABL == 0 && !DUAL), "the dilated form exists for the plain pipelined instances");
     constexpr int WM = BM / 2;
     constexpr int WN = BN / 2;
     constexpr int MI = WM / 32;
@@ -162,10 +166,11 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvParams p) {
         okcur = 0;
         // the tap's pixel shift goes into the VECTOR offset (it must be a valid non-negative offset by itself: the
         // hardware range check looks at the vector offset only); the channel chunk is the scalar offset
-        const int tapshift = (kh * p.W + kw) * p.Cin;
+        const int dl = DIL ? p.dil : 1;
+        const int tapshift = (kh * dl * p.W + kw * dl) * p.Cin;
 #pragma unroll
         for (int j = 0; j < AL; ++j) {
-            const int iy = iy0[j] + kh, ix = ix0[j] + kw;
+            const int iy = iy0[j] + kh * dl, ix = ix0[j] + kw * dl;
             const bool ok = mok[j] & ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
             okcur |= (ok ? 1u : 0u) << j;
             voffA[j] = ok ? (rowoff[j] + tapshift) * 4 : -1;
@@ -585,8 +590,9 @@ constexpr int STREAM_MIN_TILES = 1024;   // four tiles per persistent workgroup;
 static int conv2d_fwd_launch(const float* in, const float* wgt, float* out, const float* scale, const float* bias,
                              const float* residual, const float* in_a, const float* in_b, float* gn_part, int N,
                              int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int Kpad,
-                             int flags, int in_relu, int bm_fix, int* variant_out, hipStream_t stream) {
+                             int flags, int in_relu, int bm_fix, int* variant_out, hipStream_t stream, int dil = 1) {
     CPR_CHECK_ARG(in && wgt && out);
+    CPR_CHECK_ARG(dil >= 1);
     CPR_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0);
     CPR_CHECK_ARG(Kpad % BK == 0);
     ConvParams p;
@@ -597,10 +603,14 @@ static int conv2d_fwd_launch(const float* in, const float* wgt, float* out, cons
     p.Kpad = Kpad; p.relu = flags & CPR_CONV_RELU; p.in_relu = in_relu; p.out_bf16 = (flags & CPR_CONV_OUT_BF16) ? 1 : 0;
     p.res_mask = (flags & CPR_CONV_RES_MASK) ? 1 : 0;
     p.in2 = nullptr; p.wgt2 = nullptr; p.scale2 = nullptr; p.bias2 = nullptr; p.H2 = p.W2 = p.Cin2 = p.stride2 = p.Kpad2 = 0;
+    p.dil = dil;
+    if (dil > 1)   // the dilated instances: 3x3 'same' layers, plain epilogue operands (cpr_conv2d_fwd_dil)
+        CPR_CHECK_ARG(KH == 3 && KW == 3 && stride == 1 && pad == dil && Cin % BK == 0 && !in_a && !in_b &&
+                      (!gn_part || (flags & CPR_CONV_COLSUM)) && !(flags & CPR_CONV_OUT_BF16));
     const bool colsum_mode = (flags & CPR_CONV_COLSUM) != 0;   // gn_part partials are only summed over the whole tensor (any tile)
     if (p.res_mask) CPR_CHECK_ARG(residual != nullptr);
-    p.OH = (H + 2 * pad - KH) / stride + 1;
-    p.OW = (W + 2 * pad - KW) / stride + 1;
+    p.OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
+    p.OW = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
     CPR_CHECK_ARG(p.OH > 0 && p.OW > 0);
     long long M = (long long)N * p.OH * p.OW;
     // 32-bit byte offsets inside the buffer descriptors: < 2 GiB per tensor (B=64 at 160x160x256 is 1.7 GB)
@@ -670,7 +680,13 @@ static int conv2d_fwd_launch(const float* in, const float* wgt, float* out, cons
         }
     } else
 #endif
-    if (mode1) {
+    if (dil > 1) {
+#define LAUNCH_DIL(BM_, BN_) \
+    hipLaunchKernelGGL((conv_mfma_kernel<BM_, BN_, 0, false, 1, 0, false, true>), dim3(grid), dim3(256), 0, stream, p)
+        if (bm == 128) { if (bn == 64) LAUNCH_DIL(128, 64); else LAUNCH_DIL(128, 128); }
+        else { if (bn == 64) LAUNCH_DIL(64, 64); else LAUNCH_DIL(64, 128); }
+#undef LAUNCH_DIL
+    } else if (mode1) {
         if (bn == 64) LAUNCH(128, 64, 1, false); else LAUNCH(128, 128, 1, false);
     } else if (in_a) {
         if (bn == 64) LAUNCH(128, 64, 0, true); else LAUNCH(128, 128, 0, true);
@@ -713,6 +729,43 @@ extern "C" int cpr_conv2d_fwd(const float* in, const float* wgt, float* out, con
                                          Kpad, flags, in_relu, bm_fix, &variant, stream);
         if (rc != CPR_OK) return rc;
         // only the column-sum slots tie later chunks to the first chunk's M tile (never a streamed launch: those carry no partials)
+        if (n0 == 0) { if (flags & CPR_CONV_COLSUM) bm_fix = variant / 1000000; if (variant_out) *variant_out = variant; }
+    }
+    return CPR_OK;
+}
+
+// ---- dilated 3x3: out = epilogue(conv(in, wgt; stride 1, pad = dil, tap step dil)) ---------------------------------------------
+// The conv2 of a dilated ResNet stage (T/mmdet/models/backbones/resnet.py:36-47, 175-200) and, over dy with the flipped pack, its data
+// gradient (pad 2 dil - dil = dil: the same geometry).  The weight pack is the dense [Cout][Kpad] image of cpr_conv2d_fwd; dil == 1
+// launches exactly what cpr_conv2d_fwd launches.  No Winograd, streamed or dual form; the fused input affine, the GroupNorm partials and
+// the bf16 output have no dilated instance (CPR_ERR_ARG before any launch).
+extern "C" int cpr_conv2d_fwd_dil(const float* in, const float* wgt, float* out, const float* scale, const float* bias,
+                                  const float* residual, const float* in_a, const float* in_b, float* gn_part, int N, int H,
+                                  int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil, int Kpad, int flags,
+                                  int in_relu, int* variant_out, hipStream_t stream) {
+    CPR_CHECK_ARG(dil >= 1);
+    if (dil == 1)
+        return cpr_conv2d_fwd(in, wgt, out, scale, bias, residual, in_a, in_b, gn_part, N, H, W, Cin, Cout, KH, KW, stride, pad, Kpad,
+                              flags, in_relu, variant_out, stream);
+    CPR_CHECK_ARG(in && wgt && out && N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0);
+    CPR_CHECK_ARG(KH == 3 && KW == 3 && stride == 1 && pad == dil && Cin % BK == 0 && Kpad == 9 * Cin);
+    CPR_CHECK_ARG(!in_a && !in_b && in_relu == 0 && (flags & ~15) == 0 && !(flags & CPR_CONV_OUT_BF16));
+    CPR_CHECK_ARG(!gn_part == !(flags & CPR_CONV_COLSUM));   // partials are column sums or nothing
+    if ((flags & CPR_CONV_RES_MASK)) CPR_CHECK_ARG(residual != nullptr);
+    const long long img = (long long)H * W * (Cin > Cout ? Cin : Cout) * 4;   // OH == H, OW == W
+    int align = 1;
+    if (flags & CPR_CONV_COLSUM) { const long long r = (long long)H * W; while ((r * align) % 128 != 0) align *= 2; }
+    const int per = cpr_images_per_launch(N, img, align);
+    if (per <= 0) return CPR_ERR_UNSUPPORTED;
+    int bm_fix = 0, variant = 0;
+    for (int n0 = 0; n0 < N; n0 += per) {
+        const int n = N - n0 < per ? N - n0 : per;
+        const size_t rows = (size_t)n0 * H * W;
+        float* part = gn_part ? gn_part + (bm_fix ? rows / bm_fix : 0) * Cout * 2 : nullptr;
+        const int rc = conv2d_fwd_launch(in + rows * Cin, wgt, out + rows * Cout, scale, bias, residual ? residual + rows * Cout : nullptr,
+                                         nullptr, nullptr, part, n, H, W, Cin, Cout, 3, 3, 1, pad, Kpad, flags, 0, bm_fix, &variant,
+                                         stream, dil);
+        if (rc != CPR_OK) return rc;
         if (n0 == 0) { if (flags & CPR_CONV_COLSUM) bm_fix = variant / 1000000; if (variant_out) *variant_out = variant; }
     }
     return CPR_OK;

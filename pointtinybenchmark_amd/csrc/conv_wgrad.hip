@@ -17,6 +17,7 @@ struct WgradParams {
     float* part;       // [S][Cout][KH*KW][Cin]
     int N, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, M, in_relu;
     int tilesCo, tilesCi, S, chunks_per_slab;
+    int dil;           // tap step in pixels (DIL instances only; the others never read it)
 };
 
 constexpr int WG_BK = 32;     // pixels per chunk
@@ -34,8 +35,12 @@ constexpr int WG_LD = 132;    // LDS row stride in floats (132 = 128 + 4 keeps f
 //      masks need the pixel's (ox, oy)
 //   0  general (strided): full input-coordinate tracking
 //  -1  images with fewer than 32 output pixels (unit-test sizes): decode from scratch every chunk
-template <bool XF, int ABL = 0, int GEO = 0>
+// DIL: dilated taps -- tap (kh, kw) reads the input at (oy s + kh dil - pad, ox s + kw dil - pad).  Only the general classes (0, -1)
+// have the form: they track the input coordinates themselves, so the tap offset enters in decode_row alone and the per-chunk advance
+// (a function of the stride) is unchanged.  The tap step is a compile-time 1 in every other instance.
+template <bool XF, int ABL = 0, int GEO = 0, bool DIL = false>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p) {
+    static_assert(!DIL || (GEO <= 0 && !XF && ABL == 0), "dilated taps: the general geometry classes of the plain kernel");
     __shared__ __attribute__((aligned(16))) float smem[2 * 2 * WG_BK * WG_LD];
     float* As = smem;                         // [2][32][132]  dY tile (k = pixel, i = cout)
     float* Bs = smem + 2 * WG_BK * WG_LD;     // [2][32][132]  X tile  (k = pixel, j = cin)
@@ -82,7 +87,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p) {
     const int bX0 = dX0 * pxb, bX1 = dX1 * pxb, bY0 = dY0 * rowb, bY1 = dY1 * rowb;
     const int bN = (p.H - dYw) * rowb;                              // image wrap: +H rows, -OH*stride rows
     const int va_step = WG_BK * p.Cout * 4, vb_step = WG_BK * pxb;
-    const int dkh = kh - p.pad, dkw = kw - p.pad;
+    const int dl = DIL ? p.dil : 1;
+    const int dkh = kh * dl - p.pad, dkw = kw * dl - p.pad;
     int rm[4], rox[4], roy[4], rix[4], riy[4], va[4], vb[4], vt[4];
     auto decode_row = [&](int j) {
         const int m = rm[j];
@@ -90,8 +96,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p) {
         const int rem = m - n * ohw;
         roy[j] = rem / p.OW;
         rox[j] = rem - roy[j] * p.OW;
-        riy[j] = roy[j] * p.stride + kh - p.pad;
-        rix[j] = rox[j] * p.stride + kw - p.pad;
+        riy[j] = roy[j] * p.stride + dkh;
+        rix[j] = rox[j] * p.stride + dkw;
         va[j] = m * p.Cout * 4 + cho;
         vb[j] = ((n * p.H + riy[j]) * p.W + rix[j]) * pxb + chi;
         vt[j] = n * pxb + chi;
@@ -386,17 +392,18 @@ extern "C" int cpr_conv2d_wgrad_workspace(int N, int OH, int OW, int Cin, int Co
 
 static int conv2d_wgrad_launch(const float* dy, const float* x, const float* in_a, const float* in_b, float* grad_w,
                                float* ws, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
-                               int in_relu, int accumulate, hipStream_t stream) {
+                               int in_relu, int accumulate, hipStream_t stream, int dil = 1) {
     CPR_CHECK_ARG(dy && x && grad_w && ws);
+    CPR_CHECK_ARG(dil >= 1 && (dil == 1 || !in_a));
     CPR_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0);
     CPR_CHECK_ARG(Cin % 4 == 0 && Cout % 4 == 0);
     if (in_a) CPR_CHECK_ARG(in_b != nullptr);
     WgradParams p;
     p.dy = dy; p.x = x; p.in_a = in_a; p.in_b = in_b; p.part = ws;
     p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
-    p.in_relu = in_relu;
-    p.OH = (H + 2 * pad - KH) / stride + 1;
-    p.OW = (W + 2 * pad - KW) / stride + 1;
+    p.in_relu = in_relu; p.dil = dil;
+    p.OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
+    p.OW = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
     CPR_CHECK_ARG(p.OH > 0 && p.OW > 0);
     const long long M = (long long)N * p.OH * p.OW;
     if (M * Cout * 4 >= (1ll << 31) || (long long)N * H * W * Cin * 4 >= (1ll << 31)) return CPR_ERR_UNSUPPORTED;
@@ -426,7 +433,10 @@ static int conv2d_wgrad_launch(const float* dy, const float* x, const float* in_
         }
     } else
 #endif
-    if (in_a) {
+    if (dil > 1) {   // the general classes: the 'same' class derives its border masks and its linear addresses from a tap step of 1
+        if (geo == -1) hipLaunchKernelGGL((conv_wgrad_kernel<false, 0, -1, true>), dim3((unsigned)grid), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((conv_wgrad_kernel<false, 0, 0, true>), dim3((unsigned)grid), dim3(256), 0, stream, p);
+    } else if (in_a) {
         if (geo == 2) WG_LAUNCH(true, 0, 2); else if (geo == 1) WG_LAUNCH(true, 0, 1);
         else if (geo == 0) WG_LAUNCH(true, 0, 0); else WG_LAUNCH(true, 0, -1);
     } else {
@@ -456,6 +466,27 @@ extern "C" int cpr_conv2d_wgrad(const float* dy, const float* x, const float* in
                                            in_a ? in_a + (size_t)n0 * Cin : nullptr, in_b ? in_b + (size_t)n0 * Cin : nullptr,
                                            grad_w, ws, n, H, W, Cin, Cout, KH, KW, stride, pad, in_relu,
                                            n0 == 0 ? accumulate : 1, stream);
+        if (rc != CPR_OK) return rc;
+    }
+    return CPR_OK;
+}
+
+// The same weight gradient with dilated taps (tap step dil >= 1; OH = (H + 2 pad - dil (KH - 1) - 1) / stride + 1): the conv2 of a dilated
+// ResNet stage.  No fused input affine.  Workspace: cpr_conv2d_wgrad_workspace of the same shapes; the slabs are summed in the same fixed
+// order, no atomics.  dil == 1 launches exactly what cpr_conv2d_wgrad launches.
+extern "C" int cpr_conv2d_wgrad_dil(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int Cin, int Cout,
+                                    int KH, int KW, int stride, int pad, int dil, int accumulate, hipStream_t stream) {
+    CPR_CHECK_ARG(dil >= 1);
+    if (dil == 1) return cpr_conv2d_wgrad(dy, x, nullptr, nullptr, grad_w, ws, N, H, W, Cin, Cout, KH, KW, stride, pad, 0, accumulate, stream);
+    CPR_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0);
+    CPR_CHECK_ARG(H + 2 * pad - dil * (KH - 1) - 1 >= 0 && W + 2 * pad - dil * (KW - 1) - 1 >= 0);
+    const int OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, OW = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+    const int per = cpr_images_per_launch(N, cpr_max2((long long)OH * OW * Cout * 4, (long long)H * W * Cin * 4));
+    if (per <= 0) return CPR_ERR_UNSUPPORTED;
+    for (int n0 = 0; n0 < N; n0 += per) {
+        const int n = N - n0 < per ? N - n0 : per;
+        const int rc = conv2d_wgrad_launch(dy + (size_t)n0 * OH * OW * Cout, x + (size_t)n0 * H * W * Cin, nullptr, nullptr, grad_w, ws, n,
+                                           H, W, Cin, Cout, KH, KW, stride, pad, 0, n0 == 0 ? accumulate : 1, stream, dil);
         if (rc != CPR_OK) return rc;
     }
     return CPR_OK;

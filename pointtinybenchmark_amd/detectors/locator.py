@@ -37,6 +37,10 @@ class BasicLocator(nn.Module):
         if dt != torch.float32 and groups > 1:
             raise NotImplementedError('a grouped backbone (ResNeXt groups=%d) runs in the fp32 compute mode only: the bf16 compute mode '
                                       'has no grouped convolution' % groups)
+        dilations = tuple(getattr(self.backbone, 'dilations', ()))
+        if dt != torch.float32 and any(d != 1 for d in dilations):
+            raise NotImplementedError('a dilated backbone (dilations=%r) runs in the fp32 compute mode only: the bf16 compute mode has no '
+                                      'dilated convolution' % (dilations,))
         scales = getattr(self.backbone, 'scales', 0)
         if dt != torch.float32 and scales:
             raise NotImplementedError('a Res2Net backbone (scales=%d) runs in the fp32 compute mode only: the bf16 compute mode has no '

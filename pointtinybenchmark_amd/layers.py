@@ -195,7 +195,8 @@ class _PackCache:
 
 def packed_conv(cache, conv, dtype=torch.float32):
     return cache.get(('pc', id(conv), dtype), [conv.weight],
-                     lambda: ops.PackedConv(conv.weight, conv.stride[0], conv.padding[0], dtype, groups=conv.groups),
+                     lambda: ops.PackedConv(conv.weight, conv.stride[0], conv.padding[0], dtype, groups=conv.groups,
+                                            dilation=conv.dilation[0]),
                      lambda pc: _pack_job(pc, conv.weight))
 
 
@@ -240,7 +241,7 @@ def dgrad_packed(cache, conv, bn=None, dtype=torch.float32, pitch=None):
     """The packed weights of the data gradient of ``conv`` (ops.dgrad_pack; bf16 stride 1: PackedConv.for_dgrad_bf16) with the
     folded scale of the eval-mode ``bn`` multiplied in -- or the raw weights (bn None: a batch-statistics layer).  pitch (a grouped
     layer with eval-mode ``bn``): the channel pitch of its gradient maps."""
-    w, stride, pad = conv.weight, conv.stride[0], conv.padding[0]
+    w, stride, pad, dil = conv.weight, conv.stride[0], conv.padding[0], conv.dilation[0]
     if pitch is not None and pitch != w.shape[0]:
         assert bn is not None and conv.groups > 1 and dtype == torch.float32
 
@@ -253,13 +254,13 @@ def dgrad_packed(cache, conv, bn=None, dtype=torch.float32, pitch=None):
             return None if fold is None else _pack_job(pc, w, 1, fold)
         return cache.get(('dgrad', id(conv), dtype, pitch), [w, bn.weight, bn.running_var], make_p, job_p)
     if bn is None:
-        return cache.get(('dgrad_raw', id(conv)), [w], lambda: ops.dgrad_pack(w, stride, pad, groups=conv.groups),
+        return cache.get(('dgrad_raw', id(conv)), [w], lambda: ops.dgrad_pack(w, stride, pad, groups=conv.groups, dilation=dil),
                          lambda pc: _pack_job(pc, w, 1))
 
     def make():
         scale, _ = folded_bn(cache, bn)
-        if dtype == torch.float32 or stride != 1 or conv.groups > 1:
-            return ops.dgrad_pack(w, stride, pad, scale=scale, dtype=dtype, groups=conv.groups)
+        if dtype == torch.float32 or stride != 1 or conv.groups > 1 or dil != 1:
+            return ops.dgrad_pack(w, stride, pad, scale=scale, dtype=dtype, groups=conv.groups, dilation=dil)
         return ops.PackedConv.for_dgrad_bf16(w, pad, scale=scale)
 
     def job(pc):        # linked to the fold job of the scale make() multiplied in

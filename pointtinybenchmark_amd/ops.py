@@ -120,18 +120,29 @@ class PackedConv:
     groups = 1      # > 1: a grouped 3x3 layer (ResNeXt conv2) in the layout of csrc/conv_group.hip, see _init_grouped
     cg = None       # ... its group width (channels per group)
     C = None        # ... its real channels; Cin = Cout = the pitch of the maps it reads and writes (>= C, RegNet)
+    dilation = 1    # > 1: a dilated 3x3 / stride 1 / padding == dilation layer (fp32; cpr_conv2d_fwd_dil, cpr_conv_group_fwd_dil)
 
     def _packed(self):
         """A pack kernel was just enqueued on the current stream: consumers on OTHER streams (CPR_STREAMS > 1 sub-batches)
         must order themselves behind it."""
         self.ready = record_ready()
 
-    def __init__(self, weight, stride=1, padding=0, dtype=torch.float32, groups=1, pitch=None):
+    def __init__(self, weight, stride=1, padding=0, dtype=torch.float32, groups=1, pitch=None, dilation=1):
+        dilation = int(dilation)
+        assert dilation >= 1, 'dilation must be >= 1, got %d' % dilation
+        if dilation != 1 and dtype == torch.bfloat16:
+            raise NotImplementedError('dilation=%d: a dilated convolution runs in the fp32 compute mode only (the bf16 kernels have no '
+                                      'dilated form)' % dilation)
         if groups > 1:
-            self._init_grouped(weight, stride, padding, dtype, groups, None, 0, pitch)
+            self._init_grouped(weight, stride, padding, dtype, groups, None, 0, pitch, dilation)
             return
         assert pitch is None, 'a channel pitch is the grouped kernels\' (dense layers pad their packs)'
         Cout, Cin, KH, KW = weight.shape
+        if dilation != 1:      # the pack itself is the undilated one; the launch carries the tap step
+            assert (KH, KW) == (3, 3) and stride == 1 and padding == dilation and Cin % 32 == 0, \
+                'dilation=%d: 3x3 / stride 1 / padding == dilation with Cin %% 32 == 0, got weight %s stride %d padding %d' \
+                % (dilation, tuple(weight.shape), stride, padding)
+            self.dilation = dilation
         w = weight.detach().to(torch.float32).permute(0, 2, 3, 1)  # OHWI
         self.dtype = dtype
         if dtype == torch.bfloat16:
@@ -167,7 +178,7 @@ class PackedConv:
         packed[:, :K] = wp.reshape(Cout, K)
         self.w = packed.contiguous()
 
-    def _init_grouped(self, weight, stride, padding, dtype, groups, scale, transpose, pitch=None):
+    def _init_grouped(self, weight, stride, padding, dtype, groups, scale, transpose, pitch=None, dilation=1):
         """A grouped 3x3 / padding 1 conv, weight (C, cg, 3, 3) with cg = C / groups in GROUP_WIDTHS (csrc/conv_group.hip): self.w is the
         kernel's own image, 9 * cg * C floats [tap][cg / 4][4][C / 4][4] (cpr_pack_weights_grouped), not the dense [Cout][Kpad] rows.
         transpose: the data-gradient pack -- per group in / out channels swapped, taps flipped, ``scale`` multiplied in.  fp32 only.
@@ -178,12 +189,16 @@ class PackedConv:
         if dtype != torch.float32:
             raise NotImplementedError('a grouped convolution (groups=%d) runs in the fp32 compute mode only, not in %s' % (groups, dtype))
         assert weight.is_cuda, 'the grouped pack is built on the device'
-        assert cg * groups == C and cg in GROUP_WIDTHS and (KH, KW) == (3, 3) and padding == 1 and stride in (1, 2), \
-            'grouped conv: 3x3 / padding 1 / stride 1 or 2 with a group width in %s, got weight %s groups %d stride %d padding %d' \
-            % (GROUP_WIDTHS, tuple(weight.shape), groups, stride, padding)
+        assert cg * groups == C and cg in GROUP_WIDTHS and (KH, KW) == (3, 3) and padding == dilation and stride in (1, 2), \
+            'grouped conv: 3x3 / padding == dilation / stride 1 or 2 with a group width in %s, got weight %s groups %d stride %d ' \
+            'padding %d dilation %d' % (GROUP_WIDTHS, tuple(weight.shape), groups, stride, padding, dilation)
+        assert dilation == 1 or (stride == 1 and pitch == C), \
+            'grouped conv: dilation=%d needs stride 1 and unpitched maps, got stride %d pitch %d (C = %d)' % (dilation, stride, pitch, C)
         self.dtype, self.groups, self.cg, self.C = torch.float32, groups, cg, C
         self.Cout, self.Cin, self.KH, self.KW, self.Kpad = pitch, pitch, 3, 3, 9 * cg
-        self.stride, self.padding = stride, 1
+        self.stride, self.padding = stride, dilation
+        if dilation != 1:
+            self.dilation = dilation
         src = weight.detach()
         if src.dtype != torch.float32 or not src.is_contiguous():
             src = src.float().contiguous()
@@ -191,12 +206,18 @@ class PackedConv:
         _lib.call('cpr_pack_weights_grouped', _ptr(src), _ptr(scale), _ptr(self.w), C, cg, int(transpose), _stream())
         self._packed()
 
+    @staticmethod
+    def dgrad_padding(k, padding, dilation=1):
+        """Padding of the stride-1 conv over dy (flipped taps, the same dilation) that yields the data gradient of a k x k conv with
+        ``padding`` and ``dilation``: the taps span d (k - 1) pixels, so d (k - 1) - p (k - 1 - p undilated; d for a 3x3 with p = d)."""
+        return dilation * (k - 1) - padding
+
     @classmethod
-    def for_dgrad_grouped(cls, weight, groups, scale=None, pitch=None):
+    def for_dgrad_grouped(cls, weight, groups, scale=None, pitch=None, dilation=1):
         """The grouped pack of the stride-1 grouped conv over dy (zero-inserted first for a stride-2 layer, conv2d_dgrad) that yields
-        the data gradient of a grouped 3x3 / padding 1 conv: what for_dgrad is to the dense layers."""
+        the data gradient of a grouped 3x3 / padding == dilation conv: what for_dgrad is to the dense layers (padding 2 d - d = d)."""
         self = cls.__new__(cls)
-        self._init_grouped(weight, 1, 1, torch.float32, groups, scale, 1, pitch)
+        self._init_grouped(weight, 1, self.dgrad_padding(3, dilation, dilation), torch.float32, groups, scale, 1, pitch, dilation)
         return self
 
     def _pack_bf16(self, weight, scale, transpose):
@@ -244,12 +265,16 @@ class PackedConv:
         return self.wfrag
 
     @classmethod
-    def for_dgrad(cls, weight, padding, scale=None, pad_override=None):
+    def for_dgrad(cls, weight, padding, scale=None, pad_override=None, dilation=1):
         """Weights of the stride-1 conv over dy that yields the data gradient: in/out channels swapped, taps flipped,
-        optional per-output-channel scale of the FORWARD conv (folded BatchNorm) multiplied in, padding K-1-p
-        (``pad_override``: explicit padding, used by the per-parity sub-kernels of a strided conv)."""
+        optional per-output-channel scale of the FORWARD conv (folded BatchNorm) multiplied in, padding d (K-1) - p at the forward's
+        dilation d (``pad_override``: explicit padding, used by the per-parity sub-kernels of a strided conv)."""
         Cout, Cin, KH, KW = weight.shape
         assert (KH == KW or pad_override is not None) and weight.is_cuda
+        dilation = int(dilation)
+        assert dilation == 1 or ((KH, KW) == (3, 3) and pad_override is None and padding == dilation and Cout % 32 == 0), \
+            'dilation=%d: the data gradient of a 3x3 / padding == dilation layer, got weight %s padding %d' \
+            % (dilation, tuple(weight.shape), padding)
         assert Cout % 32 == 0 or Cout <= 4, 'gradient channels must be a multiple of 32 (or <= 4)'
         self = cls.__new__(cls)
         self.dtype = torch.float32
@@ -257,7 +282,9 @@ class PackedConv:
         K = KH * KW * cols_p
         Kpad = (K + 31) // 32 * 32
         self.Cout, self.Cin, self.KH, self.KW, self.Kpad = Cin, cols_p, KH, KW, Kpad
-        self.stride, self.padding = 1, (KH - 1 - padding if pad_override is None else pad_override)
+        self.stride, self.padding = 1, (self.dgrad_padding(KH, padding, dilation) if pad_override is None else pad_override)
+        if dilation != 1:
+            self.dilation = dilation
         src = weight.detach()
         if src.dtype != torch.float32 or not src.is_contiguous():
             src = src.float().contiguous()
@@ -267,8 +294,9 @@ class PackedConv:
         return self
 
     def out_hw(self, H, W):
-        return ((H + 2 * self.padding - self.KH) // self.stride + 1,
-                (W + 2 * self.padding - self.KW) // self.stride + 1)
+        d = self.dilation
+        return ((H + 2 * self.padding - d * (self.KH - 1) - 1) // self.stride + 1,
+                (W + 2 * self.padding - d * (self.KW - 1) - 1) // self.stride + 1)
 
 
 CONV_RELU, CONV_OUT_BF16, CONV_RES_MASK, CONV_COLSUM = 1, 2, 4, 8      # include/cpr_hip.h CPR_CONV_*
@@ -318,6 +346,8 @@ def pack_ready(pc):
 
 
 def wino_eligible(pc, H, W, dtype=torch.float32):
+    if pc.dilation != 1:      # the Winograd transforms are those of adjacent taps
+        return False
     if not (pc.groups == 1 and WINOGRAD[0] and dtype == torch.float32 and pc.dtype == torch.float32 and pc.KH == 3 and pc.KW == 3 and
             pc.stride == 1 and pc.padding == 1 and pc.Cin % 16 == 0 and pc.Cin >= 32 and pc.Cout % 64 == 0):
         return False
@@ -450,7 +480,11 @@ def conv2d(x, pc, scale=None, bias=None, residual=None, relu=False, in_ab=None, 
         assert tuple(out.shape) == (N, OH, OW, pc.Cout) and out.is_contiguous()
         if scale is not None or bias is not None:
             assert (scale is None or _check(scale).numel() >= pc.C) and (bias is None or _check(bias).numel() >= pc.C)
-        if Cin == pc.C:
+        if pc.dilation != 1:
+            assert Cin == pc.C and pc.stride == 1
+            _lib.call('cpr_conv_group_fwd_dil', _ptr(x), _ptr(pc.w), _ptr(out), _ptr(scale), _ptr(bias), N, H, W, Cin, pc.cg, pc.dilation,
+                      CONV_RELU if relu else 0, _stream())
+        elif Cin == pc.C:
             _lib.call('cpr_conv_group_fwd', _ptr(x), _ptr(pc.w), _ptr(out), _ptr(scale), _ptr(bias), N, H, W, Cin, pc.cg, pc.stride,
                       CONV_RELU if relu else 0, _stream())
         else:      # maps at a channel pitch: pad channels never read, written as +0.0
@@ -463,6 +497,25 @@ def conv2d(x, pc, scale=None, bias=None, residual=None, relu=False, in_ab=None, 
             (in_ab is None or Cin <= 512):
         return conv3x3_wino(x, pc, scale, bias, relu, gn_part, out, in_ab, in_relu, out_b8)
     assert not out_b8, 'channel-blocked output is produced by the Winograd layers only (check wino_eligible first)'
+    if pc.dilation != 1:
+        # dilated 3x3 (cpr_conv2d_fwd_dil): the direct fp32 kernel with scale / bias / residual / ReLU / mask / column sums, nothing else
+        assert in_ab is None and not (in_relu or gn_part) and odt == torch.float32 and x.dtype == torch.float32, \
+            'a dilated conv (dilation=%d) has no fused-input-affine, GroupNorm-statistics or bf16 form' % pc.dilation
+        if out is None:
+            out = torch.empty((N, OH, OW, pc.Cout), device=x.device, dtype=torch.float32)
+        assert tuple(out.shape) == (N, OH, OW, pc.Cout) and out.is_contiguous()
+        part = torch.empty(((N * OH * OW + 63) // 64, pc.Cout, 2), device=x.device, dtype=torch.float32) if colsum else None
+        variant = ctypes.c_int(0) if (colsum or TRACE_CONV_VARIANT[0]) else None
+        flags = (CONV_RELU if relu else 0) | (CONV_RES_MASK if res_mask else 0) | (CONV_COLSUM if colsum else 0)
+        _lib.call('cpr_conv2d_fwd_dil', _ptr(x), _ptr(pc.w), _ptr(out), _ptr(scale), _ptr(bias), _ptr(residual), None, None, _ptr(part),
+                  N, H, W, Cin, pc.Cout, pc.KH, pc.KW, pc.stride, pc.padding, pc.dilation, pc.Kpad, flags, 0,
+                  ctypes.byref(variant) if variant is not None else None, _stream())
+        if variant is not None:
+            TRACE_CONV_VARIANT[1] = ('fp32_dil', variant.value)
+        if colsum:
+            bm = variant.value // 1000000
+            return out, TilePartials(part, (N * OH * OW + bm - 1) // bm, pc.Cout)
+        return out
     if out is None:
         out = torch.empty((N, OH, OW, pc.Cout), device=x.device, dtype=odt)
     part = None
@@ -1621,19 +1674,28 @@ def match_cost(pred, logits, gt, labels, cls_terms, reg_terms):
 
 
 # ------------------------------------------------------------------------------------------------ backward / optimizer
-def dgrad_pack(weight, stride, padding, scale=None, dtype=torch.float32, groups=1, pitch=None):
+def dgrad_pack(weight, stride, padding, scale=None, dtype=torch.float32, groups=1, pitch=None, dilation=1):
     """PackedConv that computes the data gradient of ``conv2d(x, weight, stride, padding)`` as a stride-1 forward conv
     over dy (zero-inserted first when stride > 1): channels swapped, taps flipped, padding K-1-p; ``scale`` (Cout,) is
     the forward conv's folded-BatchNorm scale, multiplied into the weights.  Stride-2 convs with k in {1, 3} and
     padding k//2 (every strided conv of the ResNet body) get the phase-decomposed form (PhasedDgrad).  groups > 1 (a grouped 3x3 layer):
     the grouped data-gradient pack at either stride -- conv2d_dgrad zero-inserts a strided layer's gradient; ``pitch``: the channel pitch
-    of its gradient maps (PackedConv)."""
+    of its gradient maps (PackedConv).  dilation > 1 (stride 1, 3x3, padding == dilation; fp32): the same dilated conv over dy with the
+    flipped pack and padding 2 d - d = d -- never the Winograd route (wino_eligible)."""
+    dilation = int(dilation)
+    if dilation != 1:
+        assert stride == 1 and padding == dilation, \
+            'dilation=%d: the data gradient is built for stride 1 and padding == dilation, got stride %d padding %d' % (dilation, stride, padding)
+        if dtype != torch.float32:
+            raise NotImplementedError('dilation=%d: a dilated convolution runs in the fp32 compute mode only, not in %s' % (dilation, dtype))
     if groups > 1:
         if dtype != torch.float32:
             raise NotImplementedError('a grouped convolution (groups=%d) runs in the fp32 compute mode only, not in %s' % (groups, dtype))
-        assert padding == 1 and stride in (1, 2)
-        return PackedConv.for_dgrad_grouped(weight, groups, scale, pitch)
+        assert padding == dilation and stride in (1, 2)
+        return PackedConv.for_dgrad_grouped(weight, groups, scale, pitch, dilation)
     assert pitch is None
+    if dilation != 1:
+        return PackedConv.for_dgrad(weight, padding, scale, dilation=dilation)
     if stride == 2 and weight.shape[2] == weight.shape[3] and weight.shape[2] in (1, 3) and padding == weight.shape[2] // 2 \
             and _PHASED[0]:
         return PhasedDgrad(weight, stride, padding, scale, dtype)
@@ -1688,6 +1750,7 @@ def conv2d_dgrad(dy, pc_t, in_hw, stride=1, mask=None, add=None, colsum=False):
     per-channel sums of the result as TilePartials (-> (dx, partials); ``partials.reduce()`` gives the (C,) vector)."""
     N, OH, OW, Cout = _check(dy).shape
     H, W = in_hw
+    assert isinstance(pc_t, PhasedDgrad) or pc_t.dilation == 1 or stride == 1, 'the data gradient of a dilated conv is built for stride 1'
     if not isinstance(pc_t, PhasedDgrad) and pc_t.groups > 1:
         # grouped layer: the grouped kernel over dy (its epilogue has no extra operand), then sum / mask / column sums as ONE streaming
         # pass over the result.  Stride 2: zero insertion -- the map is the block's narrow one and three layers of the net are strided
@@ -1783,17 +1846,20 @@ def conv3x3_wino_wgrad(dy, x, weight_shape, in_ab=None, in_relu=False, grad=None
     return grad
 
 
-def conv2d_wgrad(dy, x, weight_shape, stride, padding, in_ab=None, in_relu=False, grad=None, out=None, groups=1):
+def conv2d_wgrad(dy, x, weight_shape, stride, padding, in_ab=None, in_relu=False, grad=None, out=None, groups=1, dilation=1):
     """grad_w [Cout][Cin][KH][KW]: accumulated into ``grad`` when given, written into ``out`` when given, else a new
     tensor.  in_ab: fused GroupNorm affine (+ReLU) of the input.  groups > 1: a grouped 3x3 / padding 1 layer, grad_w (C, C / groups, 3, 3)
     (csrc/conv_group.hip; the split over pixels is added up in a fixed order); dy and x may sit at a channel pitch >= C (their last
-    dimension), whose pad channels are not read."""
+    dimension), whose pad channels are not read.  dilation > 1: the dilated kernels (cpr_conv2d_wgrad_dil, cpr_conv_group_wgrad_dil; no
+    fused input affine), never the Winograd route."""
     N, H, W, Cin = _check(x).shape
     _, OH, OW, Cout = _check(dy).shape
     KH, KW = weight_shape[2], weight_shape[3]
+    dilation = int(dilation)
+    assert dilation >= 1
     if groups > 1:
         cg, C = weight_shape[1], weight_shape[0]
-        assert Cout == Cin >= C == cg * groups and Cin % 4 == 0 and cg in GROUP_WIDTHS and (KH, KW) == (3, 3) and padding == 1 and \
+        assert Cout == Cin >= C == cg * groups and Cin % 4 == 0 and cg in GROUP_WIDTHS and (KH, KW) == (3, 3) and padding == dilation and \
             in_ab is None and not in_relu and x.dtype == torch.float32 and dy.dtype == torch.float32, (weight_shape, groups, Cin, Cout)
         assert (OH, OW) == ((H - 1) // stride + 1, (W - 1) // stride + 1), (dy.shape, x.shape, stride)
         n = _lib.call('cpr_conv_group_wgrad_workspace', N, OH, OW, C, cg, positive=True)
@@ -1802,14 +1868,17 @@ def conv2d_wgrad(dy, x, weight_shape, stride, padding, in_ab=None, in_relu=False
         if grad is None:
             grad = out if out is not None else torch.empty(tuple(weight_shape), device=x.device, dtype=torch.float32)
         assert tuple(grad.shape) == tuple(weight_shape) and grad.is_contiguous()
-        if Cin == C:
+        if dilation != 1:
+            assert stride == 1 and Cin == C, 'grouped conv: dilation=%d needs stride 1 and unpitched maps' % dilation
+            _lib.call('cpr_conv_group_wgrad_dil', _ptr(dy), _ptr(x), _ptr(grad), _ptr(ws), N, H, W, Cin, cg, dilation, int(acc), _stream())
+        elif Cin == C:
             _lib.call('cpr_conv_group_wgrad', _ptr(dy), _ptr(x), _ptr(grad), _ptr(ws), N, H, W, Cin, cg, stride, int(acc), _stream())
         else:
             _lib.call('cpr_conv_group_wgrad_pitch', _ptr(dy), _ptr(x), _ptr(grad), _ptr(ws), N, H, W, C, Cin, cg, stride, int(acc),
                       _stream())
         return grad
     assert weight_shape[0] == Cout and weight_shape[1] == Cin, (weight_shape, Cout, Cin)
-    if WINOGRAD[0] and KH == 3 and KW == 3 and stride == 1 and padding == 1 and Cin % 64 == 0 and Cout % 64 == 0 and \
+    if dilation == 1 and WINOGRAD[0] and KH == 3 and KW == 3 and stride == 1 and padding == 1 and Cin % 64 == 0 and Cout % 64 == 0 and \
             x.dtype == torch.float32 and W / float((W + 15) // 16 * 16) >= WINO_MIN_FILL and H * W >= 1024 and \
             (in_ab is None or Cin <= 512):     # (20x20 maps: too few tiles per K slice against 16 frequencies of partials)
         return conv3x3_wino_wgrad(dy, x, weight_shape, in_ab, in_relu, grad, out)
@@ -1819,6 +1888,14 @@ def conv2d_wgrad(dy, x, weight_shape, stride, padding, in_ab=None, in_relu=False
     if grad is None:
         grad = out if out is not None else torch.empty(tuple(weight_shape), device=x.device, dtype=torch.float32)
     assert tuple(grad.shape) == tuple(weight_shape) and grad.is_contiguous()
+    if dilation != 1:
+        assert in_ab is None and not in_relu and x.dtype == torch.float32 and dy.dtype == torch.float32, \
+            'a dilated conv (dilation=%d) has no fused-input-affine or bf16 weight gradient' % dilation
+        assert (OH, OW) == ((H + 2 * padding - dilation * (KH - 1) - 1) // stride + 1,
+                            (W + 2 * padding - dilation * (KW - 1) - 1) // stride + 1), (dy.shape, x.shape, stride, padding, dilation)
+        _lib.call('cpr_conv2d_wgrad_dil', _ptr(dy), _ptr(x), _ptr(grad), _ptr(ws), N, H, W, Cin, Cout, KH, KW, stride, padding, dilation,
+                  int(acc), _stream())
+        return grad
     a = b = None
     if in_ab is not None:
         a, b = in_ab

@@ -307,6 +307,9 @@ class BackwardEngine:
         if getattr(bb, 'compute_dtype', torch.float32) != torch.float32 and getattr(bb, 'groups', 1) > 1:
             raise NotImplementedError('a grouped backbone (ResNeXt groups=%d) trains in the fp32 compute mode only: the bf16 compute mode '
                                       'has no grouped convolution' % bb.groups)
+        if getattr(bb, 'compute_dtype', torch.float32) != torch.float32 and any(d != 1 for d in getattr(bb, 'dilations', ())):
+            raise NotImplementedError('a dilated backbone (dilations=%r) trains in the fp32 compute mode only: the bf16 compute mode has '
+                                      'no dilated convolution' % (tuple(bb.dilations),))
         if getattr(bb, 'scales', 0):      # a Res2Net backbone (backbones/res2net.py)
             if getattr(bb, 'compute_dtype', torch.float32) != torch.float32:
                 raise NotImplementedError('a Res2Net backbone (scales=%d) trains in the fp32 compute mode only: the bf16 compute mode has '
@@ -1027,7 +1030,8 @@ class BackwardEngine:
                 if w16:
                     ops.conv_wgrad_bf16(g16, x, w.shape, out=gw, stride=conv.stride[0])    # (x: the bf16 recorded map, or a widened copy that rounds back exactly)
                 else:
-                    ops.conv2d_wgrad(g, self._f32(x), w.shape, conv.stride[0], conv.padding[0], out=gw, groups=conv.groups)
+                    ops.conv2d_wgrad(g, self._f32(x), w.shape, conv.stride[0], conv.padding[0], out=gw, groups=conv.groups,
+                                     dilation=conv.dilation[0])
                 ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, cs,
                                 out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
             # x may be a widened fp32 temporary of the mixed-precision step that the main stream frees right after this call
@@ -1343,7 +1347,8 @@ class BackwardEngine:
         w = conv.weight
         if w.requires_grad:
             def param_grads():
-                ops.conv2d_wgrad(dy, x, w.shape, conv.stride[0], conv.padding[0], out=self._g(w), groups=conv.groups)
+                ops.conv2d_wgrad(dy, x, w.shape, conv.stride[0], conv.padding[0], out=self._g(w), groups=conv.groups,
+                                 dilation=conv.dilation[0])
             self._param_side(param_grads, dy, x)
         if not need_dx:
             return None
