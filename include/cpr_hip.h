@@ -546,6 +546,34 @@ int cpr_res2_pool_fwd(const float* x, int x_pitch, int x_off, float* out, int ou
                       int stride, void* stream);
 int cpr_res2_pool_bwd(const float* dy, int dy_pitch, int dy_off, float* dx, int dx_pitch, int dx_off, int N, int H, int W, int width,
                       int stride, void* stream);
+/* ---- ResNeSt split attention, radix 2 (resnest.py:40-150; csrc/splat.hip), NHWC fp32 -------------------------------------------------
+ * u (N,H,W,2w): the block's 3x3 conv + bn0 + ReLU output, channel r*w + c = split r of channel c.  w % 4 == 0, 4 .. 1024, inter 1 .. 1024,
+ * pool 0 / 1, and N <= 65535 in the three reductions (gap, attn_grad, apply_bwd): anything else (and a NULL map) is CPR_ERR_ARG before any launch; 2^31 pixels or more is CPR_ERR_UNSUPPORTED.
+ * Pixel reductions run per (image, chunk of pixels), cpr_splat_chunks(H, W, w) chunks per image -- a function of (H, W, w) alone --
+ * and the chunk partials (ws) are added in ascending order by a second launch: no atomics, bit-repeatable, batch-independent.
+ * cpr_splat_gap: g[n,c] = mean over pixels of u[n,p,c] + u[n,p,w+c].  ws: N * chunks * w floats. */
+int cpr_splat_chunks(int H, int W, int w);
+int cpr_splat_gap(const float* u, float* g, float* ws, int N, int H, int W, int w, void* stream);
+/* One workgroup per image: z = relu(s1 * (fc1w g + fc1b) + t1) (fc1w (inter, w); s1 / t1 the folded eval BatchNorm), a = fc2w z + fc2b
+ * (fc2w (2w, inter)), att[n,r,c] = softmax over r of a[n, r*w + c] (the maximum subtracted, expf).  z (N, inter) may be NULL. */
+int cpr_splat_attn(const float* g, const float* fc1w, const float* fc1b, const float* s1, const float* t1, const float* fc2w,
+                   const float* fc2b, float* att, float* z, int N, int w, int inter, void* stream);
+/* out = sum_r att[n,r,c] * u[n,p,r*w+c] (N,H,W,w), or with pool AvgPool2d(3, 2, padding 1) of it in the same launch: (N,(H-1)/2+1,
+ * (W-1)/2+1,w), out-of-range taps contribute 0, the divisor is always 9. */
+int cpr_splat_apply(const float* u, const float* att, float* out, int N, int H, int W, int w, int pool, void* stream);
+/* datt[n,r,c] = sum over pixels of dv[n,p,c] * u[n,p,r*w+c]; dv = dout (N,H,W,w), or with pool the pool's adjoint of dout
+ * (N,(H-1)/2+1,(W-1)/2+1,w) in gather form.  ws: N * chunks * 2w floats. */
+int cpr_splat_attn_grad(const float* dout, const float* u, float* datt, float* ws, int N, int H, int W, int w, int pool, void* stream);
+/* Per image: da = att * (datt - sum_r att * datt), dz = fc2w^T da, dh' = dz * (z > 0), dh = s1 * dh', dg (N,w) = fc1w^T dh.  Then the
+ * parameter gradients, images added in ascending order (each may be NULL): fc2w / fc2b from da and z, fc1w / fc1b from dh and g, the
+ * eval BatchNorm's weight / bias from dh' and xhat = (fc1w g + fc1b - mean) * inv_sigma.  ws: N * (2w + 3 * inter) floats. */
+int cpr_splat_attn_bwd(const float* att, const float* datt, const float* z, const float* g, const float* fc1w, const float* fc1b,
+                       const float* s1, const float* mean, const float* inv_sigma, const float* fc2w, float* dg, float* ws, float* gfc1w,
+                       float* gfc1b, float* gbnw, float* gbnb, float* gfc2w, float* gfc2b, int N, int w, int inter, void* stream);
+/* du[n,p,r*w+c] = (att[n,r,c] * dv[n,p,c] + dg[n,c] / (H*W)) * (u > 0) and colsum[2w], its per-channel sums over images and pixels
+ * (chunks of an image, then images, ascending).  ws: N * chunks * 2w + N * 2w floats. */
+int cpr_splat_apply_bwd(const float* dout, const float* u, const float* att, const float* dg, float* du, float* colsum, float* ws, int N,
+                        int H, int W, int w, int pool, void* stream);
 /* FPN extra pyramid levels (fpn.py:195-217; csrc/fpn_extra.hip), NHWC, 16 bytes of channels per lane.
  * cpr_subsample2: out (N,(H+1)/2,(W+1)/2,C) = y[:, ::2, ::2, :] with y = x, or x*a[n,c] + b[n,c] when a/b (N,C) are given (the producer's
  * pending GroupNorm affine, cpr_gn_apply's arithmetic) -- F.max_pool2d(y, 1, stride=2) bit for bit.  x/out fp32 (C%4==0) or bf16

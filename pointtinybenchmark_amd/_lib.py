@@ -141,6 +141,13 @@ SIGNATURES = {
     'cpr_res2_pool_fwd': [_p, _i, _i, _p, _i, _i] + [_i] * 5 + [_p],
     'cpr_res2_relu_bwd_colsum': [_p, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _l, _i, _p],
     'cpr_res2_pool_bwd': [_p, _i, _i, _p, _i, _i] + [_i] * 5 + [_p],
+    'cpr_splat_chunks': [_i] * 3,
+    'cpr_splat_gap': [_p, _p, _p] + [_i] * 4 + [_p],
+    'cpr_splat_attn': [_p] * 9 + [_i] * 3 + [_p],
+    'cpr_splat_apply': [_p] * 3 + [_i] * 5 + [_p],
+    'cpr_splat_attn_grad': [_p] * 4 + [_i] * 5 + [_p],
+    'cpr_splat_attn_bwd': [_p] * 18 + [_i] * 3 + [_p],
+    'cpr_splat_apply_bwd': [_p] * 7 + [_i] * 5 + [_p],
     'cpr_spin': [ctypes.c_longlong, _p],
     'cpr_bn_fold': [_p, _p, _p, _p, _f, _p, _p, _p, _i, _p],
     'cpr_bn_train_ws': [_l, _i],

@@ -2384,3 +2384,119 @@ def res2_relu_bwd(g, g_off, y, y_off, width, carry=None, carry_off=0):
     _lib.call('cpr_res2_relu_bwd_colsum', _ptr(g), gp, g_off, _ptr(carry), cp, carry_off, _ptr(y), yp, y_off, _ptr(cs), _ptr(ws), M, width,
               _stream())
     return cs
+
+
+# ---- ResNeSt split attention, radix 2 (csrc/splat.hip).  u (N,H,W,2w) fp32: the block's 3x3 conv + bn0 + ReLU output, channel r*w + c =
+# split r of channel c.  The C entry points check w % 4 == 0 and the ranges (include/cpr_hip.h) and raise CprHipError('... invalid
+# argument') before any launch; the shapes of the operands against each other are checked here.
+SPLAT_RADIX = 2
+
+
+def _splat_map(u):
+    assert u.dim() == 4 and u.shape[-1] % SPLAT_RADIX == 0, 'split attention: a (N,H,W,2w) map, got %s' % (tuple(u.shape),)
+    N, H, W, C2 = _check(u).shape
+    return N, H, W, C2 // SPLAT_RADIX
+
+
+def _splat_pooled(H, W, pool):
+    return ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if pool else (H, W)
+
+
+def _splat_ws(u, rows, w):
+    N, H, W, _ = u.shape
+    k = _lib.call('cpr_splat_chunks', H, W, w, positive=True)
+    return k, torch.empty((N * k * rows,), device=u.device, dtype=torch.float32)
+
+
+def splat_dense_weight(weight):
+    """The split-attention conv's parameter (2w, w/2, 3, 3) -- two groups, w/2 -> w each -- as the dense (2w, w, 3, 3) weight with exact
+    zeros off the two diagonal blocks (the dense kernels' pack and data-gradient pack are built from it)."""
+    O, I, KH, KW = weight.shape
+    assert O == 4 * I, 'split-attention conv: a (2w, w/2, k, k) weight, got %s' % (tuple(weight.shape),)
+    w = O // 2
+    dense = torch.zeros((O, w, KH, KW), device=weight.device, dtype=torch.float32)
+    dense[:w, :I].copy_(weight.detach()[:w])
+    dense[w:, I:].copy_(weight.detach()[w:])
+    return dense
+
+
+def splat_gap(u):
+    """g (N,w) = the mean over pixels of u[..., c] + u[..., w + c]."""
+    N, H, W, w = _splat_map(u)
+    _, ws = _splat_ws(u, w, w)
+    g = torch.empty((N, w), device=u.device, dtype=torch.float32)
+    _lib.call('cpr_splat_gap', _ptr(u), _ptr(g), _ptr(ws), N, H, W, w, _stream())
+    return g
+
+
+def splat_attn(g, fc1_w, fc1_b, scale, shift, fc2_w, fc2_b, record=False):
+    """att (N,2,w) = the radix softmax of fc2(relu(scale * (fc1 g + b1) + shift)) + b2 (scale / shift: the folded eval BatchNorm);
+    record: -> (att, z), z (N,inter) the ReLU's output."""
+    N, w = _check(g).shape
+    inter = fc1_w.shape[0]
+    assert tuple(fc1_w.shape[:2]) == (inter, w) and fc1_w.numel() == inter * w, (fc1_w.shape, g.shape)
+    assert tuple(fc2_w.shape[:2]) == (2 * w, inter) and fc2_w.numel() == 2 * w * inter, (fc2_w.shape, g.shape)
+    assert fc1_b.numel() == scale.numel() == shift.numel() == inter and fc2_b.numel() == 2 * w
+    for t in (fc1_w, fc1_b, scale, shift, fc2_w, fc2_b):
+        _check(t)
+    att = torch.empty((N, SPLAT_RADIX, w), device=g.device, dtype=torch.float32)
+    z = torch.empty((N, inter), device=g.device, dtype=torch.float32) if record else None
+    _lib.call('cpr_splat_attn', _ptr(g), _ptr(fc1_w), _ptr(fc1_b), _ptr(scale), _ptr(shift), _ptr(fc2_w), _ptr(fc2_b), _ptr(att), _ptr(z),
+              N, w, inter, _stream())
+    return (att, z) if record else att
+
+
+def splat_apply(u, att, pool=False):
+    """sum_r att[n,r,c] * u[n,p,r*w+c] (N,H,W,w), or with ``pool`` AvgPool2d(3, 2, padding=1) of it (divisor always 9), one launch."""
+    N, H, W, w = _splat_map(u)
+    assert tuple(_check(att).shape) == (N, SPLAT_RADIX, w), (att.shape, u.shape)
+    OH, OW = _splat_pooled(H, W, pool)
+    out = torch.empty((N, OH, OW, w), device=u.device, dtype=torch.float32)
+    _lib.call('cpr_splat_apply', _ptr(u), _ptr(att), _ptr(out), N, H, W, w, int(bool(pool)), _stream())
+    return out
+
+
+def splat_attn_grad(dout, u, pool=False):
+    """datt (N,2,w) = sum over pixels of dv * u[..., r*w + c]; dv = dout, or with ``pool`` the pool's adjoint of dout."""
+    N, H, W, w = _splat_map(u)
+    assert tuple(_check(dout).shape) == (N,) + _splat_pooled(H, W, pool) + (w,), (dout.shape, u.shape, pool)
+    _, ws = _splat_ws(u, 2 * w, w)
+    datt = torch.empty((N, SPLAT_RADIX, w), device=u.device, dtype=torch.float32)
+    _lib.call('cpr_splat_attn_grad', _ptr(dout), _ptr(u), _ptr(datt), _ptr(ws), N, H, W, w, int(bool(pool)), _stream())
+    return datt
+
+
+def splat_attn_bwd(att, datt, z, g, fc1_w, fc1_b, scale, mean, inv_sigma, fc2_w, grads=None):
+    """The attention MLP's backward -> dg (N,w).  grads: a dict of output tensors, any of 'fc1_w', 'fc1_b', 'bn_w', 'bn_b', 'fc2_w',
+    'fc2_b' (written, images added in ascending order)."""
+    N, w = _check(g).shape
+    inter = fc1_w.shape[0]
+    assert tuple(att.shape) == tuple(datt.shape) == (N, SPLAT_RADIX, w) and tuple(z.shape) == (N, inter), (att.shape, datt.shape, z.shape)
+    assert fc1_w.numel() == inter * w and fc2_w.numel() == 2 * w * inter
+    assert fc1_b.numel() == scale.numel() == mean.numel() == inv_sigma.numel() == inter
+    for t in (att, datt, z, fc1_w, fc1_b, scale, mean, inv_sigma, fc2_w):
+        _check(t)
+    grads = grads or {}
+    shapes = dict(fc1_w=inter * w, fc1_b=inter, bn_w=inter, bn_b=inter, fc2_w=2 * w * inter, fc2_b=2 * w)
+    for k, t in grads.items():
+        assert _check(t).numel() == shapes[k], (k, t.shape)
+    dg = torch.empty((N, w), device=g.device, dtype=torch.float32)
+    ws = torch.empty((N * (2 * w + 3 * inter),), device=g.device, dtype=torch.float32)
+    _lib.call('cpr_splat_attn_bwd', _ptr(att), _ptr(datt), _ptr(z), _ptr(g), _ptr(fc1_w), _ptr(fc1_b), _ptr(scale), _ptr(mean),
+              _ptr(inv_sigma), _ptr(fc2_w), _ptr(dg), _ptr(ws), _ptr(grads.get('fc1_w')), _ptr(grads.get('fc1_b')), _ptr(grads.get('bn_w')),
+              _ptr(grads.get('bn_b')), _ptr(grads.get('fc2_w')), _ptr(grads.get('fc2_b')), N, w, inter, _stream())
+    return dg
+
+
+def splat_apply_bwd(dout, u, att, dg, pool=False):
+    """du (N,H,W,2w) = (att[n,r,c] * dv + dg[n,c] / (H*W)) * (u > 0) and its (2w,) column sums -> (du, colsum)."""
+    N, H, W, w = _splat_map(u)
+    assert tuple(_check(dout).shape) == (N,) + _splat_pooled(H, W, pool) + (w,), (dout.shape, u.shape, pool)
+    assert tuple(_check(att).shape) == (N, SPLAT_RADIX, w) and tuple(_check(dg).shape) == (N, w), (att.shape, dg.shape)
+    k = _lib.call('cpr_splat_chunks', H, W, w, positive=True)
+    ws = torch.empty((N * k * 2 * w + N * 2 * w,), device=u.device, dtype=torch.float32)
+    du = torch.empty_like(u)
+    cs = torch.empty((2 * w,), device=u.device, dtype=torch.float32)
+    _lib.call('cpr_splat_apply_bwd', _ptr(dout), _ptr(u), _ptr(att), _ptr(dg), _ptr(du), _ptr(cs), _ptr(ws), N, H, W, w, int(bool(pool)),
+              _stream())
+    return du, cs

@@ -157,6 +157,40 @@ def regnet_state_dict(arch='regnetx_3.2gf', seed=0, prefix='backbone.', avg_down
     return sd
 
 
+def resnest_state_dict(depth=50, seed=0, radix=2, reduction_factor=4, prefix='backbone.'):
+    """The keys and shapes of mmdet's ResNeSt (resnest.py; groups=1), in its state-dict order: the deep stem, then per block conv1, bn1,
+    conv2.conv (planes * radix, planes / radix, 3, 3), conv2.bn0, conv2.fc1 (weight, bias), conv2.bn1, conv2.fc2 (weight, bias), conv3,
+    bn3, downsample.1 / .2 (behind the parameter-free pool at index 0).  Its own generator: no other call's random stream moves."""
+    g = torch.Generator().manual_seed(seed)
+    blocks = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3), 200: (3, 24, 36, 3)}[depth]
+    sd = {}
+    for i, (co, ci) in zip((0, 3, 6), ((32, 3), (32, 32), (64, 32))):
+        sd['%sstem.%d.weight' % (prefix, i)] = _kaiming((co, ci, 3, 3), g)
+        _bn(sd, '%sstem.%d' % (prefix, i + 1), co, g)
+    inplanes = 64
+    for li, nb in enumerate(blocks):
+        planes = 64 * 2 ** li
+        inter = max(planes * radix // reduction_factor, 32)
+        for bi in range(nb):
+            p = '%slayer%d.%d.' % (prefix, li + 1, bi)
+            sd[p + 'conv1.weight'] = _kaiming((planes, inplanes, 1, 1), g)
+            _bn(sd, p + 'bn1', planes, g)
+            sd[p + 'conv2.conv.weight'] = _kaiming((planes * radix, planes // radix, 3, 3), g)
+            _bn(sd, p + 'conv2.bn0', planes * radix, g)
+            sd[p + 'conv2.fc1.weight'] = _kaiming((inter, planes, 1, 1), g)
+            sd[p + 'conv2.fc1.bias'] = torch.randn(inter, generator=g) * 0.1
+            _bn(sd, p + 'conv2.bn1', inter, g)
+            sd[p + 'conv2.fc2.weight'] = _kaiming((planes * radix, inter, 1, 1), g)
+            sd[p + 'conv2.fc2.bias'] = torch.randn(planes * radix, generator=g) * 0.1
+            sd[p + 'conv3.weight'] = _kaiming((planes * 4, planes, 1, 1), g)
+            _bn(sd, p + 'bn3', planes * 4, g)
+            if bi == 0:
+                sd[p + 'downsample.1.weight'] = _kaiming((planes * 4, inplanes, 1, 1), g)
+                _bn(sd, p + 'downsample.2', planes * 4, g)
+            inplanes = planes * 4
+    return sd
+
+
 def fpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=1, seed=1, prefix='neck.', add_extra_convs=False,
                    extra_convs_on_inputs=True):
     """add_extra_convs (False / True / 'on_input' / 'on_lateral' / 'on_output', as FPN takes it): the stride-2 convs of the

@@ -1107,6 +1107,8 @@ class BackwardEngine:
             return self._bottle2neck_backward(cache, blk, rec, dout, need_dx)
         if blk.kind == 'regnet':
             return self._regnet_block_backward(cache, blk, rec, dout, need_dx)
+        if blk.kind == 'resnest':
+            return self._resnest_block_backward(cache, blk, rec, dout, need_dx)
         mixed = self._mixed
         x = rec['x']
         if isinstance(dout, tuple):
@@ -1240,6 +1242,63 @@ class BackwardEngine:
             tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
         else:
             dx = self._r2_pointwise_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3)
+            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
+        self._done(tail)
+        return dx
+
+    # ------------------------------------------------------------------ ResNeSt (backbones/resnest.py; fp32, eval-mode BatchNorm)
+    def _resnest_block_backward(self, cache, blk, rec, dout, need_dx):
+        """The split-attention block's rule.  conv3's rule gives do = d(o) (no activation sits between the attention-weighted sum, or
+        its pool, and conv3); datt = the pixel reduction of dv * u (ops.splat_attn_grad, dv the pool's adjoint of do in a pooled
+        block); the attention MLP's backward with its six parameter gradients (ops.splat_attn_bwd) gives dg; du = (att * dv + dg / HW)
+        * (u > 0) with its column sums (ops.splat_apply_bwd); then conv2.conv / bn0 as a dense conv -> folded BN -- the weight
+        gradient taken dense into scratch and the two diagonal blocks copied to the parameter's gradient, the data gradient through
+        the pack of the same block-diagonal weight -- and conv1's rule with the shortcut."""
+        x, o1, u = rec['x'], rec['o1'], rec['u']
+        if isinstance(dout, tuple):
+            g3, cs3 = dout[0], dout[1]
+        else:
+            g3, cs3 = ops.relu_bwd_colsum(dout, rec['out'])          # also the shortcut gradient
+        sa, w = blk.conv2, blk.width
+        do = self._conv_bn_backward(cache, blk.conv3, blk.bn3, g3, cs3, rec['o'], True)
+        self._done(blk.bn3.bias if blk.bn3.bias.requires_grad else blk.conv3.weight)
+        datt = ops.splat_attn_grad(do, u, pool=blk.pool)
+        sm, _ = folded_bn(cache, sa.bn1)
+        named = dict(fc2_w=sa.fc2.weight, fc2_b=sa.fc2.bias, fc1_w=sa.fc1.weight, fc1_b=sa.fc1.bias, bn_w=sa.bn1.weight, bn_b=sa.bn1.bias)
+        dg = ops.splat_attn_bwd(rec['att'], datt, rec['z'], rec['g'], sa.fc1.weight, sa.fc1.bias, sm, sa.bn1.running_mean,
+                                bn_inv_sigma(cache, sa.bn1), sa.fc2.weight, grads={k: self._g(p) for k, p in named.items() if p.requires_grad})
+        du, csu = ops.splat_apply_bwd(do, u, rec['att'], dg, pool=blk.pool)
+        del do, datt, dg
+        conv, bn = sa.conv, sa.bn0
+        scale, _ = folded_bn(cache, bn)
+        if conv.weight.requires_grad:
+            aff = bn.weight.requires_grad
+
+            def param_grads():
+                gw = self._g(conv.weight)
+                dense = ops.conv2d_wgrad(du, o1, (2 * w, w, 3, 3), 1, 1)
+                gw[:w].copy_(dense[:w, :w // 2])
+                gw[w:].copy_(dense[w:, w // 2:])
+                ops.bn_fold_bwd(gw, conv.weight, scale, bn.running_mean, bn_inv_sigma(cache, bn), csu,
+                                out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
+            self._param_side(param_grads, du, csu, o1)
+        pt = cache.get(('st_dgrad', id(conv)), [conv.weight, bn.weight, bn.running_var],
+                       lambda: ops.dgrad_pack(ops.splat_dense_weight(conv.weight), 1, 1, scale=scale))      # (lapses with the weight epoch)
+        g1, cs1 = ops.relu_bwd_colsum(ops.conv2d_dgrad(du, pt, (o1.shape[1], o1.shape[2]), 1), o1)      # conv1's ReLU
+        del du
+        self._done(bn.bias if bn.bias.requires_grad else conv.weight)
+        if blk.downsample is not None:
+            dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx)
+            pool = blk.ds_pool
+            if pool:
+                dxp = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, rec['xp'], need_dx)
+                if need_dx:
+                    dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
+            else:
+                dx = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx)
+            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
+        else:
+            dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3)
             tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
         self._done(tail)
         return dx
@@ -1652,6 +1711,14 @@ class CprTrainer(BackwardEngine):
                     for conv, bn in reversed(list(zip(blk.convs, blk.bns))):
                         add(conv.weight, bn.weight, bn.bias)
                     add(blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
+                    if blk.downsample is not None:
+                        add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
+                    continue
+                if blk.kind == 'resnest':       # (ResNeSt, _resnest_block_backward: conv3, the attention MLP, conv2.conv / bn0, conv1)
+                    sa = blk.conv2
+                    add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
+                    add(sa.fc2.weight, sa.fc2.bias, sa.fc1.weight, sa.fc1.bias, sa.bn1.weight, sa.bn1.bias)
+                    add(sa.conv.weight, sa.bn0.weight, sa.bn0.bias, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
                     if blk.downsample is not None:
                         add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
                     continue
