@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..layers import _PackCache, _pack_job, folded_bn, packed_conv
+from ..layers import _PackCache, _pack_job, folded_bn, folded_bn_padded, packed_conv, packed_conv_padded
 from ..registry import BACKBONES
 from .resnet import ResNet, _Block, block_width
 
@@ -95,40 +95,11 @@ class _RegBottleneck(_Block):
         self.inplanes, self.planes, self.width = inplanes, planes, width
         self.kind = 'bottleneck' if inplanes % 32 == 0 and planes % 32 == 0 and width % 32 == 0 else 'regnet'
 
-    # ---- layers around the padded pitch: packs with exact zeros in the pad rows / columns, folds with zero scale / shift there
-    @staticmethod
-    def padded_pack(cache, conv, Op, Ip):
-        """The dense pack of ``conv`` (O, I, k, k) at (Op, Ip): rows >= O and columns >= I zero.  (Entries without a refresh job: they
-        lapse with the weight epoch and rebuild from the refreshed parameters.)"""
-        O, I = conv.weight.shape[:2]
-        if (Op, Ip) == (O, I):
-            return packed_conv(cache, conv)
-
-        def pack():
-            w = torch.zeros((Op, Ip) + tuple(conv.weight.shape[2:]), device=conv.weight.device, dtype=torch.float32)
-            w[:O, :I].copy_(conv.weight.detach())
-            return ops.PackedConv(w, conv.stride[0], conv.padding[0])
-        return cache.get(('rg_pc', id(conv), Op, Ip), [conv.weight], pack)
-
-    @staticmethod
-    def padded_fold(cache, bn, Op):
-        O = bn.weight.numel()
-        if Op == O:
-            return folded_bn(cache, bn)
-
-        def fold():
-            s, b = folded_bn(cache, bn)
-            sp, bp = s.new_zeros((Op,)), b.new_zeros((Op,))
-            sp[:O].copy_(s)
-            bp[:O].copy_(b)
-            return sp, bp
-        return cache.get(('rg_bn', id(bn), Op), [bn.weight, bn.bias, bn.running_mean, bn.running_var], fold)
-
     def conv2_pack(self, cache, Wp):
         """conv2 at pitch Wp: the grouped kernel's pack (refreshed in place after an optimizer step), or with one group a dense one."""
         conv = self.conv2
         if conv.groups == 1:
-            return self.padded_pack(cache, conv, Wp, Wp)
+            return packed_conv_padded(cache, conv, Wp, Wp)
         w = conv.weight
         return cache.get(('rg_pc2', id(conv), Wp), [w], lambda: ops.PackedConv(w, conv.stride[0], 1, groups=conv.groups, pitch=Wp),
                          lambda pc: _pack_job(pc, w))
@@ -141,25 +112,14 @@ class _RegBottleneck(_Block):
         assert x.dtype == torch.float32
         Ip, Wp, Pp = ops.pad32(self.inplanes), ops.pad32(self.width), ops.pad32(self.planes)
         assert x.shape[-1] == Ip, (tuple(x.shape), self.inplanes)
-        s1, b1 = self.padded_fold(cache, self.bn1, Wp)
-        o1 = ops.conv2d(x, self.padded_pack(cache, self.conv1, Wp, Ip), scale=s1, bias=b1, relu=True)
+        s1, b1 = folded_bn_padded(cache, self.bn1, Wp)
+        o1 = ops.conv2d(x, packed_conv_padded(cache, self.conv1, Wp, Ip), scale=s1, bias=b1, relu=True)
         if self.conv2.groups == 1:
-            s2, b2 = self.padded_fold(cache, self.bn2, Wp)
+            s2, b2 = folded_bn_padded(cache, self.bn2, Wp)
         else:
             s2, b2 = folded_bn(cache, self.bn2)          # (the grouped kernel reads the real channels' entries alone)
         o2 = ops.conv2d(o1, self.conv2_pack(cache, Wp), scale=s2, bias=b2, relu=True)
-        pc3 = self.padded_pack(cache, self.conv3, Pp, Wp)
-        s3, b3 = self.padded_fold(cache, self.bn3, Pp)
-        xp = self.shortcut_input(x) if self.downsample is not None else None      # avg_down: pad channels average to 0
-        if self.downsample is not None:
-            pcd = self.padded_pack(cache, self.ds_conv, Pp, Ip)
-            sd, bd = self.padded_fold(cache, self.ds_bn, Pp)
-            if save is None:      # forward only: the shortcut GEMM rides in conv3's launch (ops.conv2d_dual; the same bits)
-                return ops.conv2d_dual(o2, pc3, xp, pcd, scale=s3, bias=b3, scale2=sd, bias2=bd, relu=True)
-            identity = ops.conv2d(xp, pcd, scale=sd, bias=bd)
-        else:
-            identity = x
-        out = ops.conv2d(o2, pc3, scale=s3, bias=b3, residual=identity, relu=True)
+        out, xp = self.conv3_shortcut(cache, x, o2, Pp, save is not None)
         if save is not None:
             save.update(block=self, x=x, xp=xp, o1=o1, o2=o2, out=out)
         return out

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..layers import folded_bn, packed_conv
+from ..layers import folded_bn, folded_bn_padded, packed_conv_padded
 from ..registry import BACKBONES
 from .resnet import ResNet, _Block
 
@@ -51,10 +51,6 @@ def _not_mixed(scales):
                                'has no slice convolution' % scales)
 
 
-def _pad32(c):
-    return (c + 31) // 32 * 32
-
-
 class _Bottle2neck(_Block):
     """Bottle2neck (res2net.py:14-159).  Registration order conv1, bn1, conv3, bn3, downsample, convs, bns -- the reference's
     state-dict order; there is no conv2 / bn2.  stage_type 'stage': the first block of a stage (its convs read their own slice alone, and
@@ -76,41 +72,6 @@ class _Bottle2neck(_Block):
     def _norms(self):
         return [self.bn1, self.bn3] + list(self.bns) + ([self.ds_bn] if self.downsample is not None else [])
 
-    # ---- the 1x1 layers around the padded pitch: packs and folds with exact zeros in the pad rows / columns
-    def _conv1_padded(self, cache, Cp):
-        conv, bn = self.conv1, self.bn1
-        Wd = conv.out_channels
-        if Cp == Wd:
-            return (packed_conv(cache, conv),) + tuple(folded_bn(cache, bn))
-
-        def pack():
-            w = torch.zeros((Cp,) + tuple(conv.weight.shape[1:]), device=conv.weight.device, dtype=torch.float32)
-            w[:Wd].copy_(conv.weight.detach())
-            return ops.PackedConv(w, 1, 0)
-
-        def fold():
-            s, b = folded_bn(cache, bn)
-            sp, bp = s.new_zeros((Cp,)), b.new_zeros((Cp,))
-            sp[:Wd].copy_(s)
-            bp[:Wd].copy_(b)
-            return sp, bp
-        # (entries without a refresh job: they lapse with the weight epoch and rebuild from the refreshed parameters)
-        pc = cache.get(('r2_pc1', id(conv), Cp), [conv.weight], pack)
-        sp, bp = cache.get(('r2_bn1', id(bn), Cp), [bn.weight, bn.bias, bn.running_mean, bn.running_var], fold)
-        return pc, sp, bp
-
-    def _conv3_padded(self, cache, Cp):
-        conv = self.conv3
-        Wd = conv.in_channels
-        if Cp == Wd:
-            return packed_conv(cache, conv)
-
-        def pack():
-            w = torch.zeros((conv.out_channels, Cp, 1, 1), device=conv.weight.device, dtype=torch.float32)
-            w[:, :Wd].copy_(conv.weight.detach())
-            return ops.PackedConv(w, 1, 0)
-        return cache.get(('r2_pc3', id(conv), Cp), [conv.weight], pack)
-
     def run(self, cache, x, save=None):
         if self.batch_stats():
             raise NotImplementedError('BatchNorm batch statistics inside a Res2Net block (norm_eval=False with a stage that is not frozen): '
@@ -119,8 +80,10 @@ class _Bottle2neck(_Block):
             raise _not_mixed(self.scales)
         s, w, stride = self.scales, self.width, self.stride
         Wd = s * w
-        Cp = _pad32(Wd)
-        pc1, s1, b1 = self._conv1_padded(cache, Cp)
+        Cp = ops.pad32(Wd)
+        # the 1x1 layers around the padded pitch: packs and folds with exact zeros in the pad rows / columns
+        pc1 = packed_conv_padded(cache, self.conv1, Cp, self.conv1.in_channels)
+        s1, b1 = folded_bn_padded(cache, self.bn1, Cp)
         o1 = ops.conv2d(x, pc1, scale=s1, bias=b1, relu=True)                 # (N, H, W, Cp); channels >= Wd are relu(0 * 0 + 0) = 0
         N, H, W, _ = o1.shape
         OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
@@ -135,18 +98,7 @@ class _Bottle2neck(_Block):
             ops.res2_conv(o1, i * w, pk, cat, i * w, stride=stride, add=cat if carry else None, add_off=(i - 1) * w if carry else 0,
                           scale=si, bias=bi, relu=True)
         ops.res2_pool(o1, (s - 1) * w, cat, (s - 1) * w, w, stride)            # stride 2 ('stage' blocks only): the 3x3 average
-        pc3 = self._conv3_padded(cache, Cp)
-        s3, b3 = folded_bn(cache, self.bn3)
-        xp = self.shortcut_input(x) if self.downsample is not None else None
-        if self.downsample is not None and save is None:
-            # forward only: the shortcut GEMM rides in conv3's launch (ops.conv2d_dual, as the ResNet bottleneck's; the same bits)
-            sd, bd = folded_bn(cache, self.ds_bn)
-            return ops.conv2d_dual(cat, pc3, xp, packed_conv(cache, self.ds_conv), scale=s3, bias=b3, scale2=sd, bias2=bd, relu=True)
-        identity = x
-        if self.downsample is not None:      # the recorded forward keeps the two launches (its backward walks the recorded maps)
-            sd, bd = folded_bn(cache, self.ds_bn)
-            identity = ops.conv2d(xp, packed_conv(cache, self.ds_conv), scale=sd, bias=bd)
-        out = ops.conv2d(cat, pc3, scale=s3, bias=b3, residual=identity, relu=True)
+        out, xp = self.conv3_shortcut(cache, x, cat, self.conv3.out_channels, save is not None)
         if save is not None:
             save.update(block=self, x=x, xp=xp, o1=o1, cat=cat, out=out)
         return out

@@ -108,18 +108,7 @@ class _ResNeStBlock(_Block):
         r = ops.splat_attn(g, sa.fc1.weight, sa.fc1.bias, sm, bm, sa.fc2.weight, sa.fc2.bias, record=save is not None)
         att, z = r if save is not None else (r, None)
         o = ops.splat_apply(u, att, pool=self.pool)
-        s3, b3 = folded_bn(cache, self.bn3)
-        pc3 = packed_conv(cache, self.conv3)
-        xp = self.shortcut_input(x) if self.downsample is not None else None
-        if self.downsample is not None and save is None:
-            # forward only: the shortcut GEMM rides in conv3's launch (ops.conv2d_dual, as the ResNet bottleneck's; the same bits)
-            sd, bd = folded_bn(cache, self.ds_bn)
-            return ops.conv2d_dual(o, pc3, xp, packed_conv(cache, self.ds_conv), scale=s3, bias=b3, scale2=sd, bias2=bd, relu=True)
-        identity = x
-        if self.downsample is not None:      # the recorded forward keeps the two launches (its backward walks the recorded maps)
-            sd, bd = folded_bn(cache, self.ds_bn)
-            identity = ops.conv2d(xp, packed_conv(cache, self.ds_conv), scale=sd, bias=bd)
-        out = ops.conv2d(o, pc3, scale=s3, bias=b3, residual=identity, relu=True)
+        out, xp = self.conv3_shortcut(cache, x, o, self.conv3.out_channels, save is not None)
         if save is not None:
             save.update(block=self, x=x, xp=xp, o1=o1, u=u, g=g, z=z, att=att, o=o, out=out)
         return out

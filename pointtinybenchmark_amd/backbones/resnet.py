@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..layers import _PackCache, folded_bn, packed_conv
+from ..layers import _PackCache, folded_bn, folded_bn_padded, packed_conv, packed_conv_padded
 from ..registry import BACKBONES
 
 
@@ -112,6 +112,24 @@ class _Block(nn.Module):
         """What the projection shortcut's conv reads: the block input, or with avg_down its average-pooled map (ops.avgpool)."""
         k = self.ds_pool
         return ops.avgpool(x, k) if k else x
+
+    def conv3_shortcut(self, cache, x, o, Pp, record):
+        """conv3 -> folded bn3 (+ the shortcut) -> ReLU of a family block (Bottle2neck, ResNeSt, padded RegNet) whose conv3 reads ``o``,
+        output pitch Pp -> (out, xp: what the shortcut conv read, or None).  The maps may sit at a padded pitch: the packs and folds
+        come through the padded helpers, which fall through where nothing is padded.  Forward only (record False) the shortcut GEMM
+        rides in conv3's launch (ops.conv2d_dual, as the ResNet bottleneck's; the same bits); the recorded forward keeps the two
+        launches (its backward walks the recorded maps)."""
+        pc3 = packed_conv_padded(cache, self.conv3, Pp, o.shape[-1])
+        s3, b3 = folded_bn_padded(cache, self.bn3, Pp)
+        if self.downsample is None:
+            return ops.conv2d(o, pc3, scale=s3, bias=b3, residual=x, relu=True), None
+        xp = self.shortcut_input(x)      # avg_down: the pooled map (pad channels average to 0)
+        pcd = packed_conv_padded(cache, self.ds_conv, Pp, x.shape[-1])
+        sd, bd = folded_bn_padded(cache, self.ds_bn, Pp)
+        if not record:
+            return ops.conv2d_dual(o, pc3, xp, pcd, scale=s3, bias=b3, scale2=sd, bias2=bd, relu=True), xp
+        identity = ops.conv2d(xp, pcd, scale=sd, bias=bd)
+        return ops.conv2d(o, pc3, scale=s3, bias=b3, residual=identity, relu=True), xp
 
     def _norms(self):
         return [self.bn1, self.bn2] + ([self.bn3] if self.kind == 'bottleneck' else []) + \

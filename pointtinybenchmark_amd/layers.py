@@ -200,18 +200,30 @@ def packed_conv(cache, conv, dtype=torch.float32):
                      lambda pc: _pack_job(pc, conv.weight))
 
 
-def packed_conv_padded_in(cache, conv, Ip):
-    """The fp32 pack of ``conv`` for an input map kept at the channel pitch Ip = roundup(in_channels, 32) with exact-zero pad channels (a
-    RegNet stage output read in place, ops.as_nchw_padded): zero columns [in_channels, Ip).  (No refresh job: the entry lapses with the
-    weight epoch and rebuilds from the refreshed parameter.)"""
-    O, I = conv.weight.shape[:2]
-    assert Ip == ops.pad32(I) and Ip != I, (Ip, I)
+# ---- dense fp32 layers whose maps sit at a padded channel pitch (pad channels exact zeros: RegNet blocks, the Res2Net 1x1 layers, an
+# FPN lateral reading a RegNet stage in place): packs with zero rows / columns and folds with zero scale / shift in the pad.  None of
+# these entries has a refresh job: they lapse with the weight epoch and rebuild from the refreshed parameters.
+def _zero_embedded(weight, Op, Ip):
+    """``weight`` (O, I, k, k) in the corner of an (Op, Ip, k, k) tensor of zeros."""
+    O, I = weight.shape[:2]
+    w = torch.zeros((Op, Ip) + tuple(weight.shape[2:]), device=weight.device, dtype=torch.float32)
+    w[:O, :I].copy_(weight.detach())
+    return w
 
-    def pack():
-        w = torch.zeros((O, Ip) + tuple(conv.weight.shape[2:]), device=conv.weight.device, dtype=torch.float32)
-        w[:, :I].copy_(conv.weight.detach())
-        return ops.PackedConv(w, conv.stride[0], conv.padding[0])
-    return cache.get(('pc_padin', id(conv), Ip), [conv.weight], pack)
+
+def _zero_extended(t, Op):
+    tp = t.new_zeros((Op,))
+    tp[:t.numel()].copy_(t)
+    return tp
+
+
+def packed_conv_padded(cache, conv, Op, Ip):
+    """packed_conv of the dense ``conv`` (O, I, k, k) at (Op, Ip): rows >= O and columns >= I zero."""
+    if (Op, Ip) == tuple(conv.weight.shape[:2]):
+        return packed_conv(cache, conv)
+    assert conv.groups == 1
+    return cache.get(('pc_pad', id(conv), Op, Ip), [conv.weight],
+                     lambda: ops.PackedConv(_zero_embedded(conv.weight, Op, Ip), conv.stride[0], conv.padding[0]))
 
 
 def folded_bn(cache, bn):
@@ -229,6 +241,14 @@ def folded_bn(cache, bn):
                                        for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var, val[0], val[1]))
         return FoldJob(bn, val) if ok else None
     return cache.get(('bn', id(bn)), [bn.weight, bn.bias, bn.running_mean, bn.running_var], make, job)
+
+
+def folded_bn_padded(cache, bn, Op):
+    """folded_bn zero-extended to Op channels: relu(0 * 0 + 0) = 0 keeps the pad channels of the layer's output exact zeros."""
+    if Op == bn.weight.numel():
+        return folded_bn(cache, bn)
+    return cache.get(('bn_pad', id(bn), Op), [bn.weight, bn.bias, bn.running_mean, bn.running_var],
+                     lambda: tuple(_zero_extended(t, Op) for t in folded_bn(cache, bn)))
 
 
 def bn_inv_sigma(cache, bn):
@@ -267,6 +287,20 @@ def dgrad_packed(cache, conv, bn=None, dtype=torch.float32, pitch=None):
         fold = cache._jobs.get(('bn', id(bn)))
         return None if fold is None else _pack_job(pc, w, 1, fold)
     return cache.get(('dgrad', id(conv), dtype), [w, bn.weight, bn.running_var], make, job)
+
+
+def dgrad_packed_padded(cache, conv, bn, Op, Ip):
+    """dgrad_packed of the dense ``conv`` at (Op, Ip): the data gradient of maps at a padded pitch arrives padded, its pad channels exact
+    zeros (zero rows / columns, and a zero folded scale, in the pad).  bn None: no scale (a GroupNorm layer reading a padded map)."""
+    w = conv.weight
+    if (Op, Ip) == tuple(w.shape[:2]):
+        return dgrad_packed(cache, conv, bn)
+    assert conv.groups == 1
+    if bn is None:
+        return cache.get(('dgrad_pad_raw', id(conv), Op, Ip), [w], lambda: ops.dgrad_pack(_zero_embedded(w, Op, Ip), conv.stride[0], conv.padding[0]))
+    return cache.get(('dgrad_pad', id(conv), Op, Ip), [w, bn.weight, bn.running_var],
+                     lambda: ops.dgrad_pack(_zero_embedded(w, Op, Ip), conv.stride[0], conv.padding[0],
+                                            scale=_zero_extended(folded_bn(cache, bn)[0], Op)))
 
 
 class ConvModule(nn.Module):
@@ -327,8 +361,8 @@ def conv_gn(cache, m, x, in_ab=None, in_relu=False, materialize=True, up=None, s
     gn = m.norm
     blocked = ops.is_b8(x)
     if not blocked and x.shape[-1] != m.conv.in_channels:      # a backbone map at its padded pitch (the caller vouches for the zeros)
-        assert x.dtype == torch.float32 and in_ab is None
-        pc = packed_conv_padded_in(cache, m.conv, x.shape[-1])
+        assert x.dtype == torch.float32 and in_ab is None and x.shape[-1] == ops.pad32(m.conv.in_channels), (x.shape[-1], m.conv.in_channels)
+        pc = packed_conv_padded(cache, m.conv, m.conv.out_channels, x.shape[-1])
     else:
         pc = packed_conv(cache, m.conv, x.dtype)
     if blocked:

@@ -20,7 +20,7 @@ import torch.distributed as dist
 
 from . import ops
 from ._lib import CprHipError
-from .layers import _PackCache, bn_inv_sigma, bump_weight_epoch, dgrad_packed, folded_bn
+from .layers import _PackCache, bn_inv_sigma, bump_weight_epoch, dgrad_packed, dgrad_packed_padded, folded_bn
 
 
 class GradBuckets:
@@ -526,7 +526,7 @@ class BackwardEngine:
             x = self._f32(rec['x'])
             gw = self._g(w)
             if padded_in:
-                # the input is a backbone map at its padded pitch (layers.packed_conv_padded_in): the weight gradient at the padded
+                # the input is a backbone map at its padded pitch (layers.packed_conv_padded): the weight gradient at the padded
                 # shape into scratch, the real columns copied out
                 self._param_side(lambda: gw.copy_(ops.conv2d_wgrad(draw, x, (w.shape[0], x.shape[-1]) + tuple(w.shape[2:]), cm.conv.stride[0],
                                                                    cm.conv.padding[0])[:, :w.shape[1]]), draw, x)
@@ -536,14 +536,8 @@ class BackwardEngine:
         if not need_dx:
             return None
         if padded_in:      # the data gradient through a pack with zero columns in the pad: it arrives padded, pad channels exact zeros
-            Ip = rec['x'].shape[-1]
-
-            def make():
-                wp = torch.zeros((w.shape[0], Ip) + tuple(w.shape[2:]), device=w.device, dtype=torch.float32)
-                wp[:, :w.shape[1]].copy_(w.detach())
-                return ops.dgrad_pack(wp, cm.conv.stride[0], cm.conv.padding[0])
-            # (kept in the neck's pack cache beside the forward's packed_conv_padded_in; lapses with the weight epoch)
-            pt = _inner_neck(self.model.neck)._cache.get(('pc_padin_dgrad', id(cm.conv), Ip), [w], make)
+            # (kept in the neck's pack cache beside the forward's packed_conv_padded; lapses with the weight epoch)
+            pt = dgrad_packed_padded(_inner_neck(self.model.neck)._cache, cm.conv, None, w.shape[0], rec['x'].shape[-1])
             return ops.conv2d_dgrad(draw, pt, (rec['x'].shape[1], rec['x'].shape[2]), cm.conv.stride[0], add=add)
         if dgrad16:
             assert add is None, 'the bf16 data gradient has no summed operand'
@@ -941,45 +935,26 @@ class BackwardEngine:
         the same fp32 kernels (its byte map is the bf16 stem kernel's)."""
         c1, bn = bb.conv1, bb.bn1
         w = c1.weight
-        # any subset of (conv1.weight, bn1.weight, bn1.bias) may train: each gradient is written only where its parameter trains
-        dg_out = self._g(bn.weight) if bn.weight.requires_grad else None
-        db_out = self._g(bn.bias) if bn.bias.requires_grad else None
         x, planar = rec['x'], rec['planar']
+        # any subset of (conv1.weight, bn1.weight, bn1.bias) may train: each gradient is written only where its parameter trains
         if rec.get('regnet'):
             # the RegNet stem (conv1 3x3/2 -> bn1 -> ReLU, no pool; eval-mode bn1 only): ReLU backward + column sums in one pass, the
             # weight gradient of csrc/stem3x3_bwd.hip, then bn_fold_bwd as below
             dy, cs = ops.relu_bwd_colsum(dp, rec['out'])
-            cache = bb._cache
-            scale, _ = folded_bn(cache, bn)
-            inv_sigma = bn_inv_sigma(cache, bn)
-
-            def regnet_param_grads():
-                gw = self._g(w) if w.requires_grad else torch.empty(tuple(w.shape), device=dy.device, dtype=torch.float32)
-                ops.stem3x3s2_wgrad(dy, x, planar=planar, out=gw)
-                ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, cs, want_affine=False, out_dgamma=dg_out, out_dbeta=db_out)
-            self._param_side(regnet_param_grads, dy, cs, x)
+            self._folded_param_grads(bb._cache, c1, bn, cs, lambda gw: ops.stem3x3s2_wgrad(dy, x, planar=planar, out=gw), dy, x, stem=True)
             self._done([p for p in (w, bn.weight, bn.bias) if p.requires_grad][-1])
             return
         dy, part = ops.stem_pool_bwd(dp, rec['arg'], rec['conv_hw'])
         if rec.get('batch_stats'):
             st = rec['stats']
-            dconv, _, _ = ops.bn_train_bwd(dy, rec['y'], st.cmean, st.rstd, bn.weight, center=st.center, out_dgamma=dg_out,
-                                           out_dbeta=db_out, group=rec.get('group'), count=getattr(st, 'count', None))
+            dconv, _, _ = ops.bn_train_bwd(dy, rec['y'], st.cmean, st.rstd, bn.weight, center=st.center,
+                                           out_dgamma=self._g(bn.weight) if bn.weight.requires_grad else None,
+                                           out_dbeta=self._g(bn.bias) if bn.bias.requires_grad else None,
+                                           group=rec.get('group'), count=getattr(st, 'count', None))
             if w.requires_grad:
                 self._param_side(lambda: ops.stem_wgrad_f32(dconv, x, planar=planar, out=self._g(w)), dconv, x)
         else:
-            cache = bb._cache
-            scale, _ = folded_bn(cache, bn)
-            inv_sigma = bn_inv_sigma(cache, bn)
-
-            def param_grads():
-                # dgamma = inv_sigma * (sum(Gw * W) - mean * colsum): it needs Gw even when conv1 itself is frozen (then Gw goes to
-                # a scratch tensor -- the same kernels, so bn1's gradients are the same bits either way)
-                gw = self._g(w) if w.requires_grad else torch.empty(tuple(w.shape), device=dy.device, dtype=torch.float32)
-                ops.stem_wgrad_f32(dy, x, planar=planar, out=gw)
-                ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, part, want_affine=False, out_dgamma=dg_out,
-                                out_dbeta=db_out)
-            self._param_side(param_grads, dy, part, x)
+            self._folded_param_grads(bb._cache, c1, bn, part, lambda gw: ops.stem_wgrad_f32(dy, x, planar=planar, out=gw), dy, x, stem=True)
         self._done([p for p in (w, bn.weight, bn.bias) if p.requires_grad][-1])
 
     def _bf16_grads(self, conv, x, has_add, need_dx):
@@ -1002,6 +977,29 @@ class BackwardEngine:
         w16, d16 = self._bf16_grads(conv, x, has_add, need_dx)
         return self._mixed and (w16 or not conv.weight.requires_grad) and (d16 or not need_dx)
 
+    def _folded_param_grads(self, cache, conv, bn, colsum, wgrad, *tensors, stem=False):
+        """The parameter gradients of conv -> folded eval-BN, on the side stream: ``wgrad(gw)`` writes the raw weight gradient Gw of the
+        folded weight into gw, the weight's gradient; ops.bn_fold_bwd turns it into dW = scale * Gw in place and writes dgamma / dbeta
+        where bn.weight trains.  ``colsum``: the column sums of the output gradient (the TilePartials of a conv epilogue are summed
+        inside bn_fold_bwd); ``tensors``: what wgrad reads (_param_side).  The fold and 1 / sigma are looked up here, on the main
+        stream.  A frozen weight: nothing runs.  stem (the eval-mode stems, _backward_stem): any subset of (conv.weight, bn.weight,
+        bn.bias) may train -- dgamma = inv_sigma * (sum(Gw * W) - mean * colsum) needs Gw even when the conv is frozen (then Gw goes
+        to a scratch tensor: the same kernels, so bn's gradients are the same bits either way), and each of dgamma / dbeta is written
+        only where its own parameter trains."""
+        w = conv.weight
+        if not (stem or w.requires_grad):
+            return
+        scale, _ = folded_bn(cache, bn)
+        inv_sigma = bn_inv_sigma(cache, bn)
+
+        def param_grads():
+            gw = self._g(w) if w.requires_grad else torch.empty(tuple(w.shape), device=w.device, dtype=torch.float32)
+            wgrad(gw)
+            ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, colsum, want_affine=not stem,
+                            out_dgamma=self._g(bn.weight) if bn.weight.requires_grad else None,
+                            out_dbeta=self._g(bn.bias) if (bn.bias if stem else bn.weight).requires_grad else None)
+        self._param_side(param_grads, colsum, *tensors)
+
     def _conv_bn_backward(self, cache, conv, bn, g, colsum, x, need_dx, mask=None, add=None, want_colsum=False, g16=None, want16=False,
                           need32=True):
         """conv -> folded eval-BN given g = d(pre-activation output) (un-scaled) and its column sums.  Parameter
@@ -1014,28 +1012,20 @@ class BackwardEngine:
         consumer reads only the bf16 rounding, _reads_bf16_only): a bf16 data gradient with a mask then runs in the kernel's mask mode
         -- ReLU backward, bf16 rounding and column sums in its epilogue, no fp32 map, no streaming pass -- and returns
         (None, column-sum partials, gradient16).  g may be None when g16 is given and both gradients of this conv are bf16."""
-        scale, _ = folded_bn(cache, bn)
-        inv_sigma = bn_inv_sigma(cache, bn)
         w = conv.weight
         k = conv.kernel_size[0]
         w16, d16 = self._bf16_grads(conv, x, add is not None, need_dx)      # mixed precision: ONE bf16 copy of g feeds both
         if g16 is None and (w16 or d16):
             g16 = g.to(torch.bfloat16)
-        if w.requires_grad:
-            aff = bn.weight.requires_grad
 
-            def param_grads():
-                cs = colsum            # (TilePartials of a conv epilogue are summed inside bn_fold_bwd)
-                gw = self._g(w)
-                if w16:
-                    ops.conv_wgrad_bf16(g16, x, w.shape, out=gw, stride=conv.stride[0])    # (x: the bf16 recorded map, or a widened copy that rounds back exactly)
-                else:
-                    ops.conv2d_wgrad(g, self._f32(x), w.shape, conv.stride[0], conv.padding[0], out=gw, groups=conv.groups,
-                                     dilation=conv.dilation[0])
-                ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, cs,
-                                out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
-            # x may be a widened fp32 temporary of the mixed-precision step that the main stream frees right after this call
-            self._param_side(param_grads, g, colsum, g16, x)
+        def wgrad(gw):
+            if w16:
+                ops.conv_wgrad_bf16(g16, x, w.shape, out=gw, stride=conv.stride[0])    # (x: the bf16 recorded map, or a widened copy that rounds back exactly)
+            else:
+                ops.conv2d_wgrad(g, self._f32(x), w.shape, conv.stride[0], conv.padding[0], out=gw, groups=conv.groups,
+                                 dilation=conv.dilation[0])
+        # x may be a widened fp32 temporary of the mixed-precision step that the main stream frees right after this call
+        self._folded_param_grads(cache, conv, bn, colsum, wgrad, g, g16, x)
         if not need_dx:
             return None
 
@@ -1111,11 +1101,7 @@ class BackwardEngine:
             return self._resnest_block_backward(cache, blk, rec, dout, need_dx)
         mixed = self._mixed
         x = rec['x']
-        if isinstance(dout, tuple):
-            g3, cs3, g3h = dout
-        else:
-            r3 = ops.relu_bwd_colsum(dout, rec['out'], want16=mixed)          # also the shortcut gradient
-            g3, cs3, g3h = r3 if mixed else (r3[0], r3[1], None)
+        g3, cs3, g3h = self._out_relu_backward(rec, dout, want16=mixed)
         o1 = rec['o1']
         if blk.kind == 'bottleneck':
             o2 = rec['o2']
@@ -1131,82 +1117,59 @@ class BackwardEngine:
             last = blk.bn2
         del o1
         self._done(last.bias if last.bias.requires_grad else blk.conv2.weight)
-        if blk.downsample is not None:     # the shortcut conv sees the same g3 (no activation on that branch)
-            dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, g16=g1h)
+        if mask_in and need_dx and blk.downsample is None:
+            dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, True, mask=x, add=g3, want_colsum=True, g16=g1h, want16=mixed)
+            self._done(blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight)
+            return dx if mixed else (dx[0], dx[1], None)
+        return self._conv1_shortcut_backward(cache, blk, rec, g1, cs1, g3, cs3, need_dx, g1h=g1h, g3h=g3h)
+
+    def _out_relu_backward(self, rec, dout, want16=False):
+        """-> (g3, column sums, bf16 g3 | None): the gradient of a block's output taken through its output ReLU -- the gradient of
+        conv3's (a BasicBlock's conv2's) pre-activation output and of the shortcut alike.  ``dout`` is that triple already when the block
+        above has taken it through the ReLU (_block_backward, mask_in); want16 (the mixed step): the bf16 rounding from the same pass."""
+        if isinstance(dout, tuple):
+            return dout
+        r = ops.relu_bwd_colsum(dout, rec['out'], want16=want16)
+        return r if want16 else (r[0], r[1], None)
+
+    def _conv1_shortcut_backward(self, cache, blk, rec, g1, cs1, g3, cs3, need_dx, g1h=None, g3h=None, padded=False):
+        """The end of a folded block's walk: conv1's rule given g1 = d(conv1's pre-activation output), the shortcut -- an identity (g3
+        summed into conv1's data gradient) or the projection conv, which sees the same g3 (no activation on that branch) -- and the
+        block's last ``_done``.  -> the gradient wrt the block input.  g1h / g3h: the bf16 roundings of g1 / g3 where the producer wrote
+        them (the base block's mixed step); padded: the block's maps sit at a padded pitch (_padded_conv_bn_backward)."""
+        rule = self._padded_conv_bn_backward if padded else self._conv_bn_backward
+        x = rec['x']
+        if blk.downsample is None:
+            dx = rule(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3, g16=g1h)
+            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
+        else:
+            dx = rule(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, g16=g1h)
             pool = blk.ds_pool
             if pool:
                 # avg_down: the shortcut conv read the pooled map xp (its weight gradient does too); its data gradient is a plain
                 # stride-1 1x1 (the bf16 pipe's plain case in the mixed step), spread back over the windows by avgpool_bwd with
                 # the conv1-branch gradient summed in the same pass
-                dxp = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, rec['xp'], need_dx, g16=g3h)
+                dxp = rule(cache, blk.ds_conv, blk.ds_bn, g3, cs3, rec['xp'], need_dx, g16=g3h)
                 if need_dx:
                     dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
             else:
-                dx = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx, g16=g3h)
+                dx = rule(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx, g16=g3h)
             tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
-        elif mask_in and need_dx:
-            dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, True, mask=x, add=g3, want_colsum=True, g16=g1h, want16=mixed)
-            dx = dx if mixed else (dx[0], dx[1], None)
-            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
-        else:
-            dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3, g16=g1h)
-            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
         self._done(tail)
         return dx
 
     # ------------------------------------------------------------------ Res2Net (backbones/res2net.py; fp32, eval-mode BatchNorm)
-    def _r2_pointwise_backward(self, cache, conv, bn, g, colsum, x, need_dx, add=None):
-        """A 1x1 conv -> folded eval-BN of a Bottle2neck whose output (conv1) or input (conv3) map sits at the padded pitch: g =
-        d(pre-activation output) and x are maps as the kernels wrote them (pad channels exact zeros), ``colsum`` the column sums of g's
-        real channels.  The weight gradient is taken at the padded shape into a scratch tensor and its real rows / columns copied to the
-        parameter's gradient -- pad channels reach no parameter and no statistic; the data gradient runs through a pack with zero
-        rows / columns (and a zero folded scale) in the pad."""
-        w = conv.weight
-        O, I = w.shape[:2]
-        Op, Ip = g.shape[-1], x.shape[-1]
-        padded = (Op, Ip) != (O, I)
-        scale, _ = folded_bn(cache, bn)
-        inv_sigma = bn_inv_sigma(cache, bn)
-        if w.requires_grad:
-            aff = bn.weight.requires_grad
-
-            def param_grads():
-                gw = self._g(w)
-                if padded:
-                    gw.copy_(ops.conv2d_wgrad(g, x, (Op, Ip, 1, 1), 1, 0)[:O, :I])
-                else:
-                    ops.conv2d_wgrad(g, x, w.shape, 1, 0, out=gw)
-                ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, colsum,
-                                out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
-            self._param_side(param_grads, g, colsum, x)
-        if not need_dx:
-            return None
-        if padded:
-            def make():
-                wp = torch.zeros((Op, Ip, 1, 1), device=w.device, dtype=torch.float32)
-                wp[:O, :I].copy_(w.detach())
-                sp = scale.new_zeros((Op,))
-                sp[:O].copy_(scale)
-                return ops.dgrad_pack(wp, 1, 0, scale=sp)
-            pt = cache.get(('r2_dgrad', id(conv), Op, Ip), [w, bn.weight, bn.running_var], make)      # (lapses with the weight epoch)
-        else:
-            pt = dgrad_packed(cache, conv, bn)
-        return ops.conv2d_dgrad(g, pt, (x.shape[1], x.shape[2]), 1, add=add)
-
     def _bottle2neck_backward(self, cache, blk, rec, dout, need_dx):
         """The Bottle2neck rule.  G = d(concatenated map) out of conv3's data gradient; walking i = scales-2 .. 0: g_i = (G[slice i] +
         carry) * (y[i] > 0) in place with its column sums (ops.res2_relu_bwd; carry = the data gradient of conv i+1, which read y[i] in
         a 'normal' block), weight gradient and bn_fold_bwd of convs[i] / bns[i] on the side stream, data gradient into d(conv1
         output)[slice i]; the last slice's gradient passes through (or through the pool's backward); then conv1's rule."""
-        x, o1, cat = rec['x'], rec['o1'], rec['cat']
-        if isinstance(dout, tuple):
-            g3, cs3 = dout[0], dout[1]
-        else:
-            g3, cs3 = ops.relu_bwd_colsum(dout, rec['out'])          # also the shortcut gradient
+        o1, cat = rec['o1'], rec['cat']
+        g3, cs3, _ = self._out_relu_backward(rec, dout)          # also the shortcut gradient
         s, w, stride = blk.scales, blk.width, blk.stride
         Wd, Cp = s * w, o1.shape[-1]
         normal = blk.stage_type == 'normal'
-        G = self._r2_pointwise_backward(cache, blk.conv3, blk.bn3, g3, cs3, cat, True)
+        G = self._padded_conv_bn_backward(cache, blk.conv3, blk.bn3, g3, cs3, cat, True)
         d1 = (torch.zeros if Cp != Wd else torch.empty)(tuple(o1.shape), device=o1.device, dtype=torch.float32)
         for i in range(s - 2, -1, -1):
             conv, bn = blk.convs[i], blk.bns[i]
@@ -1214,15 +1177,8 @@ class BackwardEngine:
             cs = ops.res2_relu_bwd(G, i * w, cat, i * w, w, carry=d1 if carry else None, carry_off=(i + 1) * w)
             scale, _ = folded_bn(cache, bn)
             summed = normal and i > 0                 # the forward conv read o1[slice i] + y[i - 1]
-            if conv.weight.requires_grad:
-                aff = bn.weight.requires_grad
-
-                def param_grads(i=i, conv=conv, bn=bn, cs=cs, scale=scale, summed=summed, aff=aff):
-                    gw = self._g(conv.weight)
-                    ops.res2_wgrad(G, i * w, o1, i * w, w, stride, add=cat if summed else None, add_off=(i - 1) * w if summed else 0, out=gw)
-                    ops.bn_fold_bwd(gw, conv.weight, scale, bn.running_mean, bn_inv_sigma(cache, bn), cs,
-                                    out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
-                self._param_side(param_grads, G, o1, cat, cs)
+            self._folded_param_grads(cache, conv, bn, cs, lambda gw, i=i, summed=summed: ops.res2_wgrad(
+                G, i * w, o1, i * w, w, stride, add=cat if summed else None, add_off=(i - 1) * w if summed else 0, out=gw), G, o1, cat)
             pt = cache.get(('r2_packT', id(conv)), [conv.weight, bn.weight, bn.running_var],
                            lambda conv=conv, scale=scale: ops.Res2Pack(conv.weight, scale=scale, transpose=True))
             ops.res2_conv(G, i * w, pt, d1, i * w, stride=stride, transposed=True)
@@ -1230,21 +1186,7 @@ class BackwardEngine:
         g1, cs1 = ops.relu_bwd_colsum(d1, o1)                        # conv1's ReLU; the pad channels stay 0
         cs1 = cs1[:Wd]
         del G, d1
-        if blk.downsample is not None:
-            dx = self._r2_pointwise_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx)
-            pool = blk.ds_pool
-            if pool:
-                dxp = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, rec['xp'], need_dx)
-                if need_dx:
-                    dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
-            else:
-                dx = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx)
-            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
-        else:
-            dx = self._r2_pointwise_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3)
-            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
-        self._done(tail)
-        return dx
+        return self._conv1_shortcut_backward(cache, blk, rec, g1, cs1, g3, cs3, need_dx, padded=True)
 
     # ------------------------------------------------------------------ ResNeSt (backbones/resnest.py; fp32, eval-mode BatchNorm)
     def _resnest_block_backward(self, cache, blk, rec, dout, need_dx):
@@ -1254,11 +1196,8 @@ class BackwardEngine:
         * (u > 0) with its column sums (ops.splat_apply_bwd); then conv2.conv / bn0 as a dense conv -> folded BN -- the weight
         gradient taken dense into scratch and the two diagonal blocks copied to the parameter's gradient, the data gradient through
         the pack of the same block-diagonal weight -- and conv1's rule with the shortcut."""
-        x, o1, u = rec['x'], rec['o1'], rec['u']
-        if isinstance(dout, tuple):
-            g3, cs3 = dout[0], dout[1]
-        else:
-            g3, cs3 = ops.relu_bwd_colsum(dout, rec['out'])          # also the shortcut gradient
+        o1, u = rec['o1'], rec['u']
+        g3, cs3, _ = self._out_relu_backward(rec, dout)          # also the shortcut gradient
         sa, w = blk.conv2, blk.width
         do = self._conv_bn_backward(cache, blk.conv3, blk.bn3, g3, cs3, rec['o'], True)
         self._done(blk.bn3.bias if blk.bn3.bias.requires_grad else blk.conv3.weight)
@@ -1271,84 +1210,47 @@ class BackwardEngine:
         del do, datt, dg
         conv, bn = sa.conv, sa.bn0
         scale, _ = folded_bn(cache, bn)
-        if conv.weight.requires_grad:
-            aff = bn.weight.requires_grad
 
-            def param_grads():
-                gw = self._g(conv.weight)
-                dense = ops.conv2d_wgrad(du, o1, (2 * w, w, 3, 3), 1, 1)
-                gw[:w].copy_(dense[:w, :w // 2])
-                gw[w:].copy_(dense[w:, w // 2:])
-                ops.bn_fold_bwd(gw, conv.weight, scale, bn.running_mean, bn_inv_sigma(cache, bn), csu,
-                                out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
-            self._param_side(param_grads, du, csu, o1)
+        def wgrad(gw):
+            dense = ops.conv2d_wgrad(du, o1, (2 * w, w, 3, 3), 1, 1)
+            gw[:w].copy_(dense[:w, :w // 2])
+            gw[w:].copy_(dense[w:, w // 2:])
+        self._folded_param_grads(cache, conv, bn, csu, wgrad, du, o1)
         pt = cache.get(('st_dgrad', id(conv)), [conv.weight, bn.weight, bn.running_var],
                        lambda: ops.dgrad_pack(ops.splat_dense_weight(conv.weight), 1, 1, scale=scale))      # (lapses with the weight epoch)
         g1, cs1 = ops.relu_bwd_colsum(ops.conv2d_dgrad(du, pt, (o1.shape[1], o1.shape[2]), 1), o1)      # conv1's ReLU
         del du
         self._done(bn.bias if bn.bias.requires_grad else conv.weight)
-        if blk.downsample is not None:
-            dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx)
-            pool = blk.ds_pool
-            if pool:
-                dxp = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, rec['xp'], need_dx)
-                if need_dx:
-                    dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
-            else:
-                dx = self._conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx)
-            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
-        else:
-            dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3)
-            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
-        self._done(tail)
-        return dx
+        return self._conv1_shortcut_backward(cache, blk, rec, g1, cs1, g3, cs3, need_dx)
 
-    # ------------------------------------------------------------------ RegNet (backbones/regnet.py; fp32, eval-mode BatchNorm)
-    def _padded_conv_bn_backward(self, cache, conv, bn, g, colsum, x, need_dx, add=None):
-        """A dense conv (1x1 at either stride, or the 3x3 of a one-group block) -> folded eval-BN of a RegNet block whose maps sit at a
-        padded pitch: _r2_pointwise_backward with the layer's own kernel size, stride and padding.  g = d(pre-activation output) and
-        x are maps as the kernels wrote them (pad channels exact zeros), ``colsum`` the column sums of g's real channels.  Weight
-        gradient at the padded shape into scratch, real rows / columns copied out; data gradient through a pack with zero rows /
-        columns (and a zero folded scale) in the pad, so its pad channels are exact zeros."""
+    # ------------------------------------------------------------------ maps at a padded pitch; RegNet (backbones/regnet.py; fp32, eval-mode BatchNorm)
+    def _padded_conv_bn_backward(self, cache, conv, bn, g, colsum, x, need_dx, add=None, **kw):
+        """A dense conv (1x1 at either stride, or the 3x3 of a one-group RegNet block) -> folded eval-BN whose output or input map sits at
+        a padded pitch (RegNet blocks; conv1 and conv3 of a Bottle2neck): g = d(pre-activation output) and x are maps as the kernels
+        wrote them (pad channels exact zeros), ``colsum`` the column sums of g's real channels.  The weight gradient is taken at the
+        padded shape into a scratch tensor and its real rows / columns copied to the parameter's gradient -- pad channels reach no
+        parameter and no statistic; the data gradient runs through a pack with zero rows / columns (and a zero folded scale) in the
+        pad (layers.dgrad_packed_padded), so its pad channels are exact zeros.  Nothing padded: _conv_bn_backward, ``kw`` its."""
         w = conv.weight
         O, I = w.shape[:2]
         Op, Ip = g.shape[-1], x.shape[-1]
         stride, pad = conv.stride[0], conv.padding[0]
         if (Op, Ip) == (O, I):
-            return self._conv_bn_backward(cache, conv, bn, g, colsum, x, need_dx, add=add)
-        scale, _ = folded_bn(cache, bn)
-        inv_sigma = bn_inv_sigma(cache, bn)
-        if w.requires_grad:
-            aff = bn.weight.requires_grad
-
-            def param_grads():
-                gw = self._g(w)
-                gw.copy_(ops.conv2d_wgrad(g, x, (Op, Ip) + tuple(w.shape[2:]), stride, pad)[:O, :I])
-                ops.bn_fold_bwd(gw, w, scale, bn.running_mean, inv_sigma, colsum,
-                                out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
-            self._param_side(param_grads, g, colsum, x)
+            return self._conv_bn_backward(cache, conv, bn, g, colsum, x, need_dx, add=add, **kw)
+        assert all(v is None or v is False for v in kw.values()), list(kw)      # (the padded layers are fp32: no bf16 map, no mask or column-sum epilogue)
+        self._folded_param_grads(cache, conv, bn, colsum, lambda gw: gw.copy_(
+            ops.conv2d_wgrad(g, x, (Op, Ip) + tuple(w.shape[2:]), stride, pad)[:O, :I]), g, x)
         if not need_dx:
             return None
-
-        def make():
-            wp = torch.zeros((Op, Ip) + tuple(w.shape[2:]), device=w.device, dtype=torch.float32)
-            wp[:O, :I].copy_(w.detach())
-            sp = scale.new_zeros((Op,))
-            sp[:O].copy_(scale)
-            return ops.dgrad_pack(wp, stride, pad, scale=sp)
-        pt = cache.get(('rg_dgrad', id(conv), Op, Ip), [w, bn.weight, bn.running_var], make)      # (lapses with the weight epoch)
-        return ops.conv2d_dgrad(g, pt, (x.shape[1], x.shape[2]), stride, add=add)
+        return ops.conv2d_dgrad(g, dgrad_packed_padded(cache, conv, bn, Op, Ip), (x.shape[1], x.shape[2]), stride, add=add)
 
     def _regnet_block_backward(self, cache, blk, rec, dout, need_dx):
         """The rule of a padded RegNet block (kind 'regnet'): the bottleneck's walk conv3 -> conv2 -> conv1 (+ shortcut) on maps at the
         padded pitch.  Every gradient map keeps exact zeros in its pad channels: a ReLU mask there is 0, the dense data gradients run
         through packs with zero rows, the grouped data gradient writes them itself; column sums are cut to the real channels."""
-        x, o1, o2 = rec['x'], rec['o1'], rec['o2']
+        o1, o2 = rec['o1'], rec['o2']
         W, P = blk.width, blk.planes
-        if isinstance(dout, tuple):
-            g3, cs3 = dout[0], dout[1]
-        else:
-            g3, cs3 = ops.relu_bwd_colsum(dout, rec['out'])          # also the shortcut gradient
+        g3, cs3, _ = self._out_relu_backward(rec, dout)          # also the shortcut gradient
         cs3 = cs3[:P]
         d2 = self._padded_conv_bn_backward(cache, blk.conv3, blk.bn3, g3, cs3, o2, True)
         g2, cs2 = ops.relu_bwd_colsum(d2, o2)
@@ -1358,38 +1260,15 @@ class BackwardEngine:
         if conv.groups == 1:
             d1 = self._padded_conv_bn_backward(cache, conv, bn, g2, cs2, o1, True)
         else:
-            w = conv.weight
-            scale, _ = folded_bn(cache, bn)
-            if w.requires_grad:
-                aff = bn.weight.requires_grad
-
-                def param_grads():
-                    gw = self._g(w)
-                    ops.conv2d_wgrad(g2, o1, w.shape, conv.stride[0], 1, out=gw, groups=conv.groups)
-                    ops.bn_fold_bwd(gw, w, scale, bn.running_mean, bn_inv_sigma(cache, bn), cs2,
-                                    out_dgamma=self._g(bn.weight) if aff else None, out_dbeta=self._g(bn.bias) if aff else None)
-                self._param_side(param_grads, g2, cs2, o1)
+            self._folded_param_grads(cache, conv, bn, cs2, lambda gw: ops.conv2d_wgrad(
+                g2, o1, conv.weight.shape, conv.stride[0], 1, out=gw, groups=conv.groups), g2, o1)
             pt = dgrad_packed(cache, conv, bn, pitch=o1.shape[-1])
             d1 = ops.conv2d_dgrad(g2, pt, (o1.shape[1], o1.shape[2]), conv.stride[0])
         g1, cs1 = ops.relu_bwd_colsum(d1, o1)
         cs1 = cs1[:W]
         del d1
         self._done(blk.bn3.bias if blk.bn3.bias.requires_grad else blk.conv2.weight)
-        if blk.downsample is not None:
-            dx = self._padded_conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx)
-            pool = blk.ds_pool
-            if pool:
-                dxp = self._padded_conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, rec['xp'], need_dx)
-                if need_dx:
-                    dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
-            else:
-                dx = self._padded_conv_bn_backward(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx)
-            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
-        else:
-            dx = self._padded_conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3)
-            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
-        self._done(tail)
-        return dx
+        return self._conv1_shortcut_backward(cache, blk, rec, g1, cs1, g3, cs3, need_dx, padded=True)
 
     # ------------------------------------------------------------------ training-mode BatchNorm (ResNet norm_eval=False)
     def _conv_bn_backward_batch_stats(self, cache, conv, bn, rec, key, g, mask, x, need_dx, add=None):
