@@ -210,14 +210,11 @@ def check(name, got, ref, bar, m=None, Cout=None, bm=None, OHW=None):
     return worst
 
 
-def slot_refs(r, m, slots, slot, M):
-    """fp64 (sum, sumsq) per channel of each whole slot, and their bars (see the module docstring).
-    Returns (ref (len(slots), C, 2), bar (len(slots), C, 2))."""
-    t, e = r['ref'], r['bar32']
-    pos = {int(v): i for i, v in enumerate(np.asarray(m))}
+def group_refs(t, e, groups):
+    """fp64 (sum, sumsq) per channel over each group of rows of t (P, C) -- ``groups``: index tensors into the rows -- and their bars
+    from the per-element bars e (see the module docstring).  Returns (ref (len(groups), C, 2), bar (len(groups), C, 2))."""
     refs, bars = [], []
-    for s in slots:
-        idx = torch.as_tensor([pos[p] for p in range(s * slot, min((s + 1) * slot, M))])
+    for idx in groups:
         ts, es = t[idx], e[idx]
         n = len(idx)
         a = ts.abs() + es
@@ -227,3 +224,10 @@ def slot_refs(r, m, slots, slot, M):
         refs.append(torch.stack([s_ref, q_ref], -1))
         bars.append(torch.stack([s_bar, q_bar], -1))
     return torch.stack(refs), torch.stack(bars)
+
+
+def slot_refs(r, m, slots, slot, M):
+    """fp64 (sum, sumsq) per channel of each whole slot, and their bars (see the module docstring).
+    Returns (ref (len(slots), C, 2), bar (len(slots), C, 2))."""
+    pos = {int(v): i for i, v in enumerate(np.asarray(m))}
+    return group_refs(r['ref'], r['bar32'], [torch.as_tensor([pos[p] for p in range(s * slot, min((s + 1) * slot, M))]) for s in slots])

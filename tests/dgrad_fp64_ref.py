@@ -27,7 +27,10 @@ returns dict(ref, bar32), the contract of conv_fp64_ref.reference / slot_refs.  
 * column sums over n summands (a slot, or all pixels for the reduced vector): any order of fp32 additions errs by at most
   ``(n - 1) * U32 * sum (|t_p| + e_p)``, so ``sum e_p + (n - 1) * U32 * sum (|t_p| + e_p) + ULP32 * |sum|`` (``colsum_ref``; per slot
   it is conv_fp64_ref.slot_refs plus the last term).  It bounds the epilogue partials and the streaming relu_bwd_colsum pass alike.
-* Winograd route: no per-element bound is derivable; the project's stated one (tests/test_gpu_wino.py): ``1e-5 * max |ref|``.
+* Winograd route: the project's stated whole-map bound (tests/test_gpu_wino.py), ``1e-5 * max |ref|``, AND beside it the per-element
+  Winograd bound of tests/wino_fp64_ref.py (its bar 1): the route runs the two forward Winograd kernels on dy with a flipped pack, so
+  ``bar_wino = ACC_REL * mag_wino`` with ``mag_wino`` the magnitude of that forward convolution carried through the transforms with
+  absolute coefficients (``wino_magnitude``), ``+ U32 * mag_wino`` for a folded scale.  Both are asserted.
 """
 import numpy as np
 import torch
@@ -132,12 +135,21 @@ def rows(t, m=None):
     return t.cpu().double()
 
 
-def finish(t, mag, add=None, mask=None, scaled=False, bf16=False, wino=False):
+def wino_magnitude(dy, ws, m):
+    """``mag_wino`` (len(m), Cin) of the data gradient as the Winograd route computes it: the 3x3 / pad 1 FORWARD convolution of dy with
+    the pack's weights w'[ci, co, a, b] = ws[co, ci, 2 - a, 2 - b], through wino_fp64_ref.magnitude."""
+    from tests import wino_fp64_ref as WR
+    return WR.magnitude(dy, ws.flip(2, 3).transpose(0, 1).contiguous(), m)
+
+
+def finish(t, mag, add=None, mask=None, scaled=False, bf16=False, wino=False, mag_wino=None):
     """Add, then mask, and the per-element bar.  t, mag, add, mask: (P, C) fp64 rows on one device.  scaled: a scale was folded into an
-    fp32 pack; bf16: t was computed from ``bf16_operands``; wino: the Winograd route's bar.  Returns dict(ref, bar32)."""
+    fp32 pack; bf16: t was computed from ``bf16_operands``; wino: the Winograd route's bars (mag_wino: ``wino_magnitude`` at the same
+    pixels).  Returns dict(ref, bar32), on the Winograd route also bar_wino."""
     if wino:
-        assert add is None and mask is None and not bf16
-        return dict(ref=t, bar32=torch.full_like(t, WINO_REL * float(t.abs().max())))
+        assert add is None and mask is None and not bf16 and mag_wino is not None
+        return dict(ref=t, bar32=torch.full_like(t, WINO_REL * float(t.abs().max())),
+                    bar_wino=(ACC_REL + (U32 if scaled else 0.0)) * mag_wino)
     bar = ACC_REL * mag
     if scaled and not bf16:
         bar = bar + U32 * mag

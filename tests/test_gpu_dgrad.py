@@ -275,11 +275,15 @@ def test_dgrad_route_vs_fp64(c):
     else:
         m, slots = np.arange(M), (list(range(_cdiv(M, slot))) if slot else [])
         t, mag = D.full_map(dy, ws, s, p, (H, W))
+    if want == 'wino':
+        kw['mag_wino'] = D.wino_magnitude(dy, ws, m)
     r = D.finish(t, mag, None if add is None else D.rows(add, m), None if mask is None else D.rows(mask, m), **kw)
     worst = worst16 = worst_s = worst_cs = 0.0
     if g['out'] is not None:
         got = D.rows(g['out'], m)
         worst = D.check(name, got, r['ref'], r['bar32'], m=m, OHW=(H, W))
+        if want == 'wino':      # the per-element Winograd bound beside the whole-map one
+            print('\nDGRAD wino per-element bound: worst %.4f' % D.check(name + ' Winograd bound', got, r['ref'], r['bar_wino'], m=m, OHW=(H, W)))
         # pixels no tap reaches (the odd rows and columns of a 1x1 / stride 2 layer, the last row and column of its even map among
         # them: the forward never read them): exactly 0, or exactly the add
         dead = (mag == 0).all(1)
