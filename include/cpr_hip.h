@@ -574,6 +574,42 @@ int cpr_splat_attn_bwd(const float* att, const float* datt, const float* z, cons
  * (chunks of an image, then images, ascending).  ws: N * chunks * 2w + N * 2w floats. */
 int cpr_splat_apply_bwd(const float* dout, const float* u, const float* att, const float* dg, float* du, float* colsum, float* ws, int N,
                         int H, int W, int w, int pool, void* stream);
+/* MobileNetV2 (T/mmdet/models/backbones/mobilenet_v2.py, T/mmdet/models/utils/inverted_residual.py; csrc/mbv2.hip): the depthwise 3x3
+ * convolution (groups == channels), padding 1, stride 1 or 2, and the ReLU6 passes around it.  fp32 NHWC maps at the channel pitch
+ * Cp = roundup(C, 32), C % 8 == 0: pad channels [C, Cp) of an input are never read, pad channels of an output are written as +0.0.  No
+ * atomics: every element is a fixed-order sum (bit-repeatable, an image of a batch equals its single-image run); reductions over pixels
+ * go through per-workgroup partials in a caller-allocated workspace, added in ascending order by a second kernel.  A shape outside
+ * these rules, another stride or an undefined flag bit: CPR_ERR_ARG before any launch.
+ * cpr_dw3x3_pack: w (C,1,3,3) -> wp [9][Cp] tap-major, pad 0, scale[c] (optional) multiplied in (the data-gradient pack carries the
+ *   folded BatchNorm scale); run again on the same buffers it overwrites the pack in place (the backbone rebuilds its packs instead). */
+#define CPR_DW_IN_CLAMP6 1 /* the input is read as min(x, 6): its producer's epilogue wrote ReLU(v), the upper clamp happens on load */
+#define CPR_DW_RELU6 2     /* out = min(max(v, 0), 6) */
+int cpr_dw3x3_pack(const float* w, const float* scale, float* wp, int C, void* stream);
+/* y (N,OH,OW) = act(scale[c] * sum_{kh,kw} in(x)[n, oh s + kh - 1, ow s + kw - 1, c] * w[c,kh,kw] + bias[c]), zero outside the map,
+ * (OH, OW) = ((H - 1) / s + 1, (W - 1) / s + 1); scale / bias (C) may be NULL (both NULL, flags 0: the raw form). */
+int cpr_dw3x3_fwd(const float* x, const float* wp, const float* scale, const float* bias, float* y, int N, int H, int W, int C, int stride,
+                  int flags, void* stream);
+/* dx (N,H,W) = sum over the taps with (h + 1 - kh) % s == 0, (w + 1 - kw) % s == 0 and the quotient in range of
+ * dy[n, (h + 1 - kh) / s, (w + 1 - kw) / s, c] * wp[kh,kw,c] -- the gather form, no zero insertion; dy (N,(H-1)/s+1,(W-1)/s+1).
+ * add (optional, dx's shape) is summed in, then mask (optional, dx's shape: the ReLU(v) map of the layer's producer) keeps the element
+ * where 0 < mask < 6 (both strict, torch's hardtanh backward).  colsum (optional, (C)): the per-channel sums of dx; then ws holds
+ * cpr_dw3x3_dgrad_workspace(N, H, W, C) floats. */
+int cpr_dw3x3_dgrad_workspace(int N, int H, int W, int C);
+int cpr_dw3x3_dgrad(const float* dy, const float* wp, const float* add, const float* mask, float* dx, float* colsum, float* ws, int N, int H,
+                    int W, int C, int stride, void* stream);
+/* grad_w (C,1,3,3) (+)= sum_{n,oh,ow} dy[n,oh,ow,c] * in(x)[n, oh s + kh - 1, ow s + kw - 1, c]; x (N,H,W), in_clamp6 (0 / 1) reads
+ * min(x, 6); accumulate (0 / 1): one more rounded addition onto grad_w.  ws: cpr_dw3x3_wgrad_workspace(N, H, W, C, stride) floats. */
+int cpr_dw3x3_wgrad_workspace(int N, int H, int W, int C, int stride);
+int cpr_dw3x3_wgrad(const float* dy, const float* x, float* grad_w, float* ws, int N, int H, int W, int C, int stride, int in_clamp6,
+                    int accumulate, void* stream);
+/* The ReLU6 twin of cpr_relu_bwd_colsum: g = (dy (+ add)) * (0 < y < 6) and colsum (C) = its per-channel sums; (M,C) row-major,
+ * C % 4 == 0.  y is a clamped map or the ReLU(v) map (the predicate is the same).  y NULL: the column sums of dy alone (g_out may then
+ * be NULL, add must be).  ws: cpr_relu6_bwd_colsum_ws(M, C) floats. */
+int cpr_relu6_bwd_colsum_ws(long long M, int C);
+int cpr_relu6_bwd_colsum(const float* dy, const float* add, const float* y, float* g_out, float* colsum, float* ws, long long M, int C,
+                         void* stream);
+/* x = min(x, 6) in place over n floats (n % 4 == 0): a ReLU(v) map that leaves the backbone with no clamping consumer */
+int cpr_clamp6(float* x, long long n, void* stream);
 /* FPN extra pyramid levels (fpn.py:195-217; csrc/fpn_extra.hip), NHWC, 16 bytes of channels per lane.
  * cpr_subsample2: out (N,(H+1)/2,(W+1)/2,C) = y[:, ::2, ::2, :] with y = x, or x*a[n,c] + b[n,c] when a/b (N,C) are given (the producer's
  * pending GroupNorm affine, cpr_gn_apply's arithmetic) -- F.max_pool2d(y, 1, stride=2) bit for bit.  x/out fp32 (C%4==0) or bf16

@@ -148,6 +148,15 @@ SIGNATURES = {
     'cpr_splat_attn_grad': [_p] * 4 + [_i] * 5 + [_p],
     'cpr_splat_attn_bwd': [_p] * 18 + [_i] * 3 + [_p],
     'cpr_splat_apply_bwd': [_p] * 7 + [_i] * 5 + [_p],
+    'cpr_dw3x3_pack': [_p, _p, _p, _i, _p],
+    'cpr_dw3x3_fwd': [_p] * 5 + [_i] * 6 + [_p],
+    'cpr_dw3x3_dgrad_workspace': [_i] * 4,
+    'cpr_dw3x3_dgrad': [_p] * 7 + [_i] * 5 + [_p],
+    'cpr_dw3x3_wgrad_workspace': [_i] * 5,
+    'cpr_dw3x3_wgrad': [_p] * 4 + [_i] * 7 + [_p],
+    'cpr_relu6_bwd_colsum_ws': [_l, _i],
+    'cpr_relu6_bwd_colsum': [_p] * 6 + [_l, _i, _p],
+    'cpr_clamp6': [_p, _l, _p],
     'cpr_spin': [ctypes.c_longlong, _p],
     'cpr_bn_fold': [_p, _p, _p, _p, _f, _p, _p, _p, _i, _p],
     'cpr_bn_train_ws': [_l, _i],

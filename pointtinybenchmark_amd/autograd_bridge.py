@@ -127,10 +127,12 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
         return 'the mixed-precision step (bf16 compute mode) covers the CPR and P2P locators'
     if any(p.requires_grad for p in bb.stem_parameters()) and bb.stem_train_reason() is not None:
         return bb.stem_train_reason()
-    if tuple(bb.out_indices) != tuple(range(len(bb.res_layers))):
+    sparse = getattr(bb, 'sparse_outputs', False)      # MobileNetV2: out_indices picks among layer1 .. layer7, conv2
+    if not sparse and tuple(bb.out_indices) != tuple(range(len(bb.res_layers))):
         return 'out_indices must name every stage'
-    for name in bb.res_layers:
-        if len({blk.conv1.weight.requires_grad for blk in getattr(bb, name)}) > 1:
+    for i, name in enumerate(bb.res_layers):
+        first = [next(blk.parameters()) for blk in bb.stage_blocks(i)] if sparse else [blk.conv1.weight for blk in getattr(bb, name)]
+        if len({p.requires_grad for p in first}) > 1:
             return 'stage %s is partly frozen' % name
     kind = type(head).__name__
     if kind == 'CPRHead':
@@ -306,14 +308,16 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
             # (ResNet.run_stem: with deep_stem ``bb.stem`` is the reference's Sequential; any other backbone runs its ``stem``)
             x = (getattr(bb, 'run_stem', None) or bb.stem)(img)
     feats = []
-    for i in range(len(bb.res_layers)):
+    sparse = getattr(bb, 'sparse_outputs', False)      # MobileNetV2: the outputs are the out_indices stages, nothing behind the last runs
+    for i in range(bb.last_stage() + 1 if sparse else len(bb.res_layers)):
         params = bridge.stage_params[i]
         if params:
             x = _StageFn.apply(bridge, i, x, *params)
         else:
             with torch.no_grad():
                 x = bb.run_stage(i, bridge.real(x))
-        feats.append(x)
+        if not sparse or i in bb.out_indices:
+            feats.append(x)
     assert len(feats) == len(neck.in_channels)
     xs = feats[neck.start_level:neck.start_level + len(neck.lateral_convs)]
     lat = _LateralsFn.apply(bridge, len(xs), *xs, *bridge.lateral_params)

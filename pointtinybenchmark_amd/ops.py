@@ -2500,3 +2500,122 @@ def splat_apply_bwd(dout, u, att, dg, pool=False):
     _lib.call('cpr_splat_apply_bwd', _ptr(dout), _ptr(u), _ptr(att), _ptr(dg), _ptr(du), _ptr(cs), _ptr(ws), N, H, W, w, int(bool(pool)),
               _stream())
     return du, cs
+
+
+# ---- MobileNetV2 (csrc/mbv2.hip): the depthwise 3x3 conv (forward, data gradient, weight gradient) and the ReLU6 passes.  Maps are NHWC
+# fp32 at the pitch pad32(C), C % 8 == 0, pad channels exact zeros (never read of an input, written as +0.0 of an output).  The C entry
+# points check shapes, strides and flag bits (include/cpr_hip.h) and raise CprHipError('... invalid argument') before any launch.
+DW_IN_CLAMP6, DW_RELU6 = 1, 2
+
+
+class DwPack:
+    """A depthwise (C, 1, 3, 3) parameter as the kernels read it (cpr_dw3x3_pack): [9][pad32(C)] floats, tap-major, pad channels zero,
+    ``scale`` (C) multiplied in -- the data-gradient pack carries the folded BatchNorm scale.  ``repack`` runs the same kernel on the same
+    buffer (nothing calls it after construction today: the backbone's packs lapse with the weight epoch and are rebuilt)."""
+
+    def __init__(self, weight, scale=None):
+        C, one, KH, KW = weight.shape
+        assert weight.is_cuda, 'the depthwise pack is built on the device'
+        assert (one, KH, KW) == (1, 3, 3), 'depthwise conv: a (C, 1, 3, 3) weight, got %s' % (tuple(weight.shape),)
+        self.C, self.Cp = C, pad32(C)
+        self.w = torch.empty((9 * self.Cp,), device=weight.device, dtype=torch.float32)
+        self.repack(weight, scale)
+
+    def repack(self, weight, scale=None):
+        src = weight.detach()
+        if src.dtype != torch.float32 or not src.is_contiguous():
+            src = src.float().contiguous()
+        if scale is not None:
+            assert _check(scale).numel() == self.C, (scale.shape, self.C)
+        _lib.call('cpr_dw3x3_pack', _ptr(src), _ptr(scale), _ptr(self.w), self.C, _stream())
+        self.ready = record_ready()
+        return self
+
+
+def _dw_map(t, C):
+    N, H, W, Cp = _check(t).shape
+    assert Cp == pad32(C), 'a map of %d channels sits at pitch %d, got %s' % (C, pad32(C), tuple(t.shape))
+    return N, H, W
+
+
+def _dw_out_hw(H, W, stride):
+    return (H - 1) // max(stride, 1) + 1, (W - 1) // max(stride, 1) + 1
+
+
+def dw_conv(x, pack, stride=1, scale=None, bias=None, in_clamp6=False, relu6=False, out=None):
+    """out (N,OH,OW,Cp) = act(scale * dwconv3x3(in(x), pack) + bias), padding 1; in_clamp6: x is read as min(x, 6) (its producer wrote
+    ReLU(v)); relu6: act = min(max(., 0), 6); scale / bias (C) None and no flag: the raw form."""
+    pack_ready(pack)
+    N, H, W = _dw_map(x, pack.C)
+    OH, OW = _dw_out_hw(H, W, stride)
+    if out is None:
+        out = torch.empty((N, OH, OW, pack.Cp), device=x.device, dtype=torch.float32)
+    assert tuple(_check(out).shape) == (N, OH, OW, pack.Cp), (out.shape, x.shape, stride)
+    for v in (scale, bias):
+        assert v is None or _check(v).numel() == pack.C, (v.shape, pack.C)
+    _lib.call('cpr_dw3x3_fwd', _ptr(x), _ptr(pack.w), _ptr(scale), _ptr(bias), _ptr(out), N, H, W, pack.C, stride,
+              (DW_IN_CLAMP6 if in_clamp6 else 0) | (DW_RELU6 if relu6 else 0), _stream())
+    if TRACE_CONV_VARIANT[0]:
+        TRACE_CONV_VARIANT[1] = ('dw', pack.C)
+    return out
+
+
+def dw_dgrad(dy, pack, in_hw, stride=1, mask6=None, add=None, colsum=False, out=None):
+    """The data gradient of dw_conv in gather form: dy (N,OH,OW,Cp), ``pack`` the DwPack of the folded weight scale * w -> dx (N,H,W,Cp),
+    (H, W) = in_hw.  add (dx's shape) is summed in, then mask6 (dx's shape, the ReLU(v) map the layer read with in_clamp6) keeps the
+    elements with 0 < mask6 < 6.  colsum: -> (dx, the (C,) per-channel sums of dx).  out: dx is written there (every element, pad
+    channels as +0.0)."""
+    pack_ready(pack)
+    H, W = in_hw
+    N, OH, OW = _dw_map(dy, pack.C)
+    assert (OH, OW) == _dw_out_hw(H, W, stride), (dy.shape, in_hw, stride)
+    dx = out if out is not None else torch.empty((N, H, W, pack.Cp), device=dy.device, dtype=torch.float32)
+    assert tuple(_check(dx).shape) == (N, H, W, pack.Cp), (dx.shape, dy.shape, in_hw)
+    for v in (mask6, add):
+        assert v is None or tuple(_check(v).shape) == tuple(dx.shape), (v.shape, dx.shape)
+    cs = ws = None
+    if colsum:
+        cs = torch.empty((pack.C,), device=dy.device, dtype=torch.float32)
+        ws = torch.empty((_lib.call('cpr_dw3x3_dgrad_workspace', N, H, W, pack.C, positive=True),), device=dy.device, dtype=torch.float32)
+    _lib.call('cpr_dw3x3_dgrad', _ptr(dy), _ptr(pack.w), _ptr(add), _ptr(mask6), _ptr(dx), _ptr(cs), _ptr(ws), N, H, W, pack.C, stride,
+              _stream())
+    return (dx, cs) if colsum else dx
+
+
+def dw_wgrad(dy, x, C, stride=1, in_clamp6=False, grad=None, out=None):
+    """grad_w (C, 1, 3, 3) of dw_conv: dy (N,OH,OW,Cp) against in(x), x (N,H,W,Cp).  Accumulated into ``grad`` when given (one more
+    rounded addition), written into ``out`` when given, else a new tensor.  The split over pixels is added up in a fixed order."""
+    N, H, W = _dw_map(x, C)
+    assert (N,) + _dw_out_hw(H, W, stride) == _dw_map(dy, C), (dy.shape, x.shape, stride)
+    ws = torch.empty((_lib.call('cpr_dw3x3_wgrad_workspace', N, H, W, C, stride, positive=True),), device=x.device, dtype=torch.float32)
+    acc = grad is not None
+    if grad is None:
+        grad = out if out is not None else torch.empty((C, 1, 3, 3), device=x.device, dtype=torch.float32)
+    assert tuple(grad.shape) == (C, 1, 3, 3) and grad.is_contiguous() and grad.dtype == torch.float32
+    _lib.call('cpr_dw3x3_wgrad', _ptr(dy), _ptr(x), _ptr(grad), _ptr(ws), N, H, W, C, stride, int(bool(in_clamp6)), int(acc), _stream())
+    return grad
+
+
+def relu6_bwd_colsum(dy, y=None, add=None, want_g=True, out=None):
+    """g = (dy (+ add)) * (0 < y < 6) and the per-channel column sums of g -> (g | None, colsum (C)): the ReLU6 twin of relu_bwd_colsum.
+    y: the clamped map or the ReLU(v) map the forward recorded (the predicate is the same).  y None: the column sums of dy alone.
+    out (with y): g is written there, every element."""
+    C = dy.shape[-1]
+    M = dy.numel() // C
+    for v in (y, add):
+        assert v is None or (_check(v).numel() == dy.numel()), (v.shape, dy.shape)
+    assert y is not None or add is None
+    g = None
+    if want_g and y is not None:
+        g = out if out is not None else torch.empty_like(dy)
+        assert _check(g).shape == dy.shape, (g.shape, dy.shape)
+    cs = torch.empty((C,), device=dy.device, dtype=torch.float32)
+    ws = torch.empty((_lib.call('cpr_relu6_bwd_colsum_ws', M, C, positive=True),), device=dy.device, dtype=torch.float32)
+    _lib.call('cpr_relu6_bwd_colsum', _ptr(_check(dy)), _ptr(add), _ptr(y), _ptr(g), _ptr(cs), _ptr(ws), M, C, _stream())
+    return (dy if (y is None and want_g) else g), cs
+
+
+def clamp6(x):
+    """x = min(x, 6) in place: a ReLU(v) map whose consumers do not clamp on load (a stage output, conv2's output)."""
+    _lib.call('cpr_clamp6', _ptr(_check(x)), x.numel(), _stream())
+    return x

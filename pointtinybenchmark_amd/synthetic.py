@@ -191,6 +191,46 @@ def resnest_state_dict(depth=50, seed=0, radix=2, reduction_factor=4, prefix='ba
     return sd
 
 
+def mobilenet_v2_state_dict(seed=0, prefix='backbone.'):
+    """The keys and shapes of mmdet's MobileNetV2 (mobilenet_v2.py, widen_factor 1.0), in its state-dict order: conv1.conv (32, 3, 3, 3) /
+    conv1.bn, per inverted-residual block expand_conv (absent in layer1.0), depthwise_conv (mid, 1, 3, 3) and linear_conv, each .conv /
+    .bn, then conv2.conv (1280, 320, 1, 1) / conv2.bn.  Scales are chosen so that ReLU6 clamps on both sides: a conv's weights have
+    variance 1 / (fan_in * E[x^2]) for its input's nominal second moment (1 for the image and the linear maps, 5 for a ReLU6 map), so
+    its output is about unit variance, and the BatchNorm in front of a ReLU6 has gamma in [2.5, 4.5) and beta ~ N(1, 1) -- a
+    pre-activation of standard deviation ~3.5 that is below 0 on ~40 % and above 6 on ~8 % of the elements; a linear conv's BatchNorm
+    has gamma in [0.5, 1).  Its own generator: no other call's random stream moves."""
+    from .backbones.mobilenet_v2 import MobileNetV2
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def conv_bn(p, shape, in_moment, act):
+        fan_in = shape[1] * shape[2] * shape[3]
+        sd[p + '.conv.weight'] = torch.randn(shape, generator=g) * math.sqrt(1.0 / (fan_in * in_moment))
+        c = shape[0]
+        if act:
+            sd[p + '.bn.weight'] = torch.rand(c, generator=g) * 2.0 + 2.5
+            sd[p + '.bn.bias'] = torch.randn(c, generator=g) + 1.0
+        else:
+            sd[p + '.bn.weight'] = torch.rand(c, generator=g) * 0.5 + 0.5
+            sd[p + '.bn.bias'] = torch.randn(c, generator=g) * 0.1
+        sd[p + '.bn.running_mean'] = torch.randn(c, generator=g) * 0.1
+        sd[p + '.bn.running_var'] = torch.rand(c, generator=g) + 0.5
+        sd[p + '.bn.num_batches_tracked'] = torch.tensor(0, dtype=torch.long)
+    conv_bn(prefix + 'conv1', (32, 3, 3, 3), 1.0, True)
+    cin = 32
+    for li, (t, c, n, s) in enumerate(MobileNetV2.arch_settings):
+        for bi in range(n):
+            p = '%slayer%d.%d.' % (prefix, li + 1, bi)
+            mid = int(round(cin * t))
+            if t != 1:
+                conv_bn(p + 'expand_conv', (mid, cin, 1, 1), 1.0, True)
+            conv_bn(p + 'depthwise_conv', (mid, 1, 3, 3), 5.0, True)
+            conv_bn(p + 'linear_conv', (c, mid, 1, 1), 5.0, False)
+            cin = c
+    conv_bn(prefix + 'conv2', (1280, cin, 1, 1), 1.0, True)
+    return sd
+
+
 def fpn_state_dict(in_channels, out_channels=256, start_level=0, num_outs=1, seed=1, prefix='neck.', add_extra_convs=False,
                    extra_convs_on_inputs=True):
     """add_extra_convs (False / True / 'on_input' / 'on_lateral' / 'on_output', as FPN takes it): the stride-2 convs of the
@@ -303,8 +343,12 @@ def p2p_head_state_dict(num_classes=1, num_points=1, in_channels=256, feat_chann
 def locator_state_dict(depth=50, num_classes=1, start_level=0, head='cpr', seed=0, head_std=0.01, num_points=1,
                        num_cls_fcs=0, fc_out_channels=1024, binary_ins=False, ins_tower=False, out_bg_cls=False, deep_stem=False,
                        avg_down=False, groups=1, base_width=4, arch=None):
-    """arch: a RegNet backbone (regnet_state_dict) in place of the ResNet of ``depth``; the FPN then reads its stage widths."""
-    if arch is not None:
+    """arch: a RegNet backbone (regnet_state_dict) in place of the ResNet of ``depth``; the FPN then reads its stage widths.
+    arch='mobilenet_v2': MobileNetV2 with its default out_indices (1, 2, 4, 7)."""
+    if arch == 'mobilenet_v2':
+        sd = mobilenet_v2_state_dict(seed)
+        chans = [24, 32, 96, 1280]
+    elif arch is not None:
         from .backbones.regnet import RegNet, stage_layout
         sd = regnet_state_dict(arch, seed, avg_down=avg_down)
         chans = stage_layout(RegNet.arch_settings[arch] if isinstance(arch, str) else arch)[0]

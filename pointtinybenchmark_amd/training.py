@@ -298,7 +298,7 @@ class BackwardEngine:
     its flat buffer, bucketed reducer, native optimizer) and by the autograd bridge (``autograd_bridge.py``: the same rules
     behind ``torch.autograd.Function``s, gradients handed to torch, so that ``loss.backward()`` / DDP / torch.optim drive the
     drop-in classes as they drive the reference's).  ``_g(p)`` is where the gradient of parameter ``p`` is written."""
-    _sink, side, _mixed = None, None, False
+    _sink, side, _mixed, _stem_colsum = None, None, False, None
     _redirect = None      # id(p) -> scratch: where a later FPN level's contribution to p's gradient goes (_level_grads)
 
     def __init__(self, model, two_streams=True):
@@ -362,6 +362,7 @@ class BackwardEngine:
     def begin_step(self):
         self._mixed = self.model.backbone.compute_dtype == torch.bfloat16 or MIXED_BF16['force']
         self._wide = {}
+        self._stem_colsum = None      # (a pair backward_stage left that no backward_stem took: it must not outlive its step)
 
     def _done(self, p):
         """The gradient of ``p`` (and of everything before it in the trainer's flat order) has been enqueued."""
@@ -384,6 +385,12 @@ class BackwardEngine:
         return out, tape[0]
 
     def backward_stem(self, rec, dout):
+        # Invariant: the pair is taken only for the very tensor backward_stage returned (same storage, same shape), in the backward
+        # that follows it; then the stem rule runs the native trainer's kernels and its gradients are the trainer's bits.  Anything
+        # else (a hook that replaced the gradient) takes the plain route -- relu6_bwd_colsum again: correct, another summation order.
+        pair, self._stem_colsum = self._stem_colsum, None
+        if pair is not None and rec.get('mbv2') and pair[0].shape == dout.shape and pair[0].data_ptr() == dout.data_ptr():
+            dout = pair
         self._backward_stem(self.model.backbone, rec, dout)
 
     def backward_stage(self, tape, dout, need_in):
@@ -393,6 +400,10 @@ class BackwardEngine:
             rec = tape[idx]
             dx = self._block_backward(cache, rec['block'], rec, dx, need_dx=(idx > 0 or need_in), keep=idx > 0,
                                       mask_in=idx > 0 and rec['block'].downsample is None)
+        if isinstance(dx, tuple) and tape[0]['block'].kind == 'mbv2':
+            # MobileNetV2's layer1.0 hands the stem its gradient already masked, with its column sums: the map crosses the segment
+            # boundary, the sums wait here for backward_stem (the next segment's backward), so that both drivers run the same kernels
+            dx, self._stem_colsum = dx[0], dx
         return dx if need_in else None
 
     def forward_laterals(self, xs):
@@ -901,11 +912,18 @@ class BackwardEngine:
         return d_stage
 
     def _stage_trainable(self, stage):
+        """stage: the index of a backbone output (a neck input); a backbone whose out_indices pick among its stages (MobileNetV2)
+        maps it to the stage behind it."""
         bb = self.model.backbone
+        if getattr(bb, 'sparse_outputs', False):
+            stage = sorted(set(bb.out_indices))[stage]
         return any(p.requires_grad for p in getattr(bb, bb.res_layers[stage]).parameters())
 
     def _backward_backbone(self, bb, tape, d_stage):
         c = bb._cache
+        if getattr(bb, 'sparse_outputs', False):      # MobileNetV2: output k is stage out_indices[k] of layer1 .. layer7, conv2
+            stages = sorted(set(bb.out_indices))
+            d_stage = {stages[k]: g for k, g in d_stage.items()}
         dx = None            # gradient flowing down from the block above
         cur_stage = None
         stem = tape[0] if tape and tape[0].get('stem') else None      # a trainable stem: layer1's first block hands it its input gradient
@@ -933,9 +951,18 @@ class BackwardEngine:
         here).  Batch statistics: the BatchNorm backward on the recorded conv map -> dconv, then stem_wgrad_f32(dconv).  The weight
         gradient reads the image as the forward read it (planes or NHWC4) and runs on the side stream; the mixed-precision step feeds
         the same fp32 kernels (its byte map is the bf16 stem kernel's)."""
+        x, planar = rec['x'], rec['planar']
+        if rec.get('mbv2'):
+            # the MobileNetV2 stem (conv1.conv 3x3/2 -> conv1.bn -> ReLU6; eval-mode BatchNorm only).  dp from layer1.0 (it has no expand
+            # conv: its depthwise read the stem's map) is the pair (g1, column sums) already taken through the ReLU6 mask by the depthwise
+            # data gradient's epilogue -- no extra pass; a plain gradient goes through relu6_bwd_colsum.  Then the RegNet stem's kernels.
+            c1, bn = bb.conv1.conv, bb.conv1.bn
+            dy, cs = dp if isinstance(dp, tuple) else ops.relu6_bwd_colsum(dp, rec['out'])
+            self._folded_param_grads(bb._cache, c1, bn, cs, lambda gw: ops.stem3x3s2_wgrad(dy, x, planar=planar, out=gw), dy, x, stem=True)
+            self._done([p for p in (c1.weight, bn.weight, bn.bias) if p.requires_grad][-1])
+            return
         c1, bn = bb.conv1, bb.bn1
         w = c1.weight
-        x, planar = rec['x'], rec['planar']
         # any subset of (conv1.weight, bn1.weight, bn1.bias) may train: each gradient is written only where its parameter trains
         if rec.get('regnet'):
             # the RegNet stem (conv1 3x3/2 -> bn1 -> ReLU, no pool; eval-mode bn1 only): ReLU backward + column sums in one pass, the
@@ -1095,6 +1122,8 @@ class BackwardEngine:
             return self._block_backward_batch_stats(cache, blk, rec, dout, need_dx)
         if blk.kind == 'bottle2neck':
             return self._bottle2neck_backward(cache, blk, rec, dout, need_dx)
+        if blk.kind in ('mbv2', 'mbv2_conv2'):
+            return self._mbv2_block_backward(cache, blk, rec, dout, need_dx)
         if blk.kind == 'regnet':
             return self._regnet_block_backward(cache, blk, rec, dout, need_dx)
         if blk.kind == 'resnest':
@@ -1269,6 +1298,45 @@ class BackwardEngine:
         del d1
         self._done(blk.bn3.bias if blk.bn3.bias.requires_grad else blk.conv2.weight)
         return self._conv1_shortcut_backward(cache, blk, rec, g1, cs1, g3, cs3, need_dx, padded=True)
+
+    # ------------------------------------------------------------------ MobileNetV2 (backbones/mobilenet_v2.py; fp32, eval-mode BatchNorm)
+    def _mbv2_block_backward(self, cache, blk, rec, dout, need_dx):
+        """The rule of an inverted-residual block (kind 'mbv2') given dout at its (linear) output, and of conv2 (kind 'mbv2_conv2').
+          linear conv -> BN   g = dout, its column sums from relu6_bwd_colsum(y=None), x = o2; the data gradient comes back unmasked
+          ReLU6 of o2         g2, cs2 = relu6_bwd_colsum(d_o2, o2)
+          depthwise -> BN     the weight gradient dw_wgrad(g2, o1, in_clamp6) on the side stream, bn_fold_bwd on (C,1,3,3) (K = 9);
+                              g1, cs1 = dw_dgrad(g2, mask6=o1, colsum): the ReLU6 of o1 -- recorded as ReLU(v) -- and the column sums
+                              ride in the data gradient's epilogue
+          expand conv -> BN   x the block input (a linear map: no mask), add = dout where the block has the shortcut
+        layer1.0 has no expand conv: its g1 is the stem's output gradient, returned as the pair (g1, cs1) for _backward_stem.  Every
+        gradient map keeps exact zeros in its pad channels (the dense data gradients through packs with zero rows, the depthwise
+        kernels write them); column sums are cut to the real channels."""
+        from .backbones.mobilenet_v2 import dw_dgrad_pack
+        if blk.kind == 'mbv2_conv2':      # conv2 -> BN -> ReLU6: the recorded map is the clamped one
+            g, cs = ops.relu6_bwd_colsum(dout, rec['out'])
+            dx = self._padded_conv_bn_backward(cache, blk.conv, blk.bn, g, cs[:blk.conv.out_channels], rec['x'], need_dx)
+            self._done(blk.trainable()[-1])
+            return dx
+        x, o1, o2 = rec['x'], rec['o1'], rec['o2']
+        M, O = blk.mid_channels, blk.out_channels
+        lc, dw = blk.linear_conv, blk.depthwise_conv
+        _, cs3 = ops.relu6_bwd_colsum(dout)
+        d2 = self._padded_conv_bn_backward(cache, lc.conv, lc.bn, dout, cs3[:O], o2, True)
+        g2, cs2 = ops.relu6_bwd_colsum(d2, o2)
+        del d2
+        self._folded_param_grads(cache, dw.conv, dw.bn, cs2[:M], lambda gw: ops.dw_wgrad(g2, o1, M, blk.stride, in_clamp6=True, out=gw), g2, o1)
+        last = [p for m in reversed(blk.conv_modules()) for p in m.trainable()][-1]
+        if not (blk.with_expand_conv or need_dx):
+            self._done(last)
+            return None
+        g1, cs1 = ops.dw_dgrad(g2, dw_dgrad_pack(cache, dw.conv, dw.bn), (o1.shape[1], o1.shape[2]), blk.stride, mask6=o1, colsum=True)
+        if not blk.with_expand_conv:
+            self._done(last)
+            return g1, cs1
+        ec = blk.expand_conv
+        dx = self._padded_conv_bn_backward(cache, ec.conv, ec.bn, g1, cs1, x, need_dx, add=dout if blk.with_res_shortcut else None)
+        self._done(last)
+        return dx
 
     # ------------------------------------------------------------------ training-mode BatchNorm (ResNet norm_eval=False)
     def _conv_bn_backward_batch_stats(self, cache, conv, bn, rec, key, g, mask, x, need_dx, add=None):
@@ -1583,6 +1651,14 @@ class CprTrainer(BackwardEngine):
             add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
         for cm in neck.lateral_convs:
             add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+        if getattr(bb, 'sparse_outputs', False):       # (MobileNetV2, _mbv2_block_backward: conv2, then per block linear, depthwise, expand)
+            for i in range(len(bb.res_layers) - 1, -1, -1):
+                for blk in reversed(bb.stage_blocks(i)):
+                    for m in ([blk] if blk.kind == 'mbv2_conv2' else reversed(blk.conv_modules())):
+                        add(m.conv.weight, m.bn.weight, m.bn.bias)
+            if bb.stem_train_reason() is None:
+                add(bb.conv1.conv.weight, bb.conv1.bn.weight, bb.conv1.bn.bias)
+            return out
         for name in reversed(bb.res_layers):
             for blk in reversed(list(getattr(bb, name))):
                 if blk.kind == 'bottle2neck':       # (Res2Net, _bottle2neck_backward: conv3, the slice convs last first, conv1)
