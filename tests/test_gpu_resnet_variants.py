@@ -135,6 +135,9 @@ def test_deep_stem_vs_fp64_chain(hw):
         o16b = m.run_stem(ops.as_nchw(x4))
         torch.cuda.synchronize()
     assert o16.dtype == torch.bfloat16 and o16.shape == out.shape and torch.equal(o16, o16b)
+    # the bf16 mode differs only in the last store: the rounding of the fp32 mode's output, bit for bit
+    assert torch.equal(o16.view(torch.int16), out.to(torch.bfloat16).view(torch.int16)), \
+        'the bf16 output is not the rounding of the fp32 output in %d entries' % int((o16 != out.to(torch.bfloat16)).sum())
     scale = max(1.0, float(out.abs().max()))
     e = (o16.float() - out).abs()
     assert float(e.max()) <= 8e-2 * scale and float(e.mean()) <= 1e-2 * scale, (float(e.max()), float(e.mean()), scale)
