@@ -81,7 +81,7 @@ extern "C" int cpr_logit_project(const float* x, const float* w, const float* bi
                                  hipStream_t stream) {
     CPR_CHECK_ARG(x && w && bias && out && N > 0 && HW > 0 && J > 0);
     CPR_CHECK_ARG((in_a == nullptr) == (in_b == nullptr));
-    if (J > 8 || Cin > 256 || Cin % 64 != 0) return CPR_ERR_UNSUPPORTED;   // caller falls back to the MFMA conv
+    if (J > 8 || Cin < 64 || Cin > 256 || Cin % 64 != 0) return CPR_ERR_UNSUPPORTED;   // caller falls back to the MFMA conv
     const long long npix = (long long)N * HW;
     switch (J) {
         case 1: launch_project<1>(x, w, bias, in_a, in_b, out, npix, HW, Cin, in_relu, stream); break;
