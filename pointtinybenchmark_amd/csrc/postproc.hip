@@ -6,12 +6,10 @@
 #include <limits.h>
 #include "common.h"
 
-__device__ __forceinline__ unsigned f2key(float f) {  // monotone: larger float -> larger key
-    unsigned u = __float_as_uint(f);
+__device__ __forceinline__ unsigned f2key(float f) {  // monotone: larger float -> larger key; -0.0 keys as +0.0 (equal, as in
+    unsigned u = __float_as_uint(f);                  // torch.topk / a stable argsort: the index decides), so a key does not
+    if (u == 0x80000000u) u = 0u;                     // give the value's bits back -- values are read from the input
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
 // in-place bitonic sort, DESCENDING, of P (power of two) 64-bit words by one workgroup
@@ -95,8 +93,9 @@ __global__ void topk_desc_kernel(const float* __restrict__ scores, int n, int k,
     __syncthreads();
     block_bitonic_desc(sel, P);
     for (int i = tid; i < k; i += blockDim.x) {
-        out_vals[i] = key2f((unsigned)(sel[i] >> 32));
-        out_idx[i] = (long long)(~(unsigned)(sel[i] & 0xffffffffull));
+        const unsigned src = ~(unsigned)(sel[i] & 0xffffffffull);
+        out_vals[i] = scores[src];                    // the original bits (a -0.0 stays -0.0)
+        out_idx[i] = (long long)src;
     }
 }
 

@@ -1513,7 +1513,8 @@ def lsa_topk(costT_list, topk):
 
 # ------------------------------------------------------------------------------------------------ P2P inference
 def topk_desc(scores, k):
-    """k largest of a 1-D fp32 tensor, sorted descending, ties by lower index.  -> (values, indices int64)"""
+    """k largest of a 1-D fp32 tensor, sorted descending, ties by lower index (+0.0 and -0.0 are a tie; the values keep their
+    input bits).  -> (values, indices int64)"""
     n = _check(scores).numel()
     vals = torch.empty((k,), device=scores.device, dtype=torch.float32)
     idx = torch.empty((k,), device=scores.device, dtype=torch.int64)
