@@ -659,6 +659,33 @@ int cpr_bfp_scatter_bf16(const cpr_bfp_level* levels, int L, int refine_level, c
                          int N, int C, int arg_wide, void* stream);
 int cpr_bfp_scatter_bwd(const cpr_bfp_level* levels, int L, int refine_level, float* d_ref, int N, int C, int arg_wide, void* stream);
 int cpr_bfp_gather_bwd(const cpr_bfp_level* levels, int L, int refine_level, const float* d_bsf, int N, int C, int arg_wide, void* stream);
+/* HRFPN neck (hrfpn.py:76-99; csrc/hrfpn.hip), NHWC.  reduction_conv(cat_i(bilinear_i(x_i))) = bias + y_0 + sum_{i>=1} bilinear_i(y_i)
+ * with y_i the 1x1 conv of level i by its column slice of the reduction weight, at the level's own resolution.  Levels come in HOST
+ * tables, finest first; level i is (N, H0 >> i, W0 >> i, C).  bilinear_i is torch's F.interpolate(scale_factor=2^i, mode='bilinear',
+ * align_corners=False): src = max(0, (dst + 0.5) / 2^i - 0.5), taps floor(src) and min(floor(src) + 1, in - 1).
+ *   cpr_hrfpn_fuse        levels = y_0 .. y_{L-1}, L <= 4, H_i << i == H0 and W_i << i == W0 (else CPR_ERR_ARG: the reference's cat
+ *                         fails there); bias (C) or null.  out (N,H0,W0,C) = bias + y_0 + sum_i bilinear_i(y_i), fp32 sum in that order,
+ *                         the four taps of a level in the order (y0,x0), (y0,x1), (y1,x0), (y1,x1)
+ *   cpr_hrfpn_pool        levels = the pooled outputs 1 .. K1 (K1 <= 4), level k = F.avg_pool2d(out, 2^k, 2^k): floor mode, (H0 >> k,
+ *                         W0 >> k), none empty; every level from `out` itself, window in row-major order, one launch
+ *   cpr_hrfpn_pool_bwd    gs = g_0 .. g_{K-1} (fp32), K <= 5.  d_out = g_0 + sum_k g_k[y >> k, x >> k] / 4^k inside level k's floor
+ *                         region; part [cpr_hrfpn_pool_bwd_blocks(N, H0, W0)][C][2]: per-block column sums of d_out (element 0 = sum),
+ *                         what cpr_part_colsum reduces
+ *   cpr_hrfpn_fuse_bwd    dys = dy_1 .. dy_{L1} (fp32 outputs, L1 <= 3), H_i << i == H0: the adjoint of bilinear_i applied to d_out, gather
+ *                         form through LDS, destination rows ascending, within a row columns ascending (the row sum first)
+ * fp32: C%4==0; _bf16: maps bf16, C%8==0, fp32 arithmetic, one rounding at the store.  The backward maps are fp32.  Every map below
+ * 2^31 elements, N and H0 at most 65535.  No atomics: bit-repeatable; an image's result does not depend on the batch. */
+typedef struct cpr_hrfpn_level {
+    void* p;
+    int H, W;
+} cpr_hrfpn_level;
+int cpr_hrfpn_fuse(const cpr_hrfpn_level* levels, int L, const float* bias, float* out, int N, int C, void* stream);
+int cpr_hrfpn_fuse_bf16(const cpr_hrfpn_level* levels, int L, const float* bias, void* out, int N, int C, void* stream);
+int cpr_hrfpn_pool(const float* out, int H0, int W0, const cpr_hrfpn_level* levels, int K1, int N, int C, void* stream);
+int cpr_hrfpn_pool_bf16(const void* out, int H0, int W0, const cpr_hrfpn_level* levels, int K1, int N, int C, void* stream);
+int cpr_hrfpn_pool_bwd_blocks(int N, int H0, int W0);
+int cpr_hrfpn_pool_bwd(const cpr_hrfpn_level* gs, int K, float* d_out, float* part, int N, int C, void* stream);
+int cpr_hrfpn_fuse_bwd(const float* d_out, int H0, int W0, const cpr_hrfpn_level* dys, int L1, int N, int C, void* stream);
 /* d(gt_loss + pos_loss + neg_loss)/d(logit map) of CPRHead.loss (cpr_head.py:1101-1229): negative-grid term, MIL bag
  * and gt-centre terms taken back through the bilinear taps -- deterministically: every bag's taps are gathered into a
  * win x win cell window (win >= 2 * ceil(max |offset| / stride) + 3; win_ws (G, win, win, J) fp32 and win_org (G, 2) int32

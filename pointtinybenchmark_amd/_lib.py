@@ -114,6 +114,13 @@ SIGNATURES = {
     'cpr_bfp_scatter_bf16': [_p, _i, _i, _p, _p, _p, _i, _i, _i, _p],
     'cpr_bfp_scatter_bwd': [_p, _i, _i, _p, _i, _i, _i, _p],
     'cpr_bfp_gather_bwd': [_p, _i, _i, _p, _i, _i, _i, _p],
+    'cpr_hrfpn_fuse': [_p, _i, _p, _p, _i, _i, _p],
+    'cpr_hrfpn_fuse_bf16': [_p, _i, _p, _p, _i, _i, _p],
+    'cpr_hrfpn_pool': [_p, _i, _i, _p, _i, _i, _i, _p],
+    'cpr_hrfpn_pool_bf16': [_p, _i, _i, _p, _i, _i, _i, _p],
+    'cpr_hrfpn_pool_bwd_blocks': [_i, _i, _i],
+    'cpr_hrfpn_pool_bwd': [_p, _i, _p, _p, _i, _i, _p],
+    'cpr_hrfpn_fuse_bwd': [_p, _i, _i, _p, _i, _i, _i, _p],
     'cpr_loss_bwd': [_p] * 15 + [_i] * 10 + [_f] * 5 + [_p, _p],
     'cpr_bag_gather_bwd': [_p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p],
     'cpr_bag_points_gather_bwd': [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p],

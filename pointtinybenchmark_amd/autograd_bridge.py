@@ -13,6 +13,8 @@ chain have none: a raw map travels with a pending affine):
           -> _LateralsFn: lateral 1x1 convs + GN + top-down adds -> the lateral sums the output convs read   d(lateral sums)
           -> _HeadLossFn: FPN 3x3 output conv(s) (+ a PAFPN's bottom-up path) + extra pyramid levels + head towers + projection + point stage + losses -> the loss vector
              (add_extra_convs='on_input': the last stage's output is one more input of it, d(stage output) comes back from it too)
+    An HRFPN neck (necks/hrfpn.py) has one such boundary, its reduced map: _LateralsFn runs the per-level 1x1 convs and the fuse
+    (d(reduced map) behind it), _HeadLossFn the pools, the biased output convs and the head.
 
 Every Function takes its trainable parameters as explicit inputs, so they sit in the autograd graph as leaves: gradient
 accumulators fire per Function -- the head's 9.4 MB of gradients (63 % of the backward's time) are final and on the wire while
@@ -33,7 +35,7 @@ import warnings
 import torch
 from torch.autograd.function import once_differentiable
 
-from .training import _BFP_UNDER_CPR, BackwardEngine, P2PBackwardEngine, _bfp_of, _inner_neck
+from .training import _BFP_UNDER_CPR, BackwardEngine, P2PBackwardEngine, _bfp_of, _inner_neck, _is_hrfpn
 
 
 class _GtPack:
@@ -64,7 +66,9 @@ class Bridge:
         self.stem_params = [p for m in (getattr(bb, 'conv1', None), getattr(bb, 'bn1', None)) if m is not None
                             for p in m.parameters() if p.requires_grad]
         self.stage_params = [[p for p in getattr(bb, name).parameters() if p.requires_grad] for name in bb.res_layers]
-        self.lateral_params = [p for cm in neck.lateral_convs for p in cm.parameters() if p.requires_grad]
+        # (an HRFPN's reduction conv -- its per-level 1x1 convs -- plays the laterals' part: the same Function)
+        self.lateral_params = [p for cm in ([neck.reduction_conv] if _is_hrfpn(neck) else neck.lateral_convs) for p in cm.parameters()
+                               if p.requires_grad]
         # (a PAFPN's bottom-up modules sit between the output convs and the head: the same Function)
         # (so does the refine layer of a BFP behind the neck)
         neck_out = list(neck.fpn_convs) + list(getattr(neck, 'downsample_convs', ())) + list(getattr(neck, 'pafpn_convs', ()))
@@ -105,9 +109,14 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
         if type(head).__name__ == 'CPRHead':
             return _BFP_UNDER_CPR
         neck = _inner_neck(neck)
-    if neck is None or type(neck).__name__ not in ('FPN', 'PAFPN') or len(neck.fpn_convs) < 1:
+    if neck is None or type(neck).__name__ not in ('FPN', 'PAFPN', 'HRFPN') or len(neck.fpn_convs) < 1:
         return 'needs an FPN neck'
-    n_outs = min(len(neck.lateral_convs), neck.num_outs) + getattr(neck, 'extra_levels', 0)    # outputs, not fpn_convs: max-pool extras
+    if _is_hrfpn(neck):
+        n_outs = neck.num_outs
+        if n_outs != 1 and type(head).__name__ == 'CPRHead':
+            return 'CPRHead takes one pyramid level (cpr_head.py:487); this HRFPN has %d output levels' % n_outs
+    else:
+        n_outs = min(len(neck.lateral_convs), neck.num_outs) + getattr(neck, 'extra_levels', 0)    # outputs, not fpn_convs: max-pool extras
     if n_outs != 1 and type(head).__name__ == 'CPRHead' and type(neck).__name__ == 'PAFPN':
         return 'CPRHead takes one pyramid level (cpr_head.py:487); this PAFPN has %d output levels' % n_outs
     if n_outs != 1 and type(head).__name__ != 'P2PHead':
@@ -319,7 +328,7 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
         if not sparse or i in bb.out_indices:
             feats.append(x)
     assert len(feats) == len(neck.in_channels)
-    xs = feats[neck.start_level:neck.start_level + len(neck.lateral_convs)]
+    xs = feats if _is_hrfpn(neck) else feats[neck.start_level:neck.start_level + len(neck.lateral_convs)]
     lat = _LateralsFn.apply(bridge, len(xs), *xs, *bridge.lateral_params)
     lats = tuple(lat) if isinstance(lat, (tuple, list)) else (lat,)
     if bridge.extra_on_input:

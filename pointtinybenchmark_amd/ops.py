@@ -1252,6 +1252,75 @@ def bfp_gather_bwd(gs, refine_level, d_bsf, args):
     return outs
 
 
+# ------------------------------------------------------------------------------------------------ HRFPN neck (csrc/hrfpn.hip)
+class _HrfpnLevel(ctypes.Structure):    # include/cpr_hip.h: cpr_hrfpn_level
+    _fields_ = [('p', ctypes.c_void_p), ('H', ctypes.c_int), ('W', ctypes.c_int)]
+
+
+HRFPN_MAX_LEVELS, HRFPN_MAX_OUTS = 4, 5
+
+
+def _hrfpn_table(maps):
+    t = (_HrfpnLevel * max(1, len(maps)))()
+    for e, m in zip(t, maps):
+        e.p, e.H, e.W = m.data_ptr(), m.shape[1], m.shape[2]
+    return t
+
+
+def _hrfpn_maps(maps, dtype):
+    """The common checks of a level table: NHWC, one dtype, one batch, one channel count.  Sizes are the kernels' own argument check."""
+    N, _, _, C = _check(maps[0], dtype).shape
+    for m in maps:
+        assert _check(m, dtype).dtype == maps[0].dtype and m.dim() == 4 and m.shape[0] == N and m.shape[3] == C, (m.shape, maps[0].shape)
+    return N, C
+
+
+def hrfpn_fuse(ys, bias=None):
+    """out = bias + ys[0] + sum_{i>=1} bilinear_i(ys[i]): the HRFPN reduction conv behind its per-level 1x1 convs (csrc/hrfpn.hip).
+    ys: 1..4 NHWC maps, fp32 or bf16, level i at (H0 >> i, W0 >> i) with H_i * 2^i == H0 (anything else is refused by the kernel's
+    argument check); bilinear_i: F.interpolate(scale_factor=2**i, mode='bilinear', align_corners=False).  bias (C,) fp32 or None."""
+    N, C = _hrfpn_maps(ys, ACT)
+    if bias is not None:
+        assert _check(bias.detach()).numel() == C, (bias.shape, C)
+    out = torch.empty_like(ys[0])
+    _lib.call('cpr_hrfpn_fuse' + _sfx(out), _hrfpn_table(ys), len(ys), _ptr(bias), _ptr(out), N, C, _stream())
+    return out
+
+
+def hrfpn_pool(out, num_outs):
+    """-> [F.avg_pool2d(out, 2**k, 2**k) for k in 1 .. num_outs - 1] of an NHWC fp32 / bf16 map in one launch: floor mode (H0 // 2**k,
+    trailing rows and columns dropped), every level from ``out`` itself.  An empty level is refused by the kernel's argument check."""
+    N, H0, W0, C = _check(out, ACT).shape
+    if num_outs <= 1:
+        return []
+    levels = [torch.empty((N, H0 >> k, W0 >> k, C), device=out.device, dtype=out.dtype) for k in range(1, num_outs)]
+    _lib.call('cpr_hrfpn_pool' + _sfx(out), _ptr(out), H0, W0, _hrfpn_table(levels), len(levels), N, C, _stream())
+    return levels
+
+
+def hrfpn_pool_bwd(gs):
+    """gs: the fp32 gradients g_0 .. g_{K-1} of hrfpn_pool's input and outputs (g_k at (H0 >> k, W0 >> k)) ->
+    (d_out = g_0 + sum_k g_k[y >> k, x >> k] / 4**k inside level k's floor region, TilePartials of d_out's column sums)."""
+    N, C = _hrfpn_maps(gs, torch.float32)
+    _, H0, W0, _ = gs[0].shape
+    d_out = torch.empty_like(gs[0])
+    tiles = _lib.call('cpr_hrfpn_pool_bwd_blocks', N, H0, W0, positive=True)
+    part = torch.empty((tiles, C, 2), device=d_out.device, dtype=torch.float32)
+    _lib.call('cpr_hrfpn_pool_bwd', _hrfpn_table(gs), len(gs), _ptr(d_out), _ptr(part), N, C, _stream())
+    return d_out, TilePartials(part, tiles, C)
+
+
+def hrfpn_fuse_bwd(d_out, sizes):
+    """The adjoint of hrfpn_fuse's bilinear part: d_out (N, H0, W0, C) fp32 -> [dy_1, ..] with dy_i (N,) + sizes[i - 1] + (C,) (dy_0 is
+    d_out itself).  sizes: the (H_i, W_i) of levels 1 ..; H_i * 2^i != H0 is refused by the kernel's argument check."""
+    N, H0, W0, C = _check(d_out).shape
+    if not sizes:
+        return []
+    dys = [torch.empty((N, int(h), int(w), C), device=d_out.device, dtype=torch.float32) for h, w in sizes]
+    _lib.call('cpr_hrfpn_fuse_bwd', _ptr(d_out), H0, W0, _hrfpn_table(dys), len(dys), N, C, _stream())
+    return dys
+
+
 # ------------------------------------------------------------------------------------------------ CPR points
 def box_centers(boxes):
     n = boxes.shape[0]

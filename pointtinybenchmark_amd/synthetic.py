@@ -284,6 +284,23 @@ def bfp_state_dict(in_channels=256, refine_type='conv', seed=1, prefix='neck.1.'
     return sd
 
 
+def hrfpn_state_dict(in_channels, out_channels=256, num_outs=5, seed=1, prefix='neck.'):
+    """HRFPN's parameters in the reference's order (hrfpn.py:52-69): ``reduction_conv.conv.weight`` (out, sum(in_channels), 1, 1) and
+    ``.bias``, then ``fpn_convs.<k>.conv.weight`` (3x3) and ``.bias`` per output level.  Weights uniform at the fan-in bound of mmcv's
+    caffe2_xavier_init; the biases -- zero after that init -- are drawn non-zero so that a test sees them."""
+    g = torch.Generator().manual_seed(seed + 15485863)
+
+    def conv(name, shape):
+        bound = math.sqrt(3.0 / (shape[1] * shape[2] * shape[3]))
+        sd['%s%s.conv.weight' % (prefix, name)] = (torch.rand(shape, generator=g) * 2 - 1) * bound
+        sd['%s%s.conv.bias' % (prefix, name)] = torch.randn(shape[0], generator=g) * 0.1
+    sd = {}
+    conv('reduction_conv', (out_channels, sum(in_channels), 1, 1))
+    for k in range(num_outs):
+        conv('fpn_convs.%d' % k, (out_channels, out_channels, 3, 3))
+    return sd
+
+
 def cpr_head_state_dict(num_classes=1, in_channels=256, feat_channels=256, stacked_convs=4, seed=2,
                         prefix='bbox_head.', std=0.01, num_cls_fcs=0, fc_out_channels=1024, binary_ins=False,
                         ins_tower=False, out_bg_cls=False):

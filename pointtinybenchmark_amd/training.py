@@ -285,6 +285,11 @@ def _bfp_of(neck):
     return getattr(neck, 'bfp', None)
 
 
+def _is_hrfpn(neck):
+    """An HRFPN neck (necks/hrfpn.py): no lateral chain -- one reduced map, then pools and biased output convs."""
+    return type(neck).__name__ == 'HRFPN'
+
+
 def _as_list(x):
     """One map or a sequence of maps -> a list (the bridge's segments carry a single map bare; the engine works on lists)."""
     return list(x) if isinstance(x, (list, tuple)) else [x]
@@ -298,7 +303,7 @@ class BackwardEngine:
     its flat buffer, bucketed reducer, native optimizer) and by the autograd bridge (``autograd_bridge.py``: the same rules
     behind ``torch.autograd.Function``s, gradients handed to torch, so that ``loss.backward()`` / DDP / torch.optim drive the
     drop-in classes as they drive the reference's).  ``_g(p)`` is where the gradient of parameter ``p`` is written."""
-    _sink, side, _mixed, _stem_colsum = None, None, False, None
+    _sink, side, _mixed, _stem_colsum, _hr_colsum = None, None, False, None, None
     _redirect = None      # id(p) -> scratch: where a later FPN level's contribution to p's gradient goes (_level_grads)
 
     def __init__(self, model, two_streams=True):
@@ -363,6 +368,7 @@ class BackwardEngine:
         self._mixed = self.model.backbone.compute_dtype == torch.bfloat16 or MIXED_BF16['force']
         self._wide = {}
         self._stem_colsum = None      # (a pair backward_stage left that no backward_stem took: it must not outlive its step)
+        self._hr_colsum = None        # (the same for backward_head_loss / backward_laterals of an HRFPN neck)
 
     def _done(self, p):
         """The gradient of ``p`` (and of everything before it in the trainer's flat order) has been enqueued."""
@@ -411,6 +417,9 @@ class BackwardEngine:
         the backward state)."""
         tape = []
         neck = self.model.neck
+        if _is_hrfpn(neck):     # the reduced map is the one boundary with a true gradient: run_fuse in front of it, run_outputs behind
+            out = neck.run_fuse(list(xs), tape)
+            return out, tape[0]
         lat = neck.run_laterals(list(xs), tape)
         n = min(len(lat), neck.num_outs)        # the regular output convs (fpn_convs may hold extra levels behind them)
         return (lat[0] if n == 1 else tuple(lat[:n])), {r['level']: r for r in tape}
@@ -418,6 +427,14 @@ class BackwardEngine:
     def backward_laterals(self, recs, dlat, need):
         """dlat: gradient wrt the lateral sum(s) forward_laterals returned.  need[i]: whether the gradient wrt the i-th input (stage start_level + i) is wanted -> list of gradients / None."""
         neck = self.model.neck
+        if _is_hrfpn(neck):
+            # Invariant (as backward_stem's): the partials are taken only for the very tensor backward_head_loss returned, in the backward
+            # that follows it; then the reduction bias gradient is the native trainer's bits.  Anything else sums the columns again.
+            pair, self._hr_colsum = self._hr_colsum, None
+            d_out, = _as_list(dlat)
+            ok = pair is not None and pair[0].shape == d_out.shape and pair[0].data_ptr() == d_out.data_ptr()
+            d_stage = self._backward_hrfpn_inputs(neck, recs, d_out, pair[1] if ok else None, need_dx_of=lambda stage: need[stage])
+            return [d_stage.get(i) for i in range(len(need))]
         d_stage = self._backward_laterals(neck, recs, _as_list(dlat), need_dx_of=lambda stage: need[stage - neck.start_level])
         return [d_stage.get(i + neck.start_level) for i in range(len(need))]
 
@@ -570,6 +587,9 @@ class BackwardEngine:
     @staticmethod
     def _forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes):
         tape, save = [], {}
+        # (an HRFPN hands over materialised levels -- no norm follows its output convs: a raw map under the identity affine)
+        lazy = [(l, (l.new_ones((l.shape[0], l.shape[-1]), dtype=torch.float32), l.new_zeros((l.shape[0], l.shape[-1]), dtype=torch.float32)))
+                if torch.is_tensor(l) else l for l in lazy]
         losses = head.forward_train_lazy(lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes,
                                          tape=tape, save=save)
         save['tape'] = tape
@@ -774,7 +794,12 @@ class BackwardEngine:
     # ------------------------------------------------------------------ FPN, backbone
     def _backward_neck(self, neck, neck_tape, dz):
         """Everything behind the lateral sums (_backward_outputs), then the top-down chain from the finest lateral to the coarsest
-        -> {stage: d(stage output)}.  dz: gradient wrt the (normalised) neck output -- one map (one level), or a list with one per level."""
+        -> {stage: d(stage output)}.  dz: gradient wrt the (normalised) neck output -- one map (one level), or a list with one per level.
+        An HRFPN: its output convs and pools, then its fuse and 1x1 convs (_backward_hrfpn_outputs / _backward_hrfpn_inputs)."""
+        if _is_hrfpn(neck):
+            by = {r['kind']: r for r in neck_tape}
+            d_out, part = self._backward_hrfpn_outputs(neck, by['hrfpn_out'], _as_list(dz))
+            return self._backward_hrfpn_inputs(neck, by['hrfpn_in'], d_out, part)
         lat_recs = {r['level']: r for r in neck_tape if r['kind'] == 'lateral'}
         dlats, d_src = self._backward_outputs(neck, [r for r in neck_tape if r['kind'] != 'lateral'], _as_list(dz))
         d_stage = self._backward_laterals(neck, lat_recs, dlats)
@@ -789,6 +814,10 @@ class BackwardEngine:
         recs: the tape without its 'lateral' records.  dzs: one gradient per output level.  -> (one gradient per lateral sum an output
         conv read -- the last joined by an 'on_lateral' extra's --, the gradient an 'on_input' extra adds to the last backbone stage's
         output | None)."""
+        if _is_hrfpn(neck):     # (autograd bridge: the column sums wait for backward_laterals, the next segment's backward)
+            d_out, part = self._backward_hrfpn_outputs(neck, recs[0], dzs)
+            self._hr_colsum = (d_out, part)
+            return [d_out], None
         bfp_recs = [r for r in recs if r['kind'].startswith('bfp_')]
         if bfp_recs:
             dzs = self._backward_bfp(neck.bfp, bfp_recs, dzs)
@@ -818,6 +847,56 @@ class BackwardEngine:
             d = self._gn_conv_backward(by['bfp_refine'], d, relu=True, need_dx=True)
             self._done(bfp.refine.conv.weight)
         return ops.bfp_gather_bwd(gs, bfp.refine_level, d, by['bfp_gather']['args'])
+
+    def _backward_hrfpn_outputs(self, neck, rec, dzs):
+        """HRFPN behind its reduced map, in reverse (necks/hrfpn.py run_outputs; T/mmdet/models/necks/hrfpn.py:88-98): the biased 3x3
+        output convs -- weight gradient from the recorded (pooled) level, bias gradient the column sums of dz, data gradient g_k -- then
+        ops.hrfpn_pool_bwd: d_out = g_0 + sum_k g_k / 4^k through the pools.  rec: the 'hrfpn_out' record.  dzs: one fp32 gradient per
+        output level.  -> (d_out, the TilePartials of its column sums: the reduction conv's bias gradient).
+        Mixed precision: the fp32 gradient kernels on the widened recorded maps, like the other necks' stride-2 layers."""
+        levels = rec['levels']
+        assert len(dzs) == len(levels) == neck.num_outs, 'one gradient per HRFPN output level (%d outputs, %d gradients)' \
+            % (neck.num_outs, len(dzs))
+        gs = []
+        for k, (dz, lv) in enumerate(zip(dzs, levels)):
+            conv = neck.fpn_convs[k].conv
+            dz, x = dz.contiguous(), self._f32(lv)
+            gw, gb, stride, pad = self._g(conv.weight), self._g(conv.bias), conv.stride[0], conv.padding[0]
+
+            def param_grads(dz=dz, x=x, gw=gw, gb=gb, conv=conv, stride=stride, pad=pad):
+                ops.conv2d_wgrad(dz, x, conv.weight.shape, stride, pad, out=gw)
+                gb.copy_(ops.relu_bwd_colsum(dz, None, want_g=False)[1])
+            self._param_side(param_grads, dz, x)
+            gs.append(ops.conv2d_dgrad(dz, ops.dgrad_pack(conv.weight, stride, pad), (lv.shape[1], lv.shape[2]), stride))
+            self._done(conv.bias)
+        return ops.hrfpn_pool_bwd(gs)
+
+    def _backward_hrfpn_inputs(self, neck, rec, d_out, part=None, need_dx_of=None):
+        """HRFPN in front of its reduced map, in reverse (necks/hrfpn.py run_fuse): the reduction bias gradient is the column sums of
+        d_out (``part``: hrfpn_pool_bwd's partials; None -- a gradient that did not come from there -- sums them again),
+        ops.hrfpn_fuse_bwd takes d_out to dy_i, and per level the 1x1 weight gradient goes into that level's column slice of the
+        reduction weight's gradient (a scratch at the level's pitch, one strided copy) and the 1x1 data gradient into the backbone
+        stage, where it trains.  rec: the 'hrfpn_in' record.  -> {stage: d(stage output) or None}."""
+        conv = neck.reduction_conv.conv
+        xs, sizes = rec['xs'], rec['sizes']
+        gb, gw = self._g(conv.bias), self._g(conv.weight)
+        if part is None:
+            self._param_side(lambda: gb.copy_(ops.relu_bwd_colsum(d_out, None, want_g=False)[1]), d_out)
+        else:
+            self._param_side(lambda: gb.copy_(part.reduce()), part.part)
+        dys = [d_out] + ops.hrfpn_fuse_bwd(d_out, sizes[1:])
+        d_stage = {}
+        for i, (dy, x) in enumerate(zip(dys, xs)):
+            lo, c = neck.level_slice(i)
+            pitch, x32 = x.shape[-1], self._f32(x)
+
+            def level_wgrad(dy=dy, x32=x32, lo=lo, c=c, pitch=pitch):
+                gw[:, lo:lo + c].copy_(ops.conv2d_wgrad(dy, x32, (conv.weight.shape[0], pitch, 1, 1), 1, 0)[:, :c])
+            self._param_side(level_wgrad, dy, x32)
+            need = bool((need_dx_of or self._stage_trainable)(i))
+            d_stage[i] = ops.conv2d_dgrad(dy, neck.level_dgrad_pack(i, pitch), tuple(sizes[i])) if need else None
+        self._done(conv.weight)
+        return d_stage
 
     def _backward_extras(self, neck, recs, dzs, need_src=None):
         """The extra pyramid levels, last first (T/mmdet/models/necks/fpn.py:195-217).  dzs: one gradient per output level, the extras'
@@ -1414,7 +1493,12 @@ class CprTrainer(BackwardEngine):
         if _bfp_of(model.neck) is not None and type(model.bbox_head).__name__ == 'CPRHead':
             raise NotImplementedError(_BFP_UNDER_CPR)
         inner = _inner_neck(model.neck)
-        n_levels = min(len(inner.lateral_convs), inner.num_outs) + getattr(inner, 'extra_levels', 0)
+        if _is_hrfpn(inner):
+            n_levels = inner.num_outs
+            if type(model.bbox_head).__name__ == 'CPRHead' and n_levels != 1:
+                raise NotImplementedError('CPRHead takes one pyramid level (cpr_head.py:487); this HRFPN has %d output levels' % n_levels)
+        else:
+            n_levels = min(len(inner.lateral_convs), inner.num_outs) + getattr(inner, 'extra_levels', 0)
         if _is_pafpn(inner) and type(model.bbox_head).__name__ == 'CPRHead' and n_levels != 1:
             raise NotImplementedError('CPRHead takes one pyramid level (cpr_head.py:487); this PAFPN has %d output levels' % n_levels)
         self.schedule = schedule
@@ -1639,18 +1723,12 @@ class CprTrainer(BackwardEngine):
         bfp = _bfp_of(m.neck)
         if bfp is not None and bfp.refine_type is not None:      # BFP's refine layer sits between the head and the neck (_backward_bfp)
             add(bfp.refine.gn.weight, bfp.refine.gn.bias, bfp.refine.conv.weight)
-        regular = min(len(neck.lateral_convs), neck.num_outs)
-        for cm in reversed(list(neck.fpn_convs)[regular:]):      # the extra levels' convs, last first (_backward_extras)
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
-        if _is_pafpn(neck):       # the bottom-up path in reverse (_backward_pafpn): per level its pafpn conv, downsample conv, output conv
-            for i in range(regular - 1, -1, -1):
-                for cm in ([neck.pafpn_convs[i - 1]] if i >= 1 else []) + ([neck.downsample_convs[i]] if i < regular - 1 else []):
-                    add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
-                add(neck.fpn_convs[i].gn.weight, neck.fpn_convs[i].gn.bias, neck.fpn_convs[i].conv.weight)
-        for cm in list(neck.fpn_convs)[:regular]:
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
-        for cm in neck.lateral_convs:
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+        if _is_hrfpn(neck):       # (_backward_hrfpn_outputs: the output convs, finest first; _backward_hrfpn_inputs: the reduction conv)
+            for cm in neck.fpn_convs:
+                add(cm.conv.weight, cm.conv.bias)
+            add(neck.reduction_conv.conv.bias, neck.reduction_conv.conv.weight)
+        else:
+            self._fpn_param_order(neck, add)
         if getattr(bb, 'sparse_outputs', False):       # (MobileNetV2, _mbv2_block_backward: conv2, then per block linear, depthwise, expand)
             for i in range(len(bb.res_layers) - 1, -1, -1):
                 for blk in reversed(bb.stage_blocks(i)):
@@ -1685,6 +1763,22 @@ class CprTrainer(BackwardEngine):
         if bb.stem_train_reason() is None:          # frozen_stages < 0: the stem's gradients complete last
             add(bb.conv1.weight, bb.bn1.weight, bb.bn1.bias)     # (a deep stem always has a reason: it does not train)
         return out      # (a trainable non-standard stem has no backward rule and trips the constructor's check)
+
+    @staticmethod
+    def _fpn_param_order(neck, add):
+        """An FPN / PAFPN in its backward's order: extra levels, the bottom-up path, output convs, laterals."""
+        regular = min(len(neck.lateral_convs), neck.num_outs)
+        for cm in reversed(list(neck.fpn_convs)[regular:]):      # the extra levels' convs, last first (_backward_extras)
+            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+        if _is_pafpn(neck):       # the bottom-up path in reverse (_backward_pafpn): per level its pafpn conv, downsample conv, output conv
+            for i in range(regular - 1, -1, -1):
+                for cm in ([neck.pafpn_convs[i - 1]] if i >= 1 else []) + ([neck.downsample_convs[i]] if i < regular - 1 else []):
+                    add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+                add(neck.fpn_convs[i].gn.weight, neck.fpn_convs[i].gn.bias, neck.fpn_convs[i].conv.weight)
+        for cm in list(neck.fpn_convs)[:regular]:
+            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+        for cm in neck.lateral_convs:
+            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
 
     @staticmethod
     def _head_param_order(head, add):
