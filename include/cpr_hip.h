@@ -686,6 +686,26 @@ int cpr_hrfpn_pool_bf16(const void* out, int H0, int W0, const cpr_hrfpn_level* 
 int cpr_hrfpn_pool_bwd_blocks(int N, int H0, int W0);
 int cpr_hrfpn_pool_bwd(const cpr_hrfpn_level* gs, int K, float* d_out, float* part, int N, int C, void* stream);
 int cpr_hrfpn_fuse_bwd(const float* d_out, int H0, int W0, const cpr_hrfpn_level* dys, int L1, int N, int C, void* stream);
+/* HRNet branch exchange (hrnet.py:182-199, HRModule.forward; csrc/hrnet.hip), NHWC fp32, C%4==0.
+ *   cpr_hrnet_fuse       out (N,H,W,C) = ReLU(t_0 + t_1 + ..): T <= 4 terms from a HOST table.  Term (p, k), k in 0..3: a map
+ *                        (N, H >> k, W >> k, C) read at [y >> k, x >> k] -- torch's nearest rule for the scale factor 2^k; k = 0 is a map
+ *                        at the output's size.  H % 2^k == 0 and W % 2^k == 0, else CPR_ERR_ARG.  The fp32 sum runs left to right in
+ *                        table order, no multiply; ReLU(v) = v <= 0 ? +0.0 : v (a NaN stays a NaN)
+ *   cpr_hrnet_fuse_bwd   g (N,H,W,C) = y <= 0 ? +0.0 : dy; pools[k - 1] = pool_k (N, H >> k, W >> k, C), k = 1..K (K <= 3, HOST array of
+ *                        K pointers; H % 2^K == 0 and W % 2^K == 0): the sum of g over the 2^k x 2^k block, the adjoint of the nearest
+ *                        upsample.  Order: pool_1 = ((g[2y,2x] + g[2y,2x+1]) + g[2y+1,2x]) + g[2y+1,2x+1], pool_k the same expression
+ *                        over pool_{k-1}.  part [cpr_hrnet_fuse_bwd_blocks(N, H, W, C, K)][C][2]: per-block column sums of g (element
+ *                        0 = sum; a lane adds its cells' pool_K values in ascending cell order, the block its lanes in ascending
+ *                        order), what cpr_part_colsum reduces
+ * Every map below 2^31 elements, N and H at most 65535.  No atomics: bit-repeatable; an image's result does not depend on the batch. */
+typedef struct cpr_hrnet_term {
+    const void* p;
+    int k;
+} cpr_hrnet_term;
+int cpr_hrnet_fuse(const cpr_hrnet_term* terms, int T, float* out, int N, int H, int W, int C, void* stream);
+int cpr_hrnet_fuse_bwd_blocks(int N, int H, int W, int C, int K);
+int cpr_hrnet_fuse_bwd(const float* dy, const float* y, float* g, float* const* pools, int K, float* part, int N, int H, int W, int C,
+                       void* stream);
 /* d(gt_loss + pos_loss + neg_loss)/d(logit map) of CPRHead.loss (cpr_head.py:1101-1229): negative-grid term, MIL bag
  * and gt-centre terms taken back through the bilinear taps -- deterministically: every bag's taps are gathered into a
  * win x win cell window (win >= 2 * ceil(max |offset| / stride) + 3; win_ws (G, win, win, J) fp32 and win_org (G, 2) int32

@@ -121,6 +121,9 @@ SIGNATURES = {
     'cpr_hrfpn_pool_bwd_blocks': [_i, _i, _i],
     'cpr_hrfpn_pool_bwd': [_p, _i, _p, _p, _i, _i, _p],
     'cpr_hrfpn_fuse_bwd': [_p, _i, _i, _p, _i, _i, _i, _p],
+    'cpr_hrnet_fuse': [_p, _i, _p, _i, _i, _i, _i, _p],
+    'cpr_hrnet_fuse_bwd_blocks': [_i, _i, _i, _i, _i],
+    'cpr_hrnet_fuse_bwd': [_p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _p],
     'cpr_loss_bwd': [_p] * 15 + [_i] * 10 + [_f] * 5 + [_p, _p],
     'cpr_bag_gather_bwd': [_p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p],
     'cpr_bag_points_gather_bwd': [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p],

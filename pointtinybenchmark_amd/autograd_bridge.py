@@ -63,9 +63,14 @@ class Bridge:
         self.engine = engine
         bb, neck, bfp = model.backbone, _inner_neck(model.neck), _bfp_of(model.neck)
         self._maps = {}         # bf16 compute mode: data_ptr of an fp32 carrier -> the bf16 map it stands for (see carrier())
-        self.stem_params = [p for m in (getattr(bb, 'conv1', None), getattr(bb, 'bn1', None)) if m is not None
-                            for p in m.parameters() if p.requires_grad]
-        self.stage_params = [[p for p in getattr(bb, name).parameters() if p.requires_grad] for name in bb.res_layers]
+        self.hrnet = bool(getattr(bb, 'hrnet', False))
+        if self.hrnet:      # a DAG of branches: one Function from the image to the branch outputs (_HRNetFn), every parameter its input
+            self.stem_params, self.stage_params = [], []
+            self.backbone_params = [p for p in bb.parameters() if p.requires_grad]
+        else:
+            self.stem_params = [p for m in (getattr(bb, 'conv1', None), getattr(bb, 'bn1', None)) if m is not None
+                                for p in m.parameters() if p.requires_grad]
+            self.stage_params = [[p for p in getattr(bb, name).parameters() if p.requires_grad] for name in bb.res_layers]
         # (an HRFPN's reduction conv -- its per-level 1x1 convs -- plays the laterals' part: the same Function)
         self.lateral_params = [p for cm in ([neck.reduction_conv] if _is_hrfpn(neck) else neck.lateral_convs) for p in cm.parameters()
                                if p.requires_grad]
@@ -137,9 +142,12 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     if any(p.requires_grad for p in bb.stem_parameters()) and bb.stem_train_reason() is not None:
         return bb.stem_train_reason()
     sparse = getattr(bb, 'sparse_outputs', False)      # MobileNetV2: out_indices picks among layer1 .. layer7, conv2
-    if not sparse and tuple(bb.out_indices) != tuple(range(len(bb.res_layers))):
+    hrnet = getattr(bb, 'hrnet', False)                # HRNet: no out_indices, no frozen_stages -- any (conv, BN) pair may be frozen, as a whole
+    if hrnet and bb.freeze_reason() is not None:
+        return bb.freeze_reason()
+    if not (sparse or hrnet) and tuple(bb.out_indices) != tuple(range(len(bb.res_layers))):
         return 'out_indices must name every stage'
-    for i, name in enumerate(bb.res_layers):
+    for i, name in enumerate(() if hrnet else bb.res_layers):
         first = [next(blk.parameters()) for blk in bb.stage_blocks(i)] if sparse else [blk.conv1.weight for blk in getattr(bb, name)]
         if len({p.requires_grad for p in first}) > 1:
             return 'stage %s is partly frozen' % name
@@ -207,6 +215,34 @@ class _StemFn(torch.autograd.Function):
         eng.backward_stem(ctx.rec, dout.contiguous())
         grads = eng.collect(ctx.params)
         ctx.rec = None
+        return (None, None) + grads
+
+
+class _HRNetFn(torch.autograd.Function):
+    """An HRNet backbone (backbones/hrnet.py), stem included: the image (no gradient) -> the NHWC branch outputs of stage4's last
+    module; every trainable backbone parameter as an input.  Its branches exchange maps after every module, so there is no chain of
+    single-input stages to cut it into: the backward is BackwardEngine._backward_backbone on the recorded forward, as the native
+    trainer runs it."""
+
+    @staticmethod
+    def forward(ctx, bridge, img, *params):
+        bb = bridge.model.backbone
+        tape = []
+        outs = bb.run(img, tape)
+        tape[0]['stages'][-1]['modules'][-1]['out'] = [o.detach() for o in outs]      # (no output reachable from its own ctx)
+        ctx.bridge, ctx.tape, ctx.params = bridge, tape, params
+        ctx.set_materialize_grads(False)      # an output nobody differentiates hands None down, as in the native trainer
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *douts):
+        eng, tape = ctx.bridge.engine, ctx.tape
+        assert tape is not None, _CONSUMED
+        d_stage = {k: d.contiguous() for k, d in enumerate(douts) if d is not None}
+        eng._backward_backbone(ctx.bridge.model.backbone, tape, d_stage)
+        grads = eng.collect(ctx.params)
+        ctx.tape = None
         return (None, None) + grads
 
 
@@ -310,6 +346,13 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
     eng._sink.clear()
     bridge._maps.clear()
     bb, neck = model.backbone, _inner_neck(model.neck)
+    if bridge.hrnet:
+        if bridge.backbone_params:
+            feats = list(_HRNetFn.apply(bridge, img.detach(), *bridge.backbone_params))
+        else:
+            with torch.no_grad():
+                feats = bb.run(img)
+        return _neck_head_loss(model, bridge, feats, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
     if bridge.stem_params:
         x = _StemFn.apply(bridge, img.detach(), *bridge.stem_params)
     else:
@@ -327,6 +370,12 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
                 x = bb.run_stage(i, bridge.real(x))
         if not sparse or i in bb.out_indices:
             feats.append(x)
+    return _neck_head_loss(model, bridge, feats, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes)
+
+
+def _neck_head_loss(model, bridge, feats, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes):
+    """The part of forward_train behind the backbone: feats, its NHWC outputs -> the dict of losses."""
+    eng, neck = bridge.engine, _inner_neck(model.neck)
     assert len(feats) == len(neck.in_channels)
     xs = feats if _is_hrfpn(neck) else feats[neck.start_level:neck.start_level + len(neck.lateral_convs)]
     lat = _LateralsFn.apply(bridge, len(xs), *xs, *bridge.lateral_params)

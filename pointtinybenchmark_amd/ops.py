@@ -1321,6 +1321,56 @@ def hrfpn_fuse_bwd(d_out, sizes):
     return dys
 
 
+# ------------------------------------------------------------------------------------------------ HRNet branch exchange (csrc/hrnet.hip)
+class _HrnetTerm(ctypes.Structure):    # include/cpr_hip.h: cpr_hrnet_term
+    _fields_ = [('p', ctypes.c_void_p), ('k', ctypes.c_int)]
+
+
+HRNET_MAX_TERMS, HRNET_MAX_K = 4, 3
+
+
+def hrnet_fuse(terms, size, out=None):
+    """out (N, H, W, C) = ReLU(t_0 + t_1 + ..): the exchange step of HRModule.forward for one output branch (csrc/hrnet.hip).
+    terms: [(map, k)], map an NHWC fp32 tensor (N, H >> k, W >> k, C) read at [y >> k, x >> k] (nearest upsampling by 2**k; k = 0: a
+    map at the output's size), in the reference's order -- source branch ascending; the fp32 sum runs left to right.  size: (H, W).
+    The term count and the divisibility of (H, W) by 2**k are the kernel's own argument check.  out: written when given."""
+    H, W = int(size[0]), int(size[1])
+    N, C = terms[0][0].shape[0], terms[0][0].shape[3]
+    for m, k in terms:
+        assert _check(m).dim() == 4 and 0 <= int(k) <= HRNET_MAX_K and tuple(m.shape) == (N, H >> int(k), W >> int(k), C), \
+            (tuple(m.shape), k, (N, H, W, C))
+    t = (_HrnetTerm * max(1, len(terms)))()
+    for e, (m, k) in zip(t, terms):
+        e.p, e.k = m.data_ptr(), int(k)
+    if out is None:
+        out = torch.empty((N, H, W, C), device=terms[0][0].device, dtype=torch.float32)
+    assert tuple(_check(out).shape) == (N, H, W, C)
+    _lib.call('cpr_hrnet_fuse', t, len(terms), _ptr(out), N, H, W, C, _stream())
+    return out
+
+
+def hrnet_fuse_bwd(dy, y, K, out=None):
+    """The adjoint of hrnet_fuse at its output: dy, y (N, H, W, C) fp32, y the recorded output -> (g, pools, TilePartials) with
+    g = y <= 0 ? +0.0 : dy, pools[k - 1] (N, H >> k, W >> k, C) = the sum of g over 2**k x 2**k blocks for k = 1..K (the gradient of
+    a term that was upsampled by 2**k; 2x2 blocks in row-major order, then 2x2 of those), and the per-block column sums of g -- the
+    bias gradient of every folded BN that fed this branch.  out: (g, pools, partials tensor (blocks, C, 2)) written when given."""
+    N, H, W, C = _check(dy).shape
+    assert tuple(_check(y).shape) == (N, H, W, C) and dy.dim() == 4
+    K = int(K)
+    tiles = _lib.call('cpr_hrnet_fuse_bwd_blocks', N, H, W, C, K, positive=True)
+    if out is None:
+        g = torch.empty_like(dy)
+        pools = [torch.empty((N, H >> k, W >> k, C), device=dy.device, dtype=torch.float32) for k in range(1, K + 1)]
+        part = torch.empty((tiles, C, 2), device=dy.device, dtype=torch.float32)
+    else:
+        g, pools, part = out
+        assert tuple(_check(g).shape) == (N, H, W, C) and tuple(_check(part).shape) == (tiles, C, 2) and len(pools) == K and \
+            all(tuple(_check(p).shape) == (N, H >> k, W >> k, C) for k, p in enumerate(pools, 1))
+    table = (ctypes.c_void_p * max(1, K))(*[p.data_ptr() for p in pools])
+    _lib.call('cpr_hrnet_fuse_bwd', _ptr(dy), _ptr(y), _ptr(g), table, K, _ptr(part), N, H, W, C, _stream())
+    return g, pools, TilePartials(part, tiles, C)
+
+
 # ------------------------------------------------------------------------------------------------ CPR points
 def box_centers(boxes):
     n = boxes.shape[0]

@@ -301,6 +301,79 @@ def hrfpn_state_dict(in_channels, out_channels=256, num_outs=5, seed=1, prefix='
     return sd
 
 
+def hrnet_layout(extra, in_channels=3):
+    """[(conv key, conv shape, norm key)] of the reference's HRNet (hrnet.py:267-518) in its state-dict order: conv1 / bn1, conv2 / bn2,
+    layer1, then per stage its transition and its modules -- per module the branches' blocks, then ``fuse_layers.<i>.<j>``: for j > i
+    a Sequential (conv 1x1 ``0``, norm ``1``, upsample), for j < i a Sequential of i - j Sequentials (conv 3x3 / 2 ``<k>.0``, norm
+    ``<k>.1``), nothing at j == i.  A transition entry: a Sequential (conv 3x3 ``0``, norm ``1``) on an existing branch whose width
+    changes, a Sequential of Sequentials (``<k>.0``, ``<k>.1``) for a new branch, nothing otherwise."""
+    out = []
+
+    def pair(prefix, co, ci, k):
+        out.append((prefix + '.0.weight', (co, ci, k, k), prefix + '.1'))
+
+    def block(p, kind, inplanes, planes):
+        exp = 4 if kind == 'BOTTLENECK' else 1
+        if kind == 'BOTTLENECK':
+            out.append((p + '.conv1.weight', (planes, inplanes, 1, 1), p + '.bn1'))
+            out.append((p + '.conv2.weight', (planes, planes, 3, 3), p + '.bn2'))
+            out.append((p + '.conv3.weight', (planes * 4, planes, 1, 1), p + '.bn3'))
+        else:
+            out.append((p + '.conv1.weight', (planes, inplanes, 3, 3), p + '.bn1'))
+            out.append((p + '.conv2.weight', (planes, planes, 3, 3), p + '.bn2'))
+        if inplanes != planes * exp:
+            pair(p + '.downsample', planes * exp, inplanes, 1)
+        return planes * exp
+
+    out.append(('conv1.weight', (64, in_channels, 3, 3), 'bn1'))
+    out.append(('conv2.weight', (64, 64, 3, 3), 'bn2'))
+    s1 = extra['stage1']
+    c = 64
+    for b in range(s1['num_blocks'][0]):
+        c = block('layer1.%d' % b, s1['block'], c, s1['num_channels'][0])
+    pre = [c]
+    for s in (2, 3, 4):
+        cfg = extra['stage%d' % s]
+        exp = 4 if cfg['block'] == 'BOTTLENECK' else 1
+        cur = [ch * exp for ch in cfg['num_channels']]
+        for i, ch in enumerate(cur):
+            t = 'transition%d.%d' % (s - 1, i)
+            if i < len(pre):
+                if ch != pre[i]:
+                    pair(t, ch, pre[i], 3)
+            else:
+                for j in range(i + 1 - len(pre)):
+                    pair('%s.%d' % (t, j), ch if j == i - len(pre) else pre[-1], pre[-1], 3)
+        nb = cfg['num_branches']
+        inch = list(cur)
+        for m in range(cfg['num_modules']):
+            p = 'stage%d.%d' % (s, m)
+            for b in range(nb):
+                for k in range(cfg['num_blocks'][b]):
+                    inch[b] = block('%s.branches.%d.%d' % (p, b, k), cfg['block'], inch[b], cfg['num_channels'][b])
+            for i in range(nb):
+                for j in range(nb):
+                    f = '%s.fuse_layers.%d.%d' % (p, i, j)
+                    if j > i:
+                        pair(f, inch[i], inch[j], 1)
+                    elif j < i:
+                        for k in range(i - j):
+                            pair('%s.%d' % (f, k), inch[i] if k == i - j - 1 else inch[j], inch[j], 3)
+        pre = inch
+    return out
+
+
+def hrnet_state_dict(extra, seed=0, prefix='', in_channels=3):
+    """A state dict of the reference's HRNet layout for ``extra`` (hrnet_layout): Kaiming-scaled conv weights and BatchNorms with
+    non-trivial gammas, betas and running statistics (_bn)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for key, shape, norm in hrnet_layout(extra, in_channels):
+        sd[prefix + key] = _kaiming(shape, g)
+        _bn(sd, prefix + norm, shape[0], g)
+    return sd
+
+
 def cpr_head_state_dict(num_classes=1, in_channels=256, feat_channels=256, stacked_convs=4, seed=2,
                         prefix='bbox_head.', std=0.01, num_cls_fcs=0, fc_out_channels=1024, binary_ins=False,
                         ins_tower=False, out_bg_cls=False):

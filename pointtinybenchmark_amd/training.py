@@ -321,6 +321,8 @@ class BackwardEngine:
                                           'no slice convolution' % bb.scales)
         if getattr(bb, 'fp32_only', None) and getattr(bb, 'compute_dtype', torch.float32) != torch.float32:
             raise NotImplementedError(bb.fp32_only)      # (a RegNet backbone: backbones/regnet.py, naming ``arch``)
+        if getattr(bb, 'hrnet', False) and bb.freeze_reason() is not None:      # (no frozen_stages: any (conv, BN) pair may be frozen, as a whole)
+            raise NotImplementedError(bb.freeze_reason())
         dev = next(model.parameters()).device
         self._mixed, self._wide = False, {}     # set per step (bf16 compute mode = mixed precision)
         self._sink = None                       # None: p.grad (CprTrainer); dict: id(p) -> fresh tensor (autograd bridge)
@@ -994,11 +996,15 @@ class BackwardEngine:
         """stage: the index of a backbone output (a neck input); a backbone whose out_indices pick among its stages (MobileNetV2)
         maps it to the stage behind it."""
         bb = self.model.backbone
+        if getattr(bb, 'hrnet', False):      # every branch output of an HRNet is reached from every parameter below the last exchange
+            return any(p.requires_grad for p in bb.parameters())
         if getattr(bb, 'sparse_outputs', False):
             stage = sorted(set(bb.out_indices))[stage]
         return any(p.requires_grad for p in getattr(bb, bb.res_layers[stage]).parameters())
 
     def _backward_backbone(self, bb, tape, d_stage):
+        if getattr(bb, 'hrnet', False):      # a DAG of parallel branches (backbones/hrnet.py), not a chain of stages
+            return self._backward_hrnet(bb, tape, d_stage)
         c = bb._cache
         if getattr(bb, 'sparse_outputs', False):      # MobileNetV2: output k is stage out_indices[k] of layer1 .. layer7, conv2
             stages = sorted(set(bb.out_indices))
@@ -1022,6 +1028,141 @@ class BackwardEngine:
         self._wide = {}      # nothing below the lowest trainable block reads a widened copy
         if stem is not None:
             self._backward_stem(bb, stem, dx)
+
+    # ------------------------------------------------------------------ HRNet (backbones/hrnet.py; fp32, eval-mode BatchNorm)
+    @staticmethod
+    def _trains(*mods):
+        return any(p.requires_grad for m in mods if m is not None for p in m.parameters())
+
+    def _done_last(self, *mods):
+        """_done on the last trainable parameter of ``mods`` (conv, bn pairs in completion order), if any."""
+        ps = [p for m in mods for p in ((m.weight,) if isinstance(m, torch.nn.Conv2d) else (m.weight, m.bias)) if p.requires_grad]
+        if ps:
+            self._done(ps[-1])
+
+    def _chain_backward(self, cache, chain, maps, g, cs, need_in, add=None):
+        """A chain of conv -> folded BN layers with a ReLU between them (an HRNet down chain or transition), in reverse.  chain:
+        [(conv, bn)]; maps: the input of every conv (maps[k + 1] = ReLU(BN(conv_k(maps[k]))) for k + 1 < len(chain)); g, cs: the gradient
+        of the last conv's pre-activation output and its column sums.  The intermediates' ReLU masks ride with the data gradients
+        (_conv_bn_backward mask=); ``add`` is summed into the first conv's data gradient.  need_in: whether the gradient wrt maps[0] is
+        wanted; a data gradient is skipped where nothing below it trains.  -> that gradient (``add`` itself when it is not computed)."""
+        for k in range(len(chain) - 1, 0, -1):
+            conv, bn = chain[k]
+            need = need_in or any(self._trains(cv, b) for cv, b in chain[:k])
+            r = self._conv_bn_backward(cache, conv, bn, g, cs, maps[k], need, mask=maps[k], want_colsum=True)
+            self._done_last(conv, bn)
+            if not need:
+                return add
+            g, cs = r[0], r[1]
+        conv, bn = chain[0]
+        r = self._conv_bn_backward(cache, conv, bn, g, cs, maps[0], need_in, add=add)
+        self._done_last(conv, bn)
+        return r if need_in else add
+
+    def _branch_backward(self, cache, blocks, recs, dout, need_in):
+        """A chain of residual blocks (an HRModule branch, layer1) in reverse -> the gradient wrt its input, or None."""
+        dx = dout
+        for k in range(len(blocks) - 1, -1, -1):
+            need = need_in or self._trains(*blocks[:k])
+            if not (need or self._trains(blocks[k])):
+                return None
+            dx = self._block_backward(cache, blocks[k], recs[k], dx, need, mask_in=need and k > 0 and blocks[k].downsample is None)
+        return dx if need_in else None
+
+    def _hrmodule_backward(self, cache, mod, rec, dys, below):
+        """One HRModule in reverse.  dys: the gradient of every exchanged output (None: none arrives); below: something in front of
+        this module trains.  Per output branch i ops.hrnet_fuse_bwd gives g_i = dy_i through the exchange's ReLU, its 2^k x 2^k block
+        sums pool_k(g_i) -- the gradient of the term that was upsampled by 2^k -- and the column sums of g_i, which serve every folded
+        BN that fed branch i (the column sums of a pooled map are those of g_i).  The gradient of branch chain j's output x_j is then
+        summed in a fixed order: the identity term g_j first, then target branch i ascending -- for i < j the data gradient of the
+        fuse 1x1 conv on pool_{j-i}(g_i), for i > j that of the first conv of the down chain -- each riding in the ``add`` operand of
+        the next data gradient.  Then the branch's blocks.  -> the gradient wrt every module input."""
+        nb = mod.num_branches
+        blocks = [list(b) for b in mod.branches]
+        if mod.fuse_layers is None:
+            return [None if dys[0] is None else self._branch_backward(cache, blocks[0], rec['blocks'][0], dys[0], below)]
+        gs, pools, parts = [], [], []
+        for i in range(nb):
+            if dys[i] is None:
+                gs.append(None), pools.append(None), parts.append(None)
+                continue
+            g, pl, part = ops.hrnet_fuse_bwd(dys[i], rec['out'][i], nb - 1 - i)
+            gs.append(g), pools.append(pl), parts.append(part)
+        dxs = []
+        for j in range(nb):
+            need = below or self._trains(*blocks[j])
+            acc = gs[j]
+            for i in range(nb):
+                if i == j or gs[i] is None:
+                    continue
+                fl = mod.fuse_layers[i][j]
+                if i < j:
+                    acc = self._chain_backward(cache, [(fl[0], fl[1])], [rec['x'][j]], pools[i][j - i - 1], parts[i], need, add=acc)
+                else:
+                    acc = self._chain_backward(cache, [(q[0], q[1]) for q in fl], rec['chains'][i][j], gs[i], parts[i], need, add=acc)
+            dxs.append(None if acc is None or not need else self._branch_backward(cache, blocks[j], rec['blocks'][j], acc, below))
+        return dxs
+
+    def _backward_hrnet(self, bb, tape, d_stage):
+        """The HRNet walk.  tape: [the record of HRNet.run]; d_stage: {k: gradient of branch output k (NHWC)}.  Modules in reverse
+        (_hrmodule_backward); in front of a stage its transition: a branch that passes through hands its gradient to the same branch
+        of the previous stage, a transition chain (ReLU after every conv) adds its data gradient to that of the previous stage's LAST
+        branch, in branch order; then layer1, conv2 and conv1 (weight gradient only: the kernel reads the NHWC4 image, the zero fourth
+        column is dropped).  Parameter gradients go through _conv_bn_backward / _folded_param_grads on the side stream; a frozen
+        parameter gets no gradient and no launch, and a data gradient is skipped only where nothing below it trains.  A conv and the
+        BatchNorm behind it train or are frozen together (HRNet.freeze_reason: anything else is refused, naming the pair)."""
+        if bb.freeze_reason() is not None:      # (requires_grad may have changed since the engine was built)
+            raise NotImplementedError(bb.freeze_reason())
+        rec, = [r for r in tape if r.get('hrnet')]
+        c = bb._cache
+        stages = bb.stages()
+        layer1 = list(bb.layer1)
+        stem_trains = self._trains(bb.conv1, bb.bn1, bb.conv2, bb.bn2)
+        below = [stem_trains or self._trains(*layer1)]          # below[s]: something in front of stage s's transition trains
+        for trans, stage in stages[:-1]:
+            below.append(below[-1] or self._trains(*trans) or self._trains(stage))
+        dys = [d_stage.get(k) for k in range(len(bb.out_channels))]
+        for s in range(len(stages) - 1, -1, -1):
+            trans, stage = stages[s]
+            srec = rec['stages'][s]
+            front = below[s] or self._trains(*trans)
+            for m in range(len(stage) - 1, -1, -1):
+                dys = self._hrmodule_backward(c, stage[m], srec['modules'][m], dys, front or self._trains(*list(stage)[:m]))
+            d_prev = [None] * (len(stages[s - 1][1][-1].branches) if s else 1)      # (layer1 is the one branch in front of stage 2)
+            for i, t in enumerate(trans):
+                if t is None:
+                    d_prev[i] = dys[i]
+                    continue
+                if dys[i] is None:
+                    continue
+                chain = [(t[0], t[1])] if isinstance(t[0], torch.nn.Conv2d) else [(q[0], q[1]) for q in t]
+                maps = srec['trans'][i]
+                g, cs = ops.relu_bwd_colsum(dys[i], maps[-1])
+                d_prev[-1] = self._chain_backward(c, chain, maps[:-1], g, cs, below[s], add=d_prev[-1])
+            dys = d_prev
+        self._wide = {}
+        dx = dys[0]
+        if dx is None:
+            return
+        dx = self._branch_backward(c, layer1, rec['layer1'], dx, stem_trains)
+        if dx is None or not stem_trains:
+            return
+        st = rec['stem']
+        g2, cs2 = ops.relu_bwd_colsum(dx, st['o2'])
+        need1 = self._trains(bb.conv1, bb.bn1)
+        r = self._conv_bn_backward(c, bb.conv2, bb.bn2, g2, cs2, st['o1'], need1, mask=st['o1'], want_colsum=True)
+        self._done_last(bb.conv2, bb.bn2)
+        if not need1:
+            return
+        g1, cs1 = r[0], r[1]
+        x4 = st['x4']
+        w1 = bb.conv1.weight
+
+        def wgrad(gw):      # the generic weight-gradient kernel takes Cin % 4 == 0: over the NHWC4 image, the zero 4th column dropped
+            full = ops.conv2d_wgrad(g1, x4, (w1.shape[0], x4.shape[-1], 3, 3), 2, 1)
+            gw.copy_(full[:, :w1.shape[1]])
+        self._folded_param_grads(c, bb.conv1, bb.bn1, cs1, wgrad, g1, x4)
+        self._done_last(bb.conv1, bb.bn1)
 
     def _backward_stem(self, bb, rec, dp):
         """The standard stem (conv1 7x7/2 -> bn1 -> ReLU -> max-pool 3x3/2) given dp = d(pooled map), fp32 (csrc/stem_bwd.hip):
@@ -1729,6 +1870,33 @@ class CprTrainer(BackwardEngine):
             add(neck.reduction_conv.conv.bias, neck.reduction_conv.conv.weight)
         else:
             self._fpn_param_order(neck, add)
+        if getattr(bb, 'hrnet', False):       # (HRNet, _backward_hrnet: the order its walk completes them)
+            def add_block(blk):
+                if blk.kind == 'bottleneck':
+                    add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
+                add(blk.conv2.weight, blk.bn2.weight, blk.bn2.bias, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
+                if blk.downsample is not None:
+                    add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
+
+            def add_chain(chain):
+                for q in reversed(chain):
+                    add(q[0].weight, q[1].weight, q[1].bias)
+            for trans, stage in reversed(bb.stages()):
+                for mod in reversed(list(stage)):
+                    for j in range(mod.num_branches):
+                        for i in range(mod.num_branches if mod.fuse_layers is not None else 0):
+                            if i != j:
+                                fl = mod.fuse_layers[i][j]
+                                add_chain([fl] if i < j else list(fl))
+                        for blk in reversed(list(mod.branches[j])):
+                            add_block(blk)
+                for t in trans:
+                    if t is not None:
+                        add_chain([t] if isinstance(t[0], torch.nn.Conv2d) else list(t))
+            for blk in reversed(list(bb.layer1)):
+                add_block(blk)
+            add(bb.conv2.weight, bb.bn2.weight, bb.bn2.bias, bb.conv1.weight, bb.bn1.weight, bb.bn1.bias)
+            return out
         if getattr(bb, 'sparse_outputs', False):       # (MobileNetV2, _mbv2_block_backward: conv2, then per block linear, depthwise, expand)
             for i in range(len(bb.res_layers) - 1, -1, -1):
                 for blk in reversed(bb.stage_blocks(i)):
@@ -1792,6 +1960,8 @@ class CprTrainer(BackwardEngine):
 
     def _done(self, p):
         """The gradient of ``p`` (and of everything before it in the flat order) has been enqueued."""
+        if not p.requires_grad:      # a frozen parameter of a block that still hands a data gradient down (HRNet: no frozen_stages)
+            return
         end = self.offset[id(p)][1]
         if self.side is not None and self.buckets.would_launch(end):
             # The collective must see the gradients both streams wrote.  The process group orders its own stream behind the
