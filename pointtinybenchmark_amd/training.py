@@ -295,6 +295,20 @@ def _as_list(x):
     return list(x) if isinstance(x, (list, tuple)) else [x]
 
 
+# A unit: the ordered tuple of parameters that one backward call completes together.  The ``*_units`` function beside a rule lists its object's units
+# in the order the rule completes them -- once: CprTrainer's flat order (_backward_order) and every ready point (_done_last) read it.
+def _conv_bn(conv, bn):      # conv -> BatchNorm, folded or on batch statistics
+    return (conv.weight, bn.weight, bn.bias)
+
+
+def _gn_conv(cm):            # a conv -> GroupNorm module (_gn_conv_backward: the GroupNorm backward comes first)
+    return (cm.gn.weight, cm.gn.bias, cm.conv.weight)
+
+
+def _biased(m):              # an output conv or an FC layer
+    return (m.weight, m.bias)
+
+
 _BFP_UNDER_CPR = 'CPRHead takes one pyramid level without a BFP behind it: the BFP neck trains under P2PHead (neck=[FPN | PAFPN, BFP])'
 
 
@@ -374,6 +388,16 @@ class BackwardEngine:
 
     def _done(self, p):
         """The gradient of ``p`` (and of everything before it in the trainer's flat order) has been enqueued."""
+
+    def _done_last(self, *units):
+        """_done on the last trainable parameter of the completed ``units`` (a rule's own ``*_units``, in their order), if any trains."""
+        p = next((p for unit in reversed(units) for p in reversed(unit) if p.requires_grad), None)
+        if p is not None:
+            self._done(p)
+
+    def _units(self, blk):      # the units of a backbone block (its kind's units function), built once per block
+        cache = self.__dict__.setdefault('_block_units', {})      # id(block) -> units
+        return cache.get(id(blk)) or cache.setdefault(id(blk), self._BLOCK_RULES[blk.kind][1](blk))
 
     # ------------------------------------------------------------------ segment API of the autograd bridge
     # (autograd_bridge.py: one torch.autograd.Function per segment; each forward returns (output, state) and the matching
@@ -597,6 +621,13 @@ class BackwardEngine:
         save['tape'] = tape
         return losses, save
 
+    @staticmethod
+    def _head_units(head, towers=True):
+        """CPRHead: the classifiers, then the FC layers (num_cls_fcs > 0) last first, the instance tower's after the class tower's; then
+        (``towers``) the tower last layer first, and after it the instance tower (ins_share_head_feat=False)."""
+        fcs, convs = list(reversed(head.cls_fcs)) + list(reversed(head.ins_fcs)), list(reversed(head.cls_convs)) + list(reversed(head.ins_convs))
+        return [_biased(m) for m in [head.cls_out, head.ins_out] + fcs] + [_gn_conv(cm) for cm in (convs if towers else [])]
+
     def _backward_head(self, head, s, upstream=None):
         """upstream (5,): gradient of the caller's total wrt the forward's loss vector (autograd bridge); None = unit weights."""
         head_tape = s['tape']
@@ -648,7 +679,7 @@ class BackwardEngine:
         if not shared:                      # (binary_ins: the instance classifier has 2 C rows)
             self._g(head.ins_out.weight).copy_(gw[C:J, :, 0, 0])
             self._g(head.ins_out.bias).copy_(gb[C:J])
-        self._done(head.ins_out.bias if not shared else head.cls_out.bias)
+        self._done_last(*self._head_units(head, towers=False))
         dz = ops.conv2d_dgrad(dmap, ops.dgrad_pack(wpad, 1, 0), (dmap.shape[1], dmap.shape[2]))
         # ---- tower, last layer first; layer 0 consumes the (un-activated) FPN output
         order = list(reversed(head_tape))
@@ -658,7 +689,7 @@ class BackwardEngine:
             nxt = order[i + 1] if i + 1 < len(order) else None
             to16 = nxt is not None and self._mixed and MIXED_BF16['dz16'] and FUSED_CAST and nxt['raw'].dtype == torch.bfloat16
             dz = self._gn_conv_backward(rec, dz, relu=True, need_dx=True, dx_bf16=to16)
-            self._done(rec['module'].conv.weight)
+            self._done_last(_gn_conv(rec['module']))
         return dz
 
     def _backward_head_two_towers(self, head, s, dmap, J, Jd, dbias=None):
@@ -687,12 +718,12 @@ class BackwardEngine:
                 self._g(mod.bias).copy_(gb[lo:lo + n])
             first = False
             if name == 'ins':
-                self._done(head.ins_out.bias)
+                self._done_last(*self._head_units(head, towers=False))
             d = ops.conv2d_dgrad(dmap, ops.dgrad_pack(wpad, 1, 0), (dmap.shape[1], dmap.shape[2]))
             for rec in reversed(tape):
                 d = self._gn_conv_backward(rec, d, relu=True, need_dx=True)
                 if name == 'ins':
-                    self._done(rec['module'].conv.weight)
+                    self._done_last(_gn_conv(rec['module']))
             dz = d if dz is None else ops.axpby(dz, d, 1.0, 1.0)
         return dz
 
@@ -763,13 +794,13 @@ class BackwardEngine:
             else:
                 ops.bag_gather_bwd(ds.view(G, K, -1), s['centers'], s['gt_img'], s['offsets'], dfeat, s['stride'], s['radius_cells'])
             dfeats.append((dfeat, tape))
-        self._done((head.ins_fcs[0] if two else head.cls_fcs[0]).bias)       # classifiers and FC layers: complete (flat order)
+        self._done_last(*self._head_units(head, towers=False))       # classifiers and FC layers: complete
         dz = None
         for dfeat, tape in dfeats:
             d = dfeat
             for rec in reversed(tape):
                 d = self._gn_conv_backward(rec, d, relu=True, need_dx=True)
-                self._done(rec['module'].conv.weight)
+                self._done_last(_gn_conv(rec['module']))
             dz = d if dz is None else ops.axpby(dz, d, 1.0, 1.0)
         return dz
 
@@ -794,6 +825,20 @@ class BackwardEngine:
                                 (x.shape[1], x.shape[2]), conv.stride[0])
 
     # ------------------------------------------------------------------ FPN, backbone
+    @classmethod
+    def _neck_units(cls, neck):
+        """A BFP's refine layer (_backward_bfp: it sits between the head and the neck in front of the BFP), then that neck.  An HRFPN:
+        _hrfpn_units.  An FPN / PAFPN: the extra levels' convs last first (_backward_extras), the bottom-up path (_pafpn_units) or FPN's
+        output convs finest first, then the laterals finest first."""
+        bfp, neck = _bfp_of(neck), _inner_neck(neck)
+        refine = [_gn_conv(bfp.refine)] if bfp is not None and bfp.refine_type is not None else []
+        if _is_hrfpn(neck):
+            return refine + cls._hrfpn_units(neck)
+        convs = list(neck.fpn_convs)
+        regular = min(len(neck.lateral_convs), neck.num_outs)
+        outputs = cls._pafpn_units(neck, regular) if _is_pafpn(neck) else [_gn_conv(cm) for cm in convs[:regular]]
+        return refine + [_gn_conv(cm) for cm in reversed(convs[regular:])] + outputs + [_gn_conv(cm) for cm in neck.lateral_convs]
+
     def _backward_neck(self, neck, neck_tape, dz):
         """Everything behind the lateral sums (_backward_outputs), then the top-down chain from the finest lateral to the coarsest
         -> {stage: d(stage output)}.  dz: gradient wrt the (normalised) neck output -- one map (one level), or a list with one per level.
@@ -847,8 +892,13 @@ class BackwardEngine:
         d = ops.bfp_scatter_bwd(gs, bfp.refine_level, by['bfp_scatter']['args'])
         if bfp.refine_type is not None:
             d = self._gn_conv_backward(by['bfp_refine'], d, relu=True, need_dx=True)
-            self._done(bfp.refine.conv.weight)
+            self._done_last(_gn_conv(bfp.refine))
         return ops.bfp_gather_bwd(gs, bfp.refine_level, d, by['bfp_gather']['args'])
+
+    @staticmethod
+    def _hrfpn_units(neck):      # the biased output convs finest first, then the reduction conv: its bias gradient (column sums) before its weight gradient's slices
+        conv = neck.reduction_conv.conv
+        return [_biased(cm.conv) for cm in neck.fpn_convs] + [(conv.bias, conv.weight)]
 
     def _backward_hrfpn_outputs(self, neck, rec, dzs):
         """HRFPN behind its reduced map, in reverse (necks/hrfpn.py run_outputs; T/mmdet/models/necks/hrfpn.py:88-98): the biased 3x3
@@ -870,7 +920,7 @@ class BackwardEngine:
                 gb.copy_(ops.relu_bwd_colsum(dz, None, want_g=False)[1])
             self._param_side(param_grads, dz, x)
             gs.append(ops.conv2d_dgrad(dz, ops.dgrad_pack(conv.weight, stride, pad), (lv.shape[1], lv.shape[2]), stride))
-            self._done(conv.bias)
+            self._done_last(_biased(conv))
         return ops.hrfpn_pool_bwd(gs)
 
     def _backward_hrfpn_inputs(self, neck, rec, d_out, part=None, need_dx_of=None):
@@ -897,7 +947,7 @@ class BackwardEngine:
             self._param_side(level_wgrad, dy, x32)
             need = bool((need_dx_of or self._stage_trainable)(i))
             d_stage[i] = ops.conv2d_dgrad(dy, neck.level_dgrad_pack(i, pitch), tuple(sizes[i])) if need else None
-        self._done(conv.weight)
+        self._done_last(*self._hrfpn_units(neck))
         return d_stage
 
     def _backward_extras(self, neck, recs, dzs, need_src=None):
@@ -922,7 +972,7 @@ class BackwardEngine:
             if src == 'on_input':
                 need_dx = self._stage_trainable(neck.backbone_end_level - 1) if need_src is None else bool(need_src)
             dx = self._gn_conv_backward(rec, d, relu=False, need_dx=need_dx)
-            self._done(rec['module'].conv.weight)
+            self._done_last(_gn_conv(rec['module']))
             if src == 'on_input':
                 d_src = dx
             elif src == 'on_lateral':
@@ -932,6 +982,11 @@ class BackwardEngine:
             else:
                 dzs[n + k - 1] = ops.axpby(dx, dzs[n + k - 1], 1.0, 1.0)
         return dzs[:n], d_lat, d_src
+
+    @staticmethod
+    def _pafpn_units(neck, regular):      # the bottom-up path in reverse: per level, from the top down, its pafpn conv, its downsample conv, its output conv
+        return [_gn_conv(cm) for i in range(regular - 1, -1, -1) for cm in ([neck.pafpn_convs[i - 1]] if i >= 1 else []) +
+                ([neck.downsample_convs[i]] if i < regular - 1 else []) + [neck.fpn_convs[i]]]
 
     def _backward_pafpn(self, neck, recs, dzs, need_src=None):
         """The PAFPN outputs behind the lateral sums (necks/pafpn.py run_outputs; T/mmdet/models/necks/pafpn.py:113-153): the extra
@@ -954,10 +1009,10 @@ class BackwardEngine:
             g = dzs[i]
             if i >= 1:
                 g = self._gn_conv_backward(by['pa_out'][i], g, relu=False, need_dx=True)
-                self._done(by['pa_out'][i]['module'].conv.weight)
+                self._done_last(_gn_conv(by['pa_out'][i]['module']))
             if i < L - 1:
                 g = self._gn_conv_backward(by['down'][i], above, relu=False, need_dx=True, add=g)
-                self._done(by['down'][i]['module'].conv.weight)
+                self._done_last(_gn_conv(by['down'][i]['module']))
             dlats[i] = self._backward_out_conv(by['out'][i], g)
             above = g
         if d_lat is not None:
@@ -967,7 +1022,7 @@ class BackwardEngine:
     def _backward_out_conv(self, rec, dz):
         """FPN output conv (3x3 + GN, no activation): dz wrt its normalised output -> gradient wrt the finest lateral sum."""
         dlat = self._gn_conv_backward(rec, dz, relu=False, need_dx=True)
-        self._done(rec['module'].conv.weight)
+        self._done_last(_gn_conv(rec['module']))
         return dlat
 
     def _backward_laterals(self, neck, lat_recs, douts, need_dx_of=None):
@@ -986,7 +1041,7 @@ class BackwardEngine:
             stage = i + neck.start_level
             need_dx = bool((need_dx_of or self._stage_trainable)(stage))
             d_stage[stage] = self._gn_conv_backward(rec, dlat, relu=False, need_dx=need_dx)
-            self._done(rec['module'].conv.weight)
+            self._done_last(_gn_conv(rec['module']))
             if i + 1 < L:
                 nxt = lat_recs[i + 1]['raw'].shape
                 dlat = ops.upsample_add_bwd(dlat, tuple(nxt))
@@ -1001,6 +1056,16 @@ class BackwardEngine:
         if getattr(bb, 'sparse_outputs', False):
             stage = sorted(set(bb.out_indices))[stage]
         return any(p.requires_grad for p in getattr(bb, bb.res_layers[stage]).parameters())
+
+    @classmethod
+    def _backbone_units(cls, bb):
+        """The HRNet walk, or the stages in reverse with their blocks in reverse (_BLOCK_RULES: each kind's units function), then the stem
+        where it trains (a stem with a reason does not; a trainable non-standard one has no rule and trips the constructor's check)."""
+        if getattr(bb, 'hrnet', False):
+            return cls._hrnet_units(bb)
+        stages = [bb.stage_blocks(i) if getattr(bb, 'sparse_outputs', False) else list(getattr(bb, name)) for i, name in enumerate(bb.res_layers)]
+        units = [u for blocks in reversed(stages) for blk in reversed(blocks) for u in cls._BLOCK_RULES[blk.kind][1](blk)]
+        return units + (cls._stem_units(bb) if bb.stem_train_reason() is None else [])
 
     def _backward_backbone(self, bb, tape, d_stage):
         if getattr(bb, 'hrnet', False):      # a DAG of parallel branches (backbones/hrnet.py), not a chain of stages
@@ -1034,12 +1099,6 @@ class BackwardEngine:
     def _trains(*mods):
         return any(p.requires_grad for m in mods if m is not None for p in m.parameters())
 
-    def _done_last(self, *mods):
-        """_done on the last trainable parameter of ``mods`` (conv, bn pairs in completion order), if any."""
-        ps = [p for m in mods for p in ((m.weight,) if isinstance(m, torch.nn.Conv2d) else (m.weight, m.bias)) if p.requires_grad]
-        if ps:
-            self._done(ps[-1])
-
     def _chain_backward(self, cache, chain, maps, g, cs, need_in, add=None):
         """A chain of conv -> folded BN layers with a ReLU between them (an HRNet down chain or transition), in reverse.  chain:
         [(conv, bn)]; maps: the input of every conv (maps[k + 1] = ReLU(BN(conv_k(maps[k]))) for k + 1 < len(chain)); g, cs: the gradient
@@ -1050,13 +1109,13 @@ class BackwardEngine:
             conv, bn = chain[k]
             need = need_in or any(self._trains(cv, b) for cv, b in chain[:k])
             r = self._conv_bn_backward(cache, conv, bn, g, cs, maps[k], need, mask=maps[k], want_colsum=True)
-            self._done_last(conv, bn)
+            self._done_last(_conv_bn(conv, bn))
             if not need:
                 return add
             g, cs = r[0], r[1]
         conv, bn = chain[0]
         r = self._conv_bn_backward(cache, conv, bn, g, cs, maps[0], need_in, add=add)
-        self._done_last(conv, bn)
+        self._done_last(_conv_bn(conv, bn))
         return r if need_in else add
 
     def _branch_backward(self, cache, blocks, recs, dout, need_in):
@@ -1068,6 +1127,17 @@ class BackwardEngine:
                 return None
             dx = self._block_backward(cache, blocks[k], recs[k], dx, need, mask_in=need and k > 0 and blocks[k].downsample is None)
         return dx if need_in else None
+
+    @classmethod
+    def _hrmodule_units(cls, mod):      # per branch j: the exchange layers that read it (one 1x1 towards i < j, a down chain last first towards i > j), then its blocks
+        units = []
+        for j in range(mod.num_branches):
+            for i in range(mod.num_branches if mod.fuse_layers is not None else 0):
+                if i != j:
+                    units += [_conv_bn(q[0], q[1]) for q in reversed([mod.fuse_layers[i][j]] if i < j else mod.fuse_layers[i][j])]
+            for blk in reversed(list(mod.branches[j])):
+                units += cls._BLOCK_RULES[blk.kind][1](blk)
+        return units
 
     def _hrmodule_backward(self, cache, mod, rec, dys, below):
         """One HRModule in reverse.  dys: the gradient of every exchanged output (None: none arrives); below: something in front of
@@ -1102,6 +1172,19 @@ class BackwardEngine:
                     acc = self._chain_backward(cache, [(q[0], q[1]) for q in fl], rec['chains'][i][j], gs[i], parts[i], need, add=acc)
             dxs.append(None if acc is None or not need else self._branch_backward(cache, blocks[j], rec['blocks'][j], acc, below))
         return dxs
+
+    @classmethod
+    def _hrnet_units(cls, bb):      # stages last first -- their modules last first, then their transition in branch order (one triple or a chain, last first) --, layer1, the stem
+        units = []
+        for trans, stage in reversed(bb.stages()):
+            for mod in reversed(list(stage)):
+                units += cls._hrmodule_units(mod)
+            for t in trans:
+                if t is not None:
+                    units += [_conv_bn(q[0], q[1]) for q in reversed([t] if isinstance(t[0], torch.nn.Conv2d) else t)]
+        for blk in reversed(list(bb.layer1)):
+            units += cls._BLOCK_RULES[blk.kind][1](blk)
+        return units + cls._stem_units(bb)
 
     def _backward_hrnet(self, bb, tape, d_stage):
         """The HRNet walk.  tape: [the record of HRNet.run]; d_stage: {k: gradient of branch output k (NHWC)}.  Modules in reverse
@@ -1151,7 +1234,7 @@ class BackwardEngine:
         g2, cs2 = ops.relu_bwd_colsum(dx, st['o2'])
         need1 = self._trains(bb.conv1, bb.bn1)
         r = self._conv_bn_backward(c, bb.conv2, bb.bn2, g2, cs2, st['o1'], need1, mask=st['o1'], want_colsum=True)
-        self._done_last(bb.conv2, bb.bn2)
+        self._done_last(self._stem_units(bb)[0])
         if not need1:
             return
         g1, cs1 = r[0], r[1]
@@ -1162,7 +1245,13 @@ class BackwardEngine:
             full = ops.conv2d_wgrad(g1, x4, (w1.shape[0], x4.shape[-1], 3, 3), 2, 1)
             gw.copy_(full[:, :w1.shape[1]])
         self._folded_param_grads(c, bb.conv1, bb.bn1, cs1, wgrad, g1, x4)
-        self._done_last(bb.conv1, bb.bn1)
+        self._done_last(*self._stem_units(bb))
+
+    @staticmethod
+    def _stem_units(bb):      # HRNet's conv2 then conv1 (_backward_hrnet), MobileNetV2's conv1 module, else conv1 / bn1 (the standard and the RegNet stem)
+        if getattr(bb, 'sparse_outputs', False):
+            return [_conv_bn(bb.conv1.conv, bb.conv1.bn)]
+        return ([_conv_bn(bb.conv2, bb.bn2)] if getattr(bb, 'hrnet', False) else []) + [_conv_bn(bb.conv1, bb.bn1)]
 
     def _backward_stem(self, bb, rec, dp):
         """The standard stem (conv1 7x7/2 -> bn1 -> ReLU -> max-pool 3x3/2) given dp = d(pooled map), fp32 (csrc/stem_bwd.hip):
@@ -1179,7 +1268,7 @@ class BackwardEngine:
             c1, bn = bb.conv1.conv, bb.conv1.bn
             dy, cs = dp if isinstance(dp, tuple) else ops.relu6_bwd_colsum(dp, rec['out'])
             self._folded_param_grads(bb._cache, c1, bn, cs, lambda gw: ops.stem3x3s2_wgrad(dy, x, planar=planar, out=gw), dy, x, stem=True)
-            self._done([p for p in (c1.weight, bn.weight, bn.bias) if p.requires_grad][-1])
+            self._done_last(*self._stem_units(bb))
             return
         c1, bn = bb.conv1, bb.bn1
         w = c1.weight
@@ -1189,7 +1278,7 @@ class BackwardEngine:
             # weight gradient of csrc/stem3x3_bwd.hip, then bn_fold_bwd as below
             dy, cs = ops.relu_bwd_colsum(dp, rec['out'])
             self._folded_param_grads(bb._cache, c1, bn, cs, lambda gw: ops.stem3x3s2_wgrad(dy, x, planar=planar, out=gw), dy, x, stem=True)
-            self._done([p for p in (w, bn.weight, bn.bias) if p.requires_grad][-1])
+            self._done_last(*self._stem_units(bb))
             return
         dy, part = ops.stem_pool_bwd(dp, rec['arg'], rec['conv_hw'])
         if rec.get('batch_stats'):
@@ -1202,7 +1291,7 @@ class BackwardEngine:
                 self._param_side(lambda: ops.stem_wgrad_f32(dconv, x, planar=planar, out=self._g(w)), dconv, x)
         else:
             self._folded_param_grads(bb._cache, c1, bn, part, lambda gw: ops.stem_wgrad_f32(dy, x, planar=planar, out=gw), dy, x, stem=True)
-        self._done([p for p in (w, bn.weight, bn.bias) if p.requires_grad][-1])
+        self._done_last(*self._stem_units(bb))
 
     def _bf16_grads(self, conv, x, has_add, need_dx):
         """(w16, d16): whether the weight / data gradient of the folded conv ``conv`` (input map x, a shortcut gradient summed into
@@ -1329,6 +1418,11 @@ class BackwardEngine:
             return r[0], r[1], None
         return r
 
+    @staticmethod
+    def _base_block_units(blk):      # conv3 (not a BasicBlock), conv2, conv1 and the shortcut: the folded rule, the batch-statistics rule, the padded RegNet block
+        units = [_conv_bn(blk.conv3, blk.bn3)] if blk.kind != 'basic' else []
+        return units + [_conv_bn(blk.conv2, blk.bn2)] + BackwardEngine._conv1_shortcut_units(blk)
+
     def _block_backward(self, cache, blk, rec, dout, need_dx, keep=None, mask_in=False):
         """dout: the gradient of the block's output -- or the triple (g, column sums, bf16 g | None) when the block above has already
         taken it through this block's output ReLU.  mask_in (the caller guarantees that x is the output of the block whose backward
@@ -1340,14 +1434,9 @@ class BackwardEngine:
         # recorded map up front -- 5.6 % of the step's kernel time in torch copy kernels)
         if rec.get('batch_stats'):
             return self._block_backward_batch_stats(cache, blk, rec, dout, need_dx)
-        if blk.kind == 'bottle2neck':
-            return self._bottle2neck_backward(cache, blk, rec, dout, need_dx)
-        if blk.kind in ('mbv2', 'mbv2_conv2'):
-            return self._mbv2_block_backward(cache, blk, rec, dout, need_dx)
-        if blk.kind == 'regnet':
-            return self._regnet_block_backward(cache, blk, rec, dout, need_dx)
-        if blk.kind == 'resnest':
-            return self._resnest_block_backward(cache, blk, rec, dout, need_dx)
+        rule = self._BLOCK_RULES[blk.kind][0]
+        if rule is not None:      # (None: a BasicBlock / Bottleneck, the rule below)
+            return getattr(self, rule)(cache, blk, rec, dout, need_dx)
         mixed = self._mixed
         x = rec['x']
         g3, cs3, g3h = self._out_relu_backward(rec, dout, want16=mixed)
@@ -1359,16 +1448,14 @@ class BackwardEngine:
             del o2
             g1, cs1, g1h = self._conv_bn_backward(cache, blk.conv2, blk.bn2, g2, cs2, o1, True, mask=o1, want_colsum=True, g16=g2h, want16=True,
                                                   need32=not self._reads_bf16_only(blk.conv1, x, blk.downsample is None, need_dx))
-            last = blk.bn3
         else:
             g1, cs1, g1h = self._conv_bn_backward(cache, blk.conv2, blk.bn2, g3, cs3, o1, True, mask=o1, want_colsum=True, g16=g3h, want16=True,
                                                   need32=not self._reads_bf16_only(blk.conv1, x, blk.downsample is None, need_dx))
-            last = blk.bn2
         del o1
-        self._done(last.bias if last.bias.requires_grad else blk.conv2.weight)
+        self._done_last(self._units(blk)[0])
         if mask_in and need_dx and blk.downsample is None:
             dx = self._conv_bn_backward(cache, blk.conv1, blk.bn1, g1, cs1, x, True, mask=x, add=g3, want_colsum=True, g16=g1h, want16=mixed)
-            self._done(blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight)
+            self._done_last(*self._units(blk))
             return dx if mixed else (dx[0], dx[1], None)
         return self._conv1_shortcut_backward(cache, blk, rec, g1, cs1, g3, cs3, need_dx, g1h=g1h, g3h=g3h)
 
@@ -1381,6 +1468,10 @@ class BackwardEngine:
         r = ops.relu_bwd_colsum(dout, rec['out'], want16=want16)
         return r if want16 else (r[0], r[1], None)
 
+    @staticmethod
+    def _conv1_shortcut_units(blk):      # conv1, then the projection shortcut where there is one: the end of every residual block's units
+        return [_conv_bn(blk.conv1, blk.bn1)] + ([_conv_bn(blk.ds_conv, blk.ds_bn)] if blk.downsample is not None else [])
+
     def _conv1_shortcut_backward(self, cache, blk, rec, g1, cs1, g3, cs3, need_dx, g1h=None, g3h=None, padded=False):
         """The end of a folded block's walk: conv1's rule given g1 = d(conv1's pre-activation output), the shortcut -- an identity (g3
         summed into conv1's data gradient) or the projection conv, which sees the same g3 (no activation on that branch) -- and the
@@ -1390,7 +1481,6 @@ class BackwardEngine:
         x = rec['x']
         if blk.downsample is None:
             dx = rule(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, add=g3, g16=g1h)
-            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
         else:
             dx = rule(cache, blk.conv1, blk.bn1, g1, cs1, x, need_dx, g16=g1h)
             pool = blk.ds_pool
@@ -1403,11 +1493,14 @@ class BackwardEngine:
                     dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
             else:
                 dx = rule(cache, blk.ds_conv, blk.ds_bn, g3, cs3, x, need_dx, add=dx, g16=g3h)
-            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
-        self._done(tail)
+        self._done_last(*self._units(blk))
         return dx
 
     # ------------------------------------------------------------------ Res2Net (backbones/res2net.py; fp32, eval-mode BatchNorm)
+    @staticmethod
+    def _bottle2neck_units(blk):      # conv3, the slice convs last first, conv1 and the shortcut
+        return [_conv_bn(conv, bn) for conv, bn in [(blk.conv3, blk.bn3)] + list(zip(blk.convs, blk.bns))[::-1]] + BackwardEngine._conv1_shortcut_units(blk)
+
     def _bottle2neck_backward(self, cache, blk, rec, dout, need_dx):
         """The Bottle2neck rule.  G = d(concatenated map) out of conv3's data gradient; walking i = scales-2 .. 0: g_i = (G[slice i] +
         carry) * (y[i] > 0) in place with its column sums (ops.res2_relu_bwd; carry = the data gradient of conv i+1, which read y[i] in
@@ -1438,6 +1531,12 @@ class BackwardEngine:
         return self._conv1_shortcut_backward(cache, blk, rec, g1, cs1, g3, cs3, need_dx, padded=True)
 
     # ------------------------------------------------------------------ ResNeSt (backbones/resnest.py; fp32, eval-mode BatchNorm)
+    @staticmethod
+    def _resnest_block_units(blk):      # conv3, the six attention-MLP parameters (one launch), conv2.conv / bn0, conv1 and the shortcut
+        sa = blk.conv2
+        return [_conv_bn(blk.conv3, blk.bn3), (sa.fc2.weight, sa.fc2.bias, sa.fc1.weight, sa.fc1.bias, sa.bn1.weight, sa.bn1.bias),
+                _conv_bn(sa.conv, sa.bn0)] + BackwardEngine._conv1_shortcut_units(blk)
+
     def _resnest_block_backward(self, cache, blk, rec, dout, need_dx):
         """The split-attention block's rule.  conv3's rule gives do = d(o) (no activation sits between the attention-weighted sum, or
         its pool, and conv3); datt = the pixel reduction of dv * u (ops.splat_attn_grad, dv the pool's adjoint of do in a pooled
@@ -1449,7 +1548,7 @@ class BackwardEngine:
         g3, cs3, _ = self._out_relu_backward(rec, dout)          # also the shortcut gradient
         sa, w = blk.conv2, blk.width
         do = self._conv_bn_backward(cache, blk.conv3, blk.bn3, g3, cs3, rec['o'], True)
-        self._done(blk.bn3.bias if blk.bn3.bias.requires_grad else blk.conv3.weight)
+        self._done_last(self._units(blk)[0])
         datt = ops.splat_attn_grad(do, u, pool=blk.pool)
         sm, _ = folded_bn(cache, sa.bn1)
         named = dict(fc2_w=sa.fc2.weight, fc2_b=sa.fc2.bias, fc1_w=sa.fc1.weight, fc1_b=sa.fc1.bias, bn_w=sa.bn1.weight, bn_b=sa.bn1.bias)
@@ -1469,7 +1568,7 @@ class BackwardEngine:
                        lambda: ops.dgrad_pack(ops.splat_dense_weight(conv.weight), 1, 1, scale=scale))      # (lapses with the weight epoch)
         g1, cs1 = ops.relu_bwd_colsum(ops.conv2d_dgrad(du, pt, (o1.shape[1], o1.shape[2]), 1), o1)      # conv1's ReLU
         del du
-        self._done(bn.bias if bn.bias.requires_grad else conv.weight)
+        self._done_last(*self._units(blk)[:3])
         return self._conv1_shortcut_backward(cache, blk, rec, g1, cs1, g3, cs3, need_dx)
 
     # ------------------------------------------------------------------ maps at a padded pitch; RegNet (backbones/regnet.py; fp32, eval-mode BatchNorm)
@@ -1516,10 +1615,14 @@ class BackwardEngine:
         g1, cs1 = ops.relu_bwd_colsum(d1, o1)
         cs1 = cs1[:W]
         del d1
-        self._done(blk.bn3.bias if blk.bn3.bias.requires_grad else blk.conv2.weight)
+        self._done_last(self._units(blk)[0])
         return self._conv1_shortcut_backward(cache, blk, rec, g1, cs1, g3, cs3, need_dx, padded=True)
 
     # ------------------------------------------------------------------ MobileNetV2 (backbones/mobilenet_v2.py; fp32, eval-mode BatchNorm)
+    @staticmethod
+    def _mbv2_block_units(blk):      # an inverted-residual block: linear, depthwise, expand (where there is one).  conv2 (kind 'mbv2_conv2'): itself
+        return [_conv_bn(m.conv, m.bn) for m in ([blk] if blk.kind == 'mbv2_conv2' else reversed(blk.conv_modules()))]
+
     def _mbv2_block_backward(self, cache, blk, rec, dout, need_dx):
         """The rule of an inverted-residual block (kind 'mbv2') given dout at its (linear) output, and of conv2 (kind 'mbv2_conv2').
           linear conv -> BN   g = dout, its column sums from relu6_bwd_colsum(y=None), x = o2; the data gradient comes back unmasked
@@ -1535,7 +1638,7 @@ class BackwardEngine:
         if blk.kind == 'mbv2_conv2':      # conv2 -> BN -> ReLU6: the recorded map is the clamped one
             g, cs = ops.relu6_bwd_colsum(dout, rec['out'])
             dx = self._padded_conv_bn_backward(cache, blk.conv, blk.bn, g, cs[:blk.conv.out_channels], rec['x'], need_dx)
-            self._done(blk.trainable()[-1])
+            self._done_last(*self._units(blk))
             return dx
         x, o1, o2 = rec['x'], rec['o1'], rec['o2']
         M, O = blk.mid_channels, blk.out_channels
@@ -1545,17 +1648,17 @@ class BackwardEngine:
         g2, cs2 = ops.relu6_bwd_colsum(d2, o2)
         del d2
         self._folded_param_grads(cache, dw.conv, dw.bn, cs2[:M], lambda gw: ops.dw_wgrad(g2, o1, M, blk.stride, in_clamp6=True, out=gw), g2, o1)
-        last = [p for m in reversed(blk.conv_modules()) for p in m.trainable()][-1]
+        units = self._units(blk)
         if not (blk.with_expand_conv or need_dx):
-            self._done(last)
+            self._done_last(*units)
             return None
         g1, cs1 = ops.dw_dgrad(g2, dw_dgrad_pack(cache, dw.conv, dw.bn), (o1.shape[1], o1.shape[2]), blk.stride, mask6=o1, colsum=True)
         if not blk.with_expand_conv:
-            self._done(last)
+            self._done_last(*units)
             return g1, cs1
         ec = blk.expand_conv
         dx = self._padded_conv_bn_backward(cache, ec.conv, ec.bn, g1, cs1, x, need_dx, add=dout if blk.with_res_shortcut else None)
-        self._done(last)
+        self._done_last(*units)
         return dx
 
     # ------------------------------------------------------------------ training-mode BatchNorm (ResNet norm_eval=False)
@@ -1599,11 +1702,9 @@ class BackwardEngine:
             o2 = rec['o2']
             d2 = self._conv_bn_backward_batch_stats(cache, blk.conv3, blk.bn3, rec, 'bn3', g3, m3, o2, True)
             d1 = self._conv_bn_backward_batch_stats(cache, blk.conv2, blk.bn2, rec, 'bn2', d2, o2, o1, True)
-            last = blk.bn3
         else:
             d1 = self._conv_bn_backward_batch_stats(cache, blk.conv2, blk.bn2, rec, 'bn2', g3, m3, o1, True)
-            last = blk.bn2
-        self._done(last.bias if last.bias.requires_grad else blk.conv2.weight)
+        self._done_last(self._units(blk)[0])
         dx = self._conv_bn_backward_batch_stats(cache, blk.conv1, blk.bn1, rec, 'bn1', d1, o1, x, need_dx, add=ident)
         if blk.downsample is not None:
             pool = blk.ds_pool
@@ -1613,11 +1714,14 @@ class BackwardEngine:
                     dx = ops.avgpool_bwd(dxp, (x.shape[1], x.shape[2]), pool, add=dx)
             else:
                 dx = self._conv_bn_backward_batch_stats(cache, blk.ds_conv, blk.ds_bn, rec, 'bnd', g3, m3, x, need_dx, add=dx)
-            tail = blk.ds_bn.bias if blk.ds_bn.bias.requires_grad else blk.ds_conv.weight
-        else:
-            tail = blk.bn1.bias if blk.bn1.bias.requires_grad else blk.conv1.weight
-        self._done(tail)
+        self._done_last(*self._units(blk))
         return dx
+
+    # kind -> (the name of the block's rule | None: _block_backward itself, its units function); batch statistics: _block_backward_batch_stats, the base units
+    _BLOCK_RULES = {'basic': (None, _base_block_units), 'bottleneck': (None, _base_block_units),
+                    'regnet': ('_regnet_block_backward', _base_block_units), 'bottle2neck': ('_bottle2neck_backward', _bottle2neck_units),
+                    'resnest': ('_resnest_block_backward', _resnest_block_units),
+                    'mbv2': ('_mbv2_block_backward', _mbv2_block_units), 'mbv2_conv2': ('_mbv2_block_backward', _mbv2_block_units)}
 
 
 class CprTrainer(BackwardEngine):
@@ -1850,113 +1954,13 @@ class CprTrainer(BackwardEngine):
                     b[lo:hi].copy_(st[name].reshape(-1))
         self.steps = int(n)
 
-    # ------------------------------------------------------------------ parameter order = gradient completion order
+    # ------------------------------------------------------------------ parameter order = gradient completion order, read off the rules' units
     def _backward_order(self):
+        """The trainable parameters in the order the backward completes their gradients: the units of the head, a BFP's refine layer, the neck
+        in front of it and the backbone (each stated once, by the ``*_units`` function beside its rule); a shared parameter where it comes first."""
         m = self.model
-        head, neck, bb = m.bbox_head, _inner_neck(m.neck), m.backbone
-        out = []
-
-        def add(*ps):
-            for p in ps:
-                if p is not None and p.requires_grad and all(p is not q for q in out):
-                    out.append(p)
-        self._head_param_order(head, add)
-        bfp = _bfp_of(m.neck)
-        if bfp is not None and bfp.refine_type is not None:      # BFP's refine layer sits between the head and the neck (_backward_bfp)
-            add(bfp.refine.gn.weight, bfp.refine.gn.bias, bfp.refine.conv.weight)
-        if _is_hrfpn(neck):       # (_backward_hrfpn_outputs: the output convs, finest first; _backward_hrfpn_inputs: the reduction conv)
-            for cm in neck.fpn_convs:
-                add(cm.conv.weight, cm.conv.bias)
-            add(neck.reduction_conv.conv.bias, neck.reduction_conv.conv.weight)
-        else:
-            self._fpn_param_order(neck, add)
-        if getattr(bb, 'hrnet', False):       # (HRNet, _backward_hrnet: the order its walk completes them)
-            def add_block(blk):
-                if blk.kind == 'bottleneck':
-                    add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
-                add(blk.conv2.weight, blk.bn2.weight, blk.bn2.bias, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
-                if blk.downsample is not None:
-                    add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
-
-            def add_chain(chain):
-                for q in reversed(chain):
-                    add(q[0].weight, q[1].weight, q[1].bias)
-            for trans, stage in reversed(bb.stages()):
-                for mod in reversed(list(stage)):
-                    for j in range(mod.num_branches):
-                        for i in range(mod.num_branches if mod.fuse_layers is not None else 0):
-                            if i != j:
-                                fl = mod.fuse_layers[i][j]
-                                add_chain([fl] if i < j else list(fl))
-                        for blk in reversed(list(mod.branches[j])):
-                            add_block(blk)
-                for t in trans:
-                    if t is not None:
-                        add_chain([t] if isinstance(t[0], torch.nn.Conv2d) else list(t))
-            for blk in reversed(list(bb.layer1)):
-                add_block(blk)
-            add(bb.conv2.weight, bb.bn2.weight, bb.bn2.bias, bb.conv1.weight, bb.bn1.weight, bb.bn1.bias)
-            return out
-        if getattr(bb, 'sparse_outputs', False):       # (MobileNetV2, _mbv2_block_backward: conv2, then per block linear, depthwise, expand)
-            for i in range(len(bb.res_layers) - 1, -1, -1):
-                for blk in reversed(bb.stage_blocks(i)):
-                    for m in ([blk] if blk.kind == 'mbv2_conv2' else reversed(blk.conv_modules())):
-                        add(m.conv.weight, m.bn.weight, m.bn.bias)
-            if bb.stem_train_reason() is None:
-                add(bb.conv1.conv.weight, bb.conv1.bn.weight, bb.conv1.bn.bias)
-            return out
-        for name in reversed(bb.res_layers):
-            for blk in reversed(list(getattr(bb, name))):
-                if blk.kind == 'bottle2neck':       # (Res2Net, _bottle2neck_backward: conv3, the slice convs last first, conv1)
-                    add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
-                    for conv, bn in reversed(list(zip(blk.convs, blk.bns))):
-                        add(conv.weight, bn.weight, bn.bias)
-                    add(blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
-                    if blk.downsample is not None:
-                        add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
-                    continue
-                if blk.kind == 'resnest':       # (ResNeSt, _resnest_block_backward: conv3, the attention MLP, conv2.conv / bn0, conv1)
-                    sa = blk.conv2
-                    add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
-                    add(sa.fc2.weight, sa.fc2.bias, sa.fc1.weight, sa.fc1.bias, sa.bn1.weight, sa.bn1.bias)
-                    add(sa.conv.weight, sa.bn0.weight, sa.bn0.bias, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
-                    if blk.downsample is not None:
-                        add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
-                    continue
-                if blk.kind in ('bottleneck', 'regnet'):       # ('regnet': a padded RegNet block, _regnet_block_backward -- the same walk)
-                    add(blk.conv3.weight, blk.bn3.weight, blk.bn3.bias)
-                add(blk.conv2.weight, blk.bn2.weight, blk.bn2.bias, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias)
-                if blk.downsample is not None:
-                    add(blk.ds_conv.weight, blk.ds_bn.weight, blk.ds_bn.bias)
-        if bb.stem_train_reason() is None:          # frozen_stages < 0: the stem's gradients complete last
-            add(bb.conv1.weight, bb.bn1.weight, bb.bn1.bias)     # (a deep stem always has a reason: it does not train)
-        return out      # (a trainable non-standard stem has no backward rule and trips the constructor's check)
-
-    @staticmethod
-    def _fpn_param_order(neck, add):
-        """An FPN / PAFPN in its backward's order: extra levels, the bottom-up path, output convs, laterals."""
-        regular = min(len(neck.lateral_convs), neck.num_outs)
-        for cm in reversed(list(neck.fpn_convs)[regular:]):      # the extra levels' convs, last first (_backward_extras)
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
-        if _is_pafpn(neck):       # the bottom-up path in reverse (_backward_pafpn): per level its pafpn conv, downsample conv, output conv
-            for i in range(regular - 1, -1, -1):
-                for cm in ([neck.pafpn_convs[i - 1]] if i >= 1 else []) + ([neck.downsample_convs[i]] if i < regular - 1 else []):
-                    add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
-                add(neck.fpn_convs[i].gn.weight, neck.fpn_convs[i].gn.bias, neck.fpn_convs[i].conv.weight)
-        for cm in list(neck.fpn_convs)[:regular]:
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
-        for cm in neck.lateral_convs:
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
-
-    @staticmethod
-    def _head_param_order(head, add):
-        add(head.cls_out.weight, head.cls_out.bias, head.ins_out.weight, head.ins_out.bias)
-        for fc in list(reversed(list(getattr(head, 'cls_fcs', [])))) + list(reversed(list(getattr(head, 'ins_fcs', [])))):
-            add(fc.weight, fc.bias)                                    # num_cls_fcs > 0: weight before bias, ins_fcs[0] last
-        for cm in reversed(list(head.cls_convs)):
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
-        for cm in reversed(list(getattr(head, 'ins_convs', []))):      # ins_share_head_feat=False: the second tower, last
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+        units = self._head_units(m.bbox_head) + self._neck_units(m.neck) + self._backbone_units(m.backbone)
+        return list({id(p): p for unit in units for p in unit if p.requires_grad}.values())
 
     def _done(self, p):
         """The gradient of ``p`` (and of everything before it in the flat order) has been enqueued."""
@@ -2053,13 +2057,8 @@ class P2PHeadRules:
         return {'loss_cls': [out[b, 0] for b in range(B)], 'loss_pts': [out[b, 1] for b in range(B)]}
 
     @staticmethod
-    def _head_param_order(head, add):
-        add(head.reg_out.weight, head.reg_out.bias)
-        for cm in reversed(list(head.reg_convs)):
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
-        add(head.cls_out.weight, head.cls_out.bias)
-        for cm in reversed(list(head.cls_convs)):
-            add(cm.gn.weight, cm.gn.bias, cm.conv.weight)
+    def _head_units(head):      # P2PHead (_backward_head): the regression tower -- output conv, then its layers last first --, then the class tower
+        return [_biased(head.reg_out)] + [_gn_conv(cm) for cm in reversed(head.reg_convs)] + [_biased(head.cls_out)] + [_gn_conv(cm) for cm in reversed(head.cls_convs)]
 
     @staticmethod
     def _forward_head(head, lazy, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes):
@@ -2108,7 +2107,7 @@ class P2PHeadRules:
                     ds.append(self._p2p_out_conv_backward_mixed(tape, dout, n_out))
                 else:
                     ds.append(self._out_conv_backward(tape[-1], dout, n_out))
-        self._done(out.bias)
+        self._done_last(_biased(out))
         for i in range(len(tapes[0]) - 2, -1, -1):
             cm = tapes[0][i]['module']
             for lvl, tape in enumerate(tapes):
@@ -2116,7 +2115,7 @@ class P2PHeadRules:
                 to16 = i > 0 and self._mixed and MIXED_BF16['dz16'] and FUSED_CAST and tape[i - 1]['raw'].dtype == torch.bfloat16
                 with self._level_grads(lvl, (cm.gn.weight, cm.gn.bias, cm.conv.weight)):
                     ds[lvl] = self._gn_conv_backward(tape[i], ds[lvl], relu=True, need_dx=True, dx_bf16=to16)
-            self._done(cm.conv.weight)
+            self._done_last(_gn_conv(cm))
         return ds
 
     def _p2p_out_conv_backward_mixed(self, tape, dout, n_out):

@@ -23,6 +23,7 @@ from pointtinybenchmark_amd import synthetic
 from tests import bfp_ref as BR
 from tests import pafpn_ref as PR
 from tests.fpn_extra_ref import fpn_forward
+from tests.ready_point_check import run_checked_backward
 from tests.test_gpu_fpn_extra import GRID4, _cells, _data, _NeckOnly, _record_assignments
 
 pytestmark = pytest.mark.gpu
@@ -502,21 +503,8 @@ def test_three_sgd_steps_lower_the_loss(kind):
 def test_bucket_ready_points_cover_the_refine_conv(kind):
     from pointtinybenchmark_amd import training
     m, _ = build_locator(kind)
-    seen = []
-
-    class Checked(training.P2PTrainer):
-        def _done(self, p):
-            end = self.offset[id(p)][1]
-            torch.cuda.synchronize()
-            assert not bool(torch.isnan(self.flat_g[:end]).any()), 'gradient prefix [0, %d) declared final unwritten' % end
-            seen.append(end)
-    tr = Checked(m)
-    tr.flat_g.fill_(float('nan'))
     _, data = _data(seed=8)
-    tr.forward_backward(**data)
-    torch.cuda.synchronize()
-    assert not bool(torch.isnan(tr.flat_g).any())
-    assert seen and max(seen) == tr.flat_g.numel() and seen == sorted(seen)
+    tr, seen = run_checked_backward(training.P2PTrainer, m, data)
     mods = list(m.neck.inner.fpn_convs) + ([m.neck.bfp.refine] if m.neck.bfp.refine_type else [])
     assert {tr.offset[id(cm.conv.weight)][1] for cm in mods} <= set(seen), 'every neck conv, the refine conv included, declares its gradients final'
 

@@ -255,12 +255,12 @@ def test_top_down_add_between_levels_of_equal_size():
 
 
 # ------------------------------------------------------------------------------------------------ locators
-def _locator(head, seed=3):
-    """BasicLocator on the dc5_18 backbone (R18, strides (1, 2, 2, 1), dilations (1, 1, 1, 2): levels of 1/4, 1/8, 1/16, 1/16): P2P with
+def _locator(head, seed=3, depth=18):
+    """BasicLocator on the dc5_18 backbone (R18; depth=50: the same on R50, strides (1, 2, 2, 1), dilations (1, 1, 1, 2): levels of 1/4, 1/8, 1/16, 1/16): P2P with
     a 4-level FPN, CPR with num_outs=1."""
     import pointtinybenchmark_amd as P
     from bench import model_cfg, p2p_model_cfg
-    cfg = model_cfg(18, 1) if head == 'cpr' else p2p_model_cfg(18, 2)
+    cfg = model_cfg(depth, 1) if head == 'cpr' else p2p_model_cfg(depth, 2)
     cfg['backbone'] = dict(cfg['backbone'], **DR.DC5)
     C, npts = 1, 1
     if head == 'p2p':
@@ -268,9 +268,9 @@ def _locator(head, seed=3):
         cfg['neck'] = dict(cfg['neck'], num_outs=4)
         cfg['bbox_head'] = dict(cfg['bbox_head'], strides=[4, 8, 16, 16], point_anchor=[(-.25, -.25), (.25, -.25), (-.25, .25), (.25, .25)])
     m = P.build_detector(cfg).cuda()
-    sd = synthetic.locator_state_dict(18, C, 0, head, seed, head_std=0.05, num_points=npts)
+    sd = synthetic.locator_state_dict(depth, C, 0, head, seed, head_std=0.05, num_points=npts)
     if head == 'p2p':
-        sd.update(synthetic.fpn_state_dict(synthetic.backbone_out_channels(18), 256, 0, 4, seed + 1))
+        sd.update(synthetic.fpn_state_dict(synthetic.backbone_out_channels(depth), 256, 0, 4, seed + 1))
     m.load_state_dict(sd, strict=True)
     m.train()
     return m

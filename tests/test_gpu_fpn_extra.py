@@ -22,6 +22,7 @@ from oracle import cpr_oracle as O
 from oracle import p2p_options_oracle as PO
 from pointtinybenchmark_amd import synthetic
 from tests import fpn_extra_ref as FR
+from tests.ready_point_check import run_checked_backward
 
 pytestmark = pytest.mark.gpu
 
@@ -362,21 +363,8 @@ def test_three_sgd_steps_with_extras_lower_the_loss(kind):
 def test_bucket_ready_points_with_extras_only_cover_finished_gradients(kind):
     from pointtinybenchmark_amd import training
     m, _ = build_locator(kind)
-    seen = []
-
-    class Checked(training.P2PTrainer):
-        def _done(self, p):
-            end = self.offset[id(p)][1]
-            torch.cuda.synchronize()
-            assert not bool(torch.isnan(self.flat_g[:end]).any()), 'gradient prefix [0, %d) declared final unwritten' % end
-            seen.append(end)
-    tr = Checked(m)
-    tr.flat_g.fill_(float('nan'))
     _, data = _data(seed=8)
-    tr.forward_backward(**data)
-    torch.cuda.synchronize()
-    assert not bool(torch.isnan(tr.flat_g).any())
-    assert seen and max(seen) == tr.flat_g.numel() and seen == sorted(seen)
+    tr, seen = run_checked_backward(training.P2PTrainer, m, data)
     ends = {tr.offset[id(cm.conv.weight)][1] for cm in list(m.neck.fpn_convs)[len(m.neck.lateral_convs):]}
     assert ends <= set(seen), 'every extra conv declares its gradients final'
 

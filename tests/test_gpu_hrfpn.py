@@ -25,6 +25,7 @@ from oracle import cpr_oracle as O
 from oracle import p2p_options_oracle as PO
 from pointtinybenchmark_amd import synthetic
 from tests import hrfpn_ref as HR
+from tests.ready_point_check import checked
 from tests.test_gpu_fpn_extra import GRID4, _cells, _data, _NeckOnly, _record_assignments
 
 pytestmark = pytest.mark.gpu
@@ -488,18 +489,7 @@ def test_three_sgd_steps_lower_the_loss_and_ready_points_cover_the_neck(head):
     with torch.no_grad():
         ref = m.forward_train(**data)
         ref_total = sum(float(v) for k, vs in ref.items() if 'loss' in k for v in (vs if isinstance(vs, (list, tuple)) else [vs]))
-    seen = []
-
-    class Checked(_trainer(head)):
-        check = True
-
-        def _done(self, p):
-            end = self.offset[id(p)][1]
-            if self.check:
-                torch.cuda.synchronize()
-                assert not bool(torch.isnan(self.flat_g[:end]).any()), 'gradient prefix [0, %d) declared final unwritten' % end
-                seen.append(end)
-            super()._done(p)
+    Checked, seen = checked(_trainer(head))
     tr = Checked(m, lr=2e-4, momentum=0.9, weight_decay=1e-4, max_norm=35.0)
     tr.flat_g.fill_(float('nan'))
     convs = [m.neck.reduction_conv.conv] + [cm.conv for cm in m.neck.fpn_convs]

@@ -18,6 +18,7 @@ from oracle import cpr_oracle as O
 from oracle import p2p_options_oracle as PO
 from oracle.gen_golden import grad_sample_index
 from pointtinybenchmark_amd import synthetic
+from tests.ready_point_check import run_checked_backward
 
 pytestmark = pytest.mark.gpu
 
@@ -358,21 +359,8 @@ def test_multilevel_bucket_ready_points_only_cover_finished_gradients():
     written (the buffer is poisoned with NaN first), and the points sweep the buffer front to back."""
     from pointtinybenchmark_amd import training
     m, _ = build_ml_locator()
-    seen = []
-
-    class Checked(training.P2PTrainer):
-        def _done(self, p):
-            end = self.offset[id(p)][1]
-            torch.cuda.synchronize()
-            assert not bool(torch.isnan(self.flat_g[:end]).any()), 'gradient prefix [0, %d) declared final unwritten' % end
-            seen.append(end)
-    tr = Checked(m)
-    tr.flat_g.fill_(float('nan'))
     _, data = _data(seed=8)
-    tr.forward_backward(**data)
-    torch.cuda.synchronize()
-    assert not bool(torch.isnan(tr.flat_g).any())
-    assert seen and max(seen) == tr.flat_g.numel() and seen == sorted(seen)
+    tr, seen = run_checked_backward(training.P2PTrainer, m, data)
 
 
 def _worst_rel(tr, ga, gb, gmax):

@@ -233,15 +233,16 @@ def test_a_users_slice_with_nan_behind_it_takes_the_copying_route():
 ARCH = 'regnetx_1.6gf'
 
 
-def _locator(head, seed=3):
+def _locator(head, seed=3, arch=ARCH):
     import pointtinybenchmark_amd as P
     from bench import model_cfg, p2p_model_cfg
+    from pointtinybenchmark_amd.backbones.regnet import RegNet, stage_layout
     cfg = model_cfg(50, 1) if head == 'cpr' else p2p_model_cfg(50, 1)
-    cfg['backbone'] = dict(type='RegNet', arch=ARCH, out_indices=(0, 1, 2, 3), frozen_stages=-1, norm_cfg=dict(type='BN', requires_grad=True),
+    cfg['backbone'] = dict(type='RegNet', arch=arch, out_indices=(0, 1, 2, 3), frozen_stages=-1, norm_cfg=dict(type='BN', requires_grad=True),
                            norm_eval=True, style='pytorch')
-    cfg['neck'] = dict(cfg['neck'], in_channels=[72, 168, 408, 912])
+    cfg['neck'] = dict(cfg['neck'], in_channels=stage_layout(RegNet.arch_settings[arch])[0])      # ([72, 168, 408, 912] for regnetx_1.6gf)
     m = P.build_detector(cfg).cuda()
-    m.load_state_dict(synthetic.locator_state_dict(num_classes=1, head=head, seed=seed, head_std=0.3, arch=ARCH), strict=True)
+    m.load_state_dict(synthetic.locator_state_dict(num_classes=1, head=head, seed=seed, head_std=0.3, arch=arch), strict=True)
     m.train()
     return m
 

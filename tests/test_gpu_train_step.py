@@ -11,6 +11,7 @@ import torch
 from oracle import cpr_oracle as O
 from oracle.gen_golden import CPR_CASES
 from pointtinybenchmark_amd import synthetic
+from tests.ready_point_check import run_checked_backward
 from tests.test_gpu_cpr_parity import build_hip_locator, to_cuda
 
 pytestmark = pytest.mark.gpu
@@ -424,25 +425,10 @@ def test_bucket_ready_points_only_cover_finished_gradients(kind):
         m.load_state_dict(synthetic.locator_state_dict(18, 1, 0, 'p2p', 3, head_std=0.05), strict=True)
         m.train()
         base = training.P2PTrainer
-    seen = []
-
-    class Checked(base):
-        def _done(self, p):
-            end = self.offset[id(p)][1]
-            torch.cuda.synchronize()          # what wait_stream(side) + stream order give the collective
-            bad = torch.isnan(self.flat_g[:end])
-            assert not bool(bad.any()), 'gradient prefix [0, %d) declared final with %d unwritten entries (first at %d)' % (
-                end, int(bad.sum()), int(bad.nonzero()[0]))
-            seen.append(end)
-    tr = Checked(m)
-    tr.flat_g.fill_(float('nan'))
     C = 1 if kind == 'p2p' else cfg['num_classes']
     batch = synthetic.synthetic_batch(2, 128, 160, 6, C, seed=8)
     cb = to_cuda(batch)
-    tr.forward_backward(cb['img'], cb['img_metas'], cb['gt_bboxes'], cb['gt_labels'])
-    torch.cuda.synchronize()
-    assert not bool(torch.isnan(tr.flat_g).any()), 'some trainable parameter never received a gradient'
-    assert seen and max(seen) == tr.flat_g.numel() and seen == sorted(seen), 'ready points must sweep the buffer front to back'
+    run_checked_backward(base, m, dict(img=cb['img'], img_metas=cb['img_metas'], gt_bboxes=cb['gt_bboxes'], gt_labels=cb['gt_labels']))
 
 
 def test_rccl_bucket_path_single_rank():

@@ -354,10 +354,9 @@ def test_backward_order_lists_every_parameter_once():
     from types import SimpleNamespace
     from pointtinybenchmark_amd.training import CprTrainer
     bb = _build(HR.CASES['w32_tiny']['extra'])
-    head = SimpleNamespace(cls_out=SimpleNamespace(weight=None, bias=None), ins_out=SimpleNamespace(weight=None, bias=None), cls_convs=[])
     neck = SimpleNamespace(lateral_convs=[], fpn_convs=[], num_outs=0)
-    tr = SimpleNamespace(model=SimpleNamespace(bbox_head=head, neck=neck, backbone=bb), _head_param_order=CprTrainer._head_param_order,
-                         _fpn_param_order=CprTrainer._fpn_param_order)
+    tr = SimpleNamespace(model=SimpleNamespace(bbox_head=None, neck=neck, backbone=bb), _head_units=lambda head: [],
+                         _neck_units=CprTrainer._neck_units, _backbone_units=CprTrainer._backbone_units)
     order = CprTrainer._backward_order(tr)
     assert len(order) == len(list(bb.parameters())) and {id(p) for p in order} == {id(p) for p in bb.parameters()}
     names = {id(p): k for k, p in bb.named_parameters()}
