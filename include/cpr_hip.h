@@ -927,6 +927,27 @@ int cpr_preprocess_jobs_u8(const void* jobs_dev, int n_jobs, const float* mean3,
 int cpr_scale_clip_flip_boxes(float* boxes, const int* img_of, const int* flip, const int* img_hw, const float* scale4, int n,
                               int clip, void* stream);
 
+/* ---- Darknet-53 (T/mmdet/models/backbones/darknet.py; csrc/darknet.hip), fp32 NHWC maps, 16 bytes of channels per lane.  The dense
+ * conv epilogues know ReLU only: a Darknet ConvModule (conv -> BN -> LeakyReLU, darknet.py:45-47, :121, :205-208) runs its conv in the
+ * raw folded form and these passes apply the activation.
+ * cpr_leaky_fwd: out = (z > 0 ? z : z * slope) (+ res) over n floats (n % 4 == 0) -- F.leaky_relu bit for bit (the product is rounded,
+ * then the sum: no FMA), NaN propagates, -0.0 stays -0.0.  res (optional): the ResBlock's ``out + residual`` (darknet.py:53).  out may
+ * be z. */
+int cpr_leaky_fwd(const float* z, const float* res, float* out, long long n, float slope, void* stream);
+/* The LeakyReLU twin of cpr_relu_bwd_colsum / cpr_relu6_bwd_colsum: s = dy (+ add, optional, one rounding), g = y > 0 ? s : s * slope
+ * (torch's leaky_relu_backward: the slope at y == 0) and colsum (C) = the per-channel sums of g; (M, C) row-major, C % 4 == 0.  y is the
+ * pre-activation or the activated map (0 <= slope: the predicate is the same).  g_out may be NULL (the sums alone).  Per-workgroup
+ * partials in ws (cpr_leaky_bwd_colsum_ws(M, C) floats) are added in ascending order by a second kernel -- no atomics. */
+int cpr_leaky_bwd_colsum_ws(long long M, int C);
+int cpr_leaky_bwd_colsum(const float* dy, const float* add, const float* y, float* g_out, float* colsum, float* ws, long long M, int C,
+                         float slope, void* stream);
+/* Weight gradient of Darknet's first conv (darknet.py:121: 3x3 / stride 1 / pad 1, 3 -> 32), the stride-1 sibling of
+ * cpr_stem3x3s2_wgrad: gw (32, 3, 3, 3) = sum over n, h, w of dy[n, h, w, o] * in[n, h + kh - 1, w + kw - 1, c], zero outside the image;
+ * dy (N, H, W, 32); in: layout 0 (N, H, W, 4) fp32 (4th channel ignored), layout 1 (N, 3, H, W) planes.  Pixel slices
+ * (ws: cpr_stem3x3s1_wgrad_workspace(N, H, W) floats) are added in ascending order by a second kernel -- no atomics. */
+int cpr_stem3x3s1_wgrad_workspace(int N, int H, int W);
+int cpr_stem3x3s1_wgrad(const float* dy, const float* in, float* gw, float* ws, int N, int H, int W, int layout, void* stream);
+
 /* ---- measurement build only (-DCPR_BENCH_HOOKS; python -m pointtinybenchmark_amd.build --bench-hooks) ------------------
  * Process-global, not thread-safe switches used by the scripts under tools/ to A/B the conv kernels.  NOT part of the
  * product library. */

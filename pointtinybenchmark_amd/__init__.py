@@ -1,7 +1,7 @@
 """MI355X-native CPR / P2PNet point-localization hot path.
 
 Importing the package registers the drop-in classes under the reference's registry names
-(BasicLocator, ResNet, HRNet, FPN, PAFPN, BFP, HRFPN, CPRHead, P2PHead, MILLoss, HungarianAssignerV2, PointAssigner, PseudoSampler,
+(BasicLocator, ResNet, HRNet, Darknet, FPN, PAFPN, BFP, HRFPN, CPRHead, P2PHead, MILLoss, HungarianAssignerV2, PointAssigner, PseudoSampler,
 FocalLossCost, DisCostV2)."""
 import os as _os
 

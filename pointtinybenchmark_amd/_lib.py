@@ -167,6 +167,11 @@ SIGNATURES = {
     'cpr_relu6_bwd_colsum_ws': [_l, _i],
     'cpr_relu6_bwd_colsum': [_p] * 6 + [_l, _i, _p],
     'cpr_clamp6': [_p, _l, _p],
+    'cpr_leaky_fwd': [_p, _p, _p, _l, _f, _p],
+    'cpr_leaky_bwd_colsum_ws': [_l, _i],
+    'cpr_leaky_bwd_colsum': [_p] * 6 + [_l, _i, _f, _p],
+    'cpr_stem3x3s1_wgrad_workspace': [_i, _i, _i],
+    'cpr_stem3x3s1_wgrad': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     'cpr_spin': [ctypes.c_longlong, _p],
     'cpr_bn_fold': [_p, _p, _p, _p, _f, _p, _p, _p, _i, _p],
     'cpr_bn_train_ws': [_l, _i],

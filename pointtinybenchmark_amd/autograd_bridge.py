@@ -63,8 +63,9 @@ class Bridge:
         self.engine = engine
         bb, neck, bfp = model.backbone, _inner_neck(model.neck), _bfp_of(model.neck)
         self._maps = {}         # bf16 compute mode: data_ptr of an fp32 carrier -> the bf16 map it stands for (see carrier())
+        self.darknet = bool(getattr(bb, 'darknet', False))      # one Function as well (_DarknetFn): its record is one, stem included
         self.hrnet = bool(getattr(bb, 'hrnet', False))
-        if self.hrnet:      # a DAG of branches: one Function from the image to the branch outputs (_HRNetFn), every parameter its input
+        if self.hrnet or self.darknet:      # HRNet, a DAG of branches: one Function from the image to the branch outputs (_HRNetFn), every parameter its input
             self.stem_params, self.stage_params = [], []
             self.backbone_params = [p for p in bb.parameters() if p.requires_grad]
         else:
@@ -145,12 +146,19 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
     hrnet = getattr(bb, 'hrnet', False)                # HRNet: no out_indices, no frozen_stages -- any (conv, BN) pair may be frozen, as a whole
     if hrnet and bb.freeze_reason() is not None:
         return bb.freeze_reason()
+    if getattr(bb, 'darknet', False):                  # Darknet: out_indices picks among conv1, conv_res_block1 .. 5; pairs as HRNet's
+        return bb.freeze_reason() or _head_reason(model, head, n_outs, gt_bboxes, gt_labels)
     if not (sparse or hrnet) and tuple(bb.out_indices) != tuple(range(len(bb.res_layers))):
         return 'out_indices must name every stage'
     for i, name in enumerate(() if hrnet else bb.res_layers):
         first = [next(blk.parameters()) for blk in bb.stage_blocks(i)] if sparse else [blk.conv1.weight for blk in getattr(bb, name)]
         if len({p.requires_grad for p in first}) > 1:
             return 'stage %s is partly frozen' % name
+    return _head_reason(model, head, n_outs, gt_bboxes, gt_labels)
+
+
+def _head_reason(model, head, n_outs, gt_bboxes, gt_labels):
+    bb = model.backbone
     kind = type(head).__name__
     if kind == 'CPRHead':
         R = 1
@@ -230,6 +238,41 @@ class _HRNetFn(torch.autograd.Function):
         tape = []
         outs = bb.run(img, tape)
         tape[0]['stages'][-1]['modules'][-1]['out'] = [o.detach() for o in outs]      # (no output reachable from its own ctx)
+        ctx.bridge, ctx.tape, ctx.params = bridge, tape, params
+        ctx.set_materialize_grads(False)      # an output nobody differentiates hands None down, as in the native trainer
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *douts):
+        eng, tape = ctx.bridge.engine, ctx.tape
+        assert tape is not None, _CONSUMED
+        d_stage = {k: d.contiguous() for k, d in enumerate(douts) if d is not None}
+        eng._backward_backbone(ctx.bridge.model.backbone, tape, d_stage)
+        grads = eng.collect(ctx.params)
+        ctx.tape = None
+        return (None, None) + grads
+
+
+class _DarknetFn(torch.autograd.Function):
+    """A Darknet backbone (backbones/darknet.py), conv1 included: the image (no gradient) -> the NHWC outputs of its ``out_indices``
+    stages; every trainable backbone parameter as an input.  Its recorded forward is one record, walked by
+    BackwardEngine._backward_backbone as the native trainer walks it, so both drivers run the same kernels in the same order."""
+
+    @staticmethod
+    def forward(ctx, bridge, img, *params):
+        bb = bridge.model.backbone
+        tape = []
+        outs = bb.run(img, tape)
+        # (no output reachable from its own ctx: a stage output is the next stage's recorded input, conv1's the first stage's)
+        own = {id(o): o.detach() for o in outs}
+        rec = tape[0]
+        rec['a0'] = own.get(id(rec['a0']), rec['a0'])
+        for srec in rec['stages']:
+            for r in [srec] + srec['blocks']:
+                for k, v in r.items():
+                    if torch.is_tensor(v):
+                        r[k] = own.get(id(v), v)
         ctx.bridge, ctx.tape, ctx.params = bridge, tape, params
         ctx.set_materialize_grads(False)      # an output nobody differentiates hands None down, as in the native trainer
         return tuple(outs)
@@ -346,9 +389,9 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
     eng._sink.clear()
     bridge._maps.clear()
     bb, neck = model.backbone, _inner_neck(model.neck)
-    if bridge.hrnet:
+    if bridge.hrnet or bridge.darknet:
         if bridge.backbone_params:
-            feats = list(_HRNetFn.apply(bridge, img.detach(), *bridge.backbone_params))
+            feats = list((_HRNetFn if bridge.hrnet else _DarknetFn).apply(bridge, img.detach(), *bridge.backbone_params))
         else:
             with torch.no_grad():
                 feats = bb.run(img)

@@ -2739,3 +2739,47 @@ def clamp6(x):
     """x = min(x, 6) in place: a ReLU(v) map whose consumers do not clamp on load (a stage output, conv2's output)."""
     _lib.call('cpr_clamp6', _ptr(_check(x)), x.numel(), _stream())
     return x
+
+
+# ---- Darknet (csrc/darknet.hip): the LeakyReLU passes around the dense convs (whose epilogues know ReLU only) and the weight gradient
+# of the 3 -> 32 / stride 1 first conv.  fp32 NHWC maps; nothing here has a bf16 form.
+def leaky(z, slope, res=None, out=None):
+    """out = F.leaky_relu(z, slope) (+ res), bit for bit (the product is rounded, then the sum).  out None: in place, z is returned;
+    res: a map of z's shape (a ResBlock's shortcut)."""
+    if out is None:
+        out = z
+    assert _check(out).shape == _check(z).shape and (res is None or _check(res).shape == z.shape), (z.shape, out.shape)
+    _lib.call('cpr_leaky_fwd', _ptr(z), _ptr(res), _ptr(out), z.numel(), float(slope), _stream())
+    return out
+
+
+def leaky_bwd_colsum(dy, y, slope, add=None, want_g=True, out=None):
+    """g = (y > 0 ? s : s * slope) with s = dy (+ add) and the per-channel column sums of g -> (g | None, colsum (C)): the LeakyReLU
+    twin of relu_bwd_colsum / relu6_bwd_colsum.  y: the pre-activation or the activated map (the predicate is the same).  out: g is
+    written there, every element."""
+    C = dy.shape[-1]
+    M = dy.numel() // C
+    for v in (y, add):
+        assert v is None or (_check(v).numel() == dy.numel()), (v.shape, dy.shape)
+    g = None
+    if want_g:
+        g = out if out is not None else torch.empty_like(dy)
+        assert _check(g).shape == dy.shape, (g.shape, dy.shape)
+    ws = torch.empty((_lib.call('cpr_leaky_bwd_colsum_ws', M, C, positive=True),), device=dy.device, dtype=torch.float32)
+    cs = torch.empty((C,), device=dy.device, dtype=torch.float32)
+    _lib.call('cpr_leaky_bwd_colsum', _ptr(_check(dy)), _ptr(add), _ptr(y), _ptr(g), _ptr(cs), _ptr(ws), M, C, float(slope), _stream())
+    return g, cs
+
+
+def stem3x3s1_wgrad(dy, x, planar=None, out=None):
+    """Weight gradient of Darknet's first conv (3x3 / stride 1 / padding 1, 3 -> 32): dy (N,H,W,32) fp32 and the image as the forward
+    read it (NHWC4, or the (N,3,H,W) planes) -> (32,3,3,3) fp32 (written into ``out`` when given); the split over pixels is added up
+    in a fixed order (csrc/darknet.hip)."""
+    N, H, W, layout = _stem_input(_check(x), planar)
+    assert _check(dy).shape == (N, H, W, 32), (tuple(dy.shape), tuple(x.shape))
+    if out is None:
+        out = torch.empty((32, 3, 3, 3), device=x.device, dtype=torch.float32)
+    assert _check(out).shape == (32, 3, 3, 3), tuple(out.shape)
+    ws = torch.empty((_lib.call('cpr_stem3x3s1_wgrad_workspace', N, H, W, positive=True),), device=x.device, dtype=torch.float32)
+    _lib.call('cpr_stem3x3s1_wgrad', _ptr(dy), _ptr(x), _ptr(out), _ptr(ws), N, H, W, layout, _stream())
+    return out

@@ -374,6 +374,33 @@ def hrnet_state_dict(extra, seed=0, prefix='', in_channels=3):
     return sd
 
 
+def darknet_layout(depth=53):
+    """[(ConvModule key, conv shape)] of the reference's Darknet (darknet.py:121-130, :204-212) in its state-dict order: conv1, then per
+    conv_res_block{i} its stride-2 ``conv`` and res{j}.conv1 / res{j}.conv2; each holds ``.conv.weight`` and ``.bn.*``.  ``depth`` is
+    looked up in the drop-in class's ``arch_settings``."""
+    from .backbones.darknet import Darknet
+    layers, channels = Darknet.arch_settings[depth]
+    out = [('conv1', (32, 3, 3, 3))]
+    for i, (n, (cin, cout)) in enumerate(zip(layers, channels)):
+        name = 'conv_res_block%d' % (i + 1)
+        out.append((name + '.conv', (cout, cin, 3, 3)))
+        for j in range(n):
+            out.append(('%s.res%d.conv1' % (name, j), (cout // 2, cout, 1, 1)))
+            out.append(('%s.res%d.conv2' % (name, j), (cout, cout // 2, 3, 3)))
+    return out
+
+
+def darknet_state_dict(depth=53, seed=0, prefix=''):
+    """A state dict of the reference's Darknet layout for ``depth`` (darknet_layout): Kaiming-scaled conv weights and BatchNorms with
+    non-trivial gammas, betas and running statistics (_bn)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for key, shape in darknet_layout(depth):
+        sd[prefix + key + '.conv.weight'] = _kaiming(shape, g)
+        _bn(sd, prefix + key + '.bn', shape[0], g)
+    return sd
+
+
 def cpr_head_state_dict(num_classes=1, in_channels=256, feat_channels=256, stacked_convs=4, seed=2,
                         prefix='bbox_head.', std=0.01, num_cls_fcs=0, fc_out_channels=1024, binary_ins=False,
                         ins_tower=False, out_bg_cls=False):

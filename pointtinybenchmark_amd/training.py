@@ -335,7 +335,7 @@ class BackwardEngine:
                                           'no slice convolution' % bb.scales)
         if getattr(bb, 'fp32_only', None) and getattr(bb, 'compute_dtype', torch.float32) != torch.float32:
             raise NotImplementedError(bb.fp32_only)      # (a RegNet backbone: backbones/regnet.py, naming ``arch``)
-        if getattr(bb, 'hrnet', False) and bb.freeze_reason() is not None:      # (no frozen_stages: any (conv, BN) pair may be frozen, as a whole)
+        if (getattr(bb, 'hrnet', False) or getattr(bb, 'darknet', False)) and bb.freeze_reason() is not None:      # (any (conv, BN) pair may be frozen, as a whole)
             raise NotImplementedError(bb.freeze_reason())
         dev = next(model.parameters()).device
         self._mixed, self._wide = False, {}     # set per step (bf16 compute mode = mixed precision)
@@ -1053,6 +1053,8 @@ class BackwardEngine:
         bb = self.model.backbone
         if getattr(bb, 'hrnet', False):      # every branch output of an HRNet is reached from every parameter below the last exchange
             return any(p.requires_grad for p in bb.parameters())
+        if getattr(bb, 'darknet', False):    # output k is stage sorted(out_indices)[k] of conv1, conv_res_block1 .. 5: it and everything below it
+            return any(p.requires_grad for name in bb.cr_blocks[:sorted(set(bb.out_indices))[stage] + 1] for p in getattr(bb, name).parameters())
         if getattr(bb, 'sparse_outputs', False):
             stage = sorted(set(bb.out_indices))[stage]
         return any(p.requires_grad for p in getattr(bb, bb.res_layers[stage]).parameters())
@@ -1063,6 +1065,8 @@ class BackwardEngine:
         where it trains (a stem with a reason does not; a trainable non-standard one has no rule and trips the constructor's check)."""
         if getattr(bb, 'hrnet', False):
             return cls._hrnet_units(bb)
+        if getattr(bb, 'darknet', False):
+            return cls._darknet_units(bb)
         stages = [bb.stage_blocks(i) if getattr(bb, 'sparse_outputs', False) else list(getattr(bb, name)) for i, name in enumerate(bb.res_layers)]
         units = [u for blocks in reversed(stages) for blk in reversed(blocks) for u in cls._BLOCK_RULES[blk.kind][1](blk)]
         return units + (cls._stem_units(bb) if bb.stem_train_reason() is None else [])
@@ -1070,6 +1074,8 @@ class BackwardEngine:
     def _backward_backbone(self, bb, tape, d_stage):
         if getattr(bb, 'hrnet', False):      # a DAG of parallel branches (backbones/hrnet.py), not a chain of stages
             return self._backward_hrnet(bb, tape, d_stage)
+        if getattr(bb, 'darknet', False):    # one record of the whole chain (backbones/darknet.py)
+            return self._backward_darknet(bb, tape, d_stage)
         c = bb._cache
         if getattr(bb, 'sparse_outputs', False):      # MobileNetV2: output k is stage out_indices[k] of layer1 .. layer7, conv2
             stages = sorted(set(bb.out_indices))
@@ -1660,6 +1666,77 @@ class BackwardEngine:
         dx = self._padded_conv_bn_backward(cache, ec.conv, ec.bn, g1, cs1, x, need_dx, add=dout if blk.with_res_shortcut else None)
         self._done_last(*units)
         return dx
+
+    # ------------------------------------------------------------------ Darknet (backbones/darknet.py; fp32, eval-mode BatchNorm)
+    @staticmethod
+    def _darknet_units(bb):      # stages last first -- per stage its ResBlocks last first (conv2, conv1), then its stride-2 conv --, conv1 of the net last
+        units = []
+        for i in range(bb.last_stage(), 0, -1):
+            conv, blocks = bb.stage_parts(i)
+            for blk in reversed(blocks):
+                units += [_conv_bn(blk.conv2.conv, blk.conv2.bn), _conv_bn(blk.conv1.conv, blk.conv1.bn)]
+            units.append(_conv_bn(conv.conv, conv.bn))
+        return units + [_conv_bn(bb.conv1.conv, bb.conv1.bn)]
+
+    def _backward_darknet(self, bb, tape, d_stage):
+        """The Darknet walk.  tape: [the record of Darknet.run]; d_stage: {k: gradient of output k (NHWC)}, output k being stage
+        sorted(out_indices)[k].  Every layer is conv -> folded eval-BN -> LeakyReLU: g, column sums = ops.leaky_bwd_colsum(d_act, map)
+        -- the map is the activated one the forward kept in place, or a ResBlock's recorded z2 (its output carries the shortcut and
+        has lost the sign) --, then the folded rule with no mask (_conv_bn_backward).  A ResBlock's shortcut gradient (dout itself)
+        joins conv1's data gradient through its ``add`` operand; a stage output that is also a backbone output adds its lateral
+        gradient on entry.  conv1 of the net: the weight gradient of csrc/darknet.hip over the NHWC4 image.  A frozen parameter gets
+        no gradient and no launch; the walk ends where nothing below trains (frozen_stages=k freezes cr_blocks[:k])."""
+        if bb.freeze_reason() is not None:      # (requires_grad may have changed since the engine was built)
+            raise NotImplementedError(bb.freeze_reason())
+        rec, = [r for r in tape if r.get('darknet')]
+        c, slope = bb._cache, bb.negative_slope
+        stages = sorted(set(bb.out_indices))
+        d_out = {stages[k]: g for k, g in d_stage.items() if g is not None}
+        below = [False]      # below[i]: something in cr_blocks[:i] trains
+        for name in bb.cr_blocks:
+            below.append(below[-1] or self._trains(getattr(bb, name)))
+        dx = None
+        for i in range(bb.last_stage(), 0, -1):
+            lat = d_out.get(i)
+            if lat is not None:
+                dx = lat if dx is None else ops.axpby(dx, lat, 1.0, 1.0)
+            if not below[i + 1]:      # nothing in this stage or below it trains
+                self._wide = {}
+                return
+            assert dx is not None, 'no gradient reaches Darknet stage %d' % i
+            conv, blocks = bb.stage_parts(i)
+            srec = rec['stages'][i - 1]
+            for k in range(len(blocks) - 1, -1, -1):
+                blk, r = blocks[k], srec['blocks'][k]
+                if not (below[i] or self._trains(conv, *blocks[:k + 1])):
+                    break
+                g2, cs2 = ops.leaky_bwd_colsum(dx, r['z2'], slope)
+                d1 = self._conv_bn_backward(c, blk.conv2.conv, blk.conv2.bn, g2, cs2, r['a1'], True)
+                self._done_last(_conv_bn(blk.conv2.conv, blk.conv2.bn))
+                g1, cs1 = ops.leaky_bwd_colsum(d1, r['a1'], slope)
+                del d1
+                need = below[i] or self._trains(conv, *blocks[:k])
+                dx = self._conv_bn_backward(c, blk.conv1.conv, blk.conv1.bn, g1, cs1, r['x'], need, add=dx)
+                self._done_last(_conv_bn(blk.conv1.conv, blk.conv1.bn))
+                if not need:
+                    dx = None
+                    break
+            if dx is None or not (below[i] or self._trains(conv)):
+                self._wide = {}
+                return
+            g, cs = ops.leaky_bwd_colsum(dx, srec['a'], slope)
+            dx = self._conv_bn_backward(c, conv.conv, conv.bn, g, cs, srec['x'], below[i])
+            self._done_last(_conv_bn(conv.conv, conv.bn))
+        self._wide = {}
+        lat = d_out.get(0)
+        if lat is not None:
+            dx = lat if dx is None else ops.axpby(dx, lat, 1.0, 1.0)
+        if dx is None or not below[1]:
+            return
+        m, x4 = bb.conv1, rec['x4']
+        g, cs = ops.leaky_bwd_colsum(dx, rec['a0'], slope)
+        self._folded_param_grads(c, m.conv, m.bn, cs, lambda gw: ops.stem3x3s1_wgrad(g, x4, planar=False, out=gw), g, x4, stem=True)
+        self._done_last(_conv_bn(m.conv, m.bn))
 
     # ------------------------------------------------------------------ training-mode BatchNorm (ResNet norm_eval=False)
     def _conv_bn_backward_batch_stats(self, cache, conv, bn, rec, key, g, mask, x, need_dx, add=None):
