@@ -948,6 +948,19 @@ int cpr_leaky_bwd_colsum(const float* dy, const float* add, const float* y, floa
 int cpr_stem3x3s1_wgrad_workspace(int N, int H, int W);
 int cpr_stem3x3s1_wgrad(const float* dy, const float* in, float* gw, float* ws, int N, int H, int W, int layout, void* stream);
 
+/* ---- CTResNetNeck (T/mmdet/models/necks/ct_resnet_neck.py; csrc/deconv.hip): the transposed convolution 4x4 / stride 2 / padding 1
+ * without bias, fp32 NHWC, on the fp32 matrix pipe.
+ * cpr_pack_weights_deconv: the nn.ConvTranspose2d weight w (Cin, Cout, 4, 4) -> out, 16 * Cin * Cout floats: one [Cout][4 * Cin] GEMM image
+ * per output-parity class, out[2a + b][co][(2t + u) * Cin + ci] = w[ci][co][1 - a + 2t][1 - b + 2u] (K ordered tap row, tap column, cin).
+ * cpr_deconv4x4s2_fwd: out (N, 2H, 2W, Cout), out[n, 2i + a, 2j + b, co] = epi(sum_{t, u, ci} in[n, i + a - t, j + b - u, ci] * w[ci][co][..])
+ * with taps outside the map contributing zero; one launch for the four classes, the interleaved map written directly (no scatter pass, no
+ * atomics; a fixed k-ordered fp32 chain per element, independent of N and of the tile).  epi(v) = v * scale[co] + bias[co], then ReLU with
+ * flags = CPR_CONV_RELU; scale / bias may each be NULL (both NULL: the raw sums).  variant_out (optional): BM * 10^6 + BN * 10^3 + 1 of the
+ * tile instance that ran.  Cin % 32 == 0 and Cout % 32 == 0, else CPR_ERR_ARG before any launch. */
+int cpr_pack_weights_deconv(const float* w, float* out, int Cin, int Cout, void* stream);
+int cpr_deconv4x4s2_fwd(const float* in, const float* wgt, float* out, const float* scale, const float* bias, int N, int H, int W, int Cin,
+                        int Cout, int flags, int* variant_out, void* stream);
+
 /* ---- measurement build only (-DCPR_BENCH_HOOKS; python -m pointtinybenchmark_amd.build --bench-hooks) ------------------
  * Process-global, not thread-safe switches used by the scripts under tools/ to A/B the conv kernels.  NOT part of the
  * product library. */

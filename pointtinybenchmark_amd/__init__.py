@@ -1,7 +1,7 @@
 """MI355X-native CPR / P2PNet point-localization hot path.
 
 Importing the package registers the drop-in classes under the reference's registry names
-(BasicLocator, ResNet, HRNet, Darknet, FPN, PAFPN, BFP, HRFPN, CPRHead, P2PHead, MILLoss, HungarianAssignerV2, PointAssigner, PseudoSampler,
+(BasicLocator, ResNet, HRNet, Darknet, FPN, PAFPN, BFP, HRFPN, CTResNetNeck, CPRHead, P2PHead, MILLoss, HungarianAssignerV2, PointAssigner, PseudoSampler,
 FocalLossCost, DisCostV2)."""
 import os as _os
 
@@ -37,7 +37,7 @@ from .core import (AssignResult, BBoxL1Cost, ClassificationCost, ClassificationC
 from .dense_heads import CPRHead, P2PHead  # noqa: F401,E402
 from .detectors import BasicLocator  # noqa: F401,E402
 from .losses import MILLoss  # noqa: F401,E402
-from .necks import BFP, FPN, HRFPN, PAFPN, NeckSequence  # noqa: F401,E402
+from .necks import BFP, FPN, HRFPN, PAFPN, CTResNetNeck, NeckSequence  # noqa: F401,E402
 from .registry import (BACKBONES, BBOX_ASSIGNERS, BBOX_SAMPLERS, DETECTORS, HEADS, LOSSES, MATCH_COST, NECKS,  # noqa
                        build_assigner, build_backbone, build_detector, build_head, build_loss, build_match_cost,
                        build_neck, build_sampler)

@@ -172,6 +172,8 @@ SIGNATURES = {
     'cpr_leaky_bwd_colsum': [_p] * 6 + [_l, _i, _f, _p],
     'cpr_stem3x3s1_wgrad_workspace': [_i, _i, _i],
     'cpr_stem3x3s1_wgrad': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'cpr_pack_weights_deconv': [_p, _p, _i, _i, _p],
+    'cpr_deconv4x4s2_fwd': [_p] * 5 + [_i] * 6 + [_p, _p],
     'cpr_spin': [ctypes.c_longlong, _p],
     'cpr_bn_fold': [_p, _p, _p, _p, _f, _p, _p, _p, _i, _p],
     'cpr_bn_train_ws': [_l, _i],

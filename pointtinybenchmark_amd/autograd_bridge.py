@@ -15,6 +15,8 @@ chain have none: a raw map travels with a pending affine):
              (add_extra_convs='on_input': the last stage's output is one more input of it, d(stage output) comes back from it too)
     An HRFPN neck (necks/hrfpn.py) has one such boundary, its reduced map: _LateralsFn runs the per-level 1x1 convs and the fuse
     (d(reduced map) behind it), _HeadLossFn the pools, the biased output convs and the head.
+    A CTResNetNeck (necks/ct_resnet_neck.py) too, its output map: _LateralsFn runs the whole neck on the last stage's output (in
+    train() mode: batch statistics; an eval() neck is reported by unsupported_reason), _HeadLossFn the head alone.
 
 Every Function takes its trainable parameters as explicit inputs, so they sit in the autograd graph as leaves: gradient
 accumulators fire per Function -- the head's 9.4 MB of gradients (63 % of the backward's time) are final and on the wire while
@@ -35,7 +37,7 @@ import warnings
 import torch
 from torch.autograd.function import once_differentiable
 
-from .training import _BFP_UNDER_CPR, BackwardEngine, P2PBackwardEngine, _bfp_of, _inner_neck, _is_hrfpn
+from .training import _BFP_UNDER_CPR, BackwardEngine, P2PBackwardEngine, _bfp_of, _inner_neck, _is_ctneck, _is_hrfpn
 
 
 class _GtPack:
@@ -73,11 +75,13 @@ class Bridge:
                                 for p in m.parameters() if p.requires_grad]
             self.stage_params = [[p for p in getattr(bb, name).parameters() if p.requires_grad] for name in bb.res_layers]
         # (an HRFPN's reduction conv -- its per-level 1x1 convs -- plays the laterals' part: the same Function)
-        self.lateral_params = [p for cm in ([neck.reduction_conv] if _is_hrfpn(neck) else neck.lateral_convs) for p in cm.parameters()
-                               if p.requires_grad]
+        # (a CTResNetNeck as a whole too: its output map is the boundary, nothing of it sits behind)
+        ct = _is_ctneck(neck)
+        self.lateral_params = [p for cm in ([neck.reduction_conv] if _is_hrfpn(neck) else [neck] if ct else neck.lateral_convs)
+                               for p in cm.parameters() if p.requires_grad]
         # (a PAFPN's bottom-up modules sit between the output convs and the head: the same Function)
         # (so does the refine layer of a BFP behind the neck)
-        neck_out = list(neck.fpn_convs) + list(getattr(neck, 'downsample_convs', ())) + list(getattr(neck, 'pafpn_convs', ()))
+        neck_out = [] if ct else list(neck.fpn_convs) + list(getattr(neck, 'downsample_convs', ())) + list(getattr(neck, 'pafpn_convs', ()))
         if bfp is not None and bfp.refine_type is not None:
             neck_out.append(bfp.refine)
         self.head_params = [p for p in [q for cm in neck_out for q in cm.parameters()] + list(head.parameters())
@@ -115,9 +119,16 @@ def unsupported_reason(model, gt_bboxes=None, gt_labels=None):
         if type(head).__name__ == 'CPRHead':
             return _BFP_UNDER_CPR
         neck = _inner_neck(neck)
-    if neck is None or type(neck).__name__ not in ('FPN', 'PAFPN', 'HRFPN') or len(neck.fpn_convs) < 1:
+    if _is_ctneck(neck):
+        if bb.compute_dtype != torch.float32:
+            return neck.fp32_only
+        if not neck.training:
+            from .necks.ct_resnet_neck import EVAL_TAPE
+            return EVAL_TAPE
+        n_outs = 1
+    elif neck is None or type(neck).__name__ not in ('FPN', 'PAFPN', 'HRFPN') or len(neck.fpn_convs) < 1:
         return 'needs an FPN neck'
-    if _is_hrfpn(neck):
+    elif _is_hrfpn(neck):
         n_outs = neck.num_outs
         if n_outs != 1 and type(head).__name__ == 'CPRHead':
             return 'CPRHead takes one pyramid level (cpr_head.py:487); this HRFPN has %d output levels' % n_outs
@@ -419,8 +430,11 @@ def forward_train(model, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=
 def _neck_head_loss(model, bridge, feats, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_true_bboxes):
     """The part of forward_train behind the backbone: feats, its NHWC outputs -> the dict of losses."""
     eng, neck = bridge.engine, _inner_neck(model.neck)
-    assert len(feats) == len(neck.in_channels)
-    xs = feats if _is_hrfpn(neck) else feats[neck.start_level:neck.start_level + len(neck.lateral_convs)]
+    if _is_ctneck(neck):      # it reads the last backbone map alone
+        xs = feats[-1:]
+    else:
+        assert len(feats) == len(neck.in_channels)
+        xs = feats if _is_hrfpn(neck) else feats[neck.start_level:neck.start_level + len(neck.lateral_convs)]
     lat = _LateralsFn.apply(bridge, len(xs), *xs, *bridge.lateral_params)
     lats = tuple(lat) if isinstance(lat, (tuple, list)) else (lat,)
     if bridge.extra_on_input:

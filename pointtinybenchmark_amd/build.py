@@ -11,7 +11,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB = os.path.join(CSRC, 'libcprhip.so')
 SOURCES = ['conv_mfma.hip', 'conv1x1_stream.hip', 'conv_mfma_bf16.hip', 'conv_bf16_dma.hip', 'conv_bf16_pp.hip', 'stem_bf16.hip', 'stem_f32.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_bf16_tn.hip', 'conv_wgrad.hip', 'norm_pool.hip', 'cpr_points.hip', 'assign.hip',
            'postproc.hip', 'backward.hip', 'preprocess.hip', 'pack.hip', 'project.hip', 'conv_wino.hip', 'conv_wino32.hip', 'conv_wino_wgrad.hip', 'bn_train.hip',
-           'p2p_out_bf16.hip', 'optim.hip', 'stem_bwd.hip', 'fpn_extra.hip', 'stem_deep.hip', 'conv_group.hip', 'pafpn.hip', 'bfp.hip', 'res2net.hip', 'stem3x3_bwd.hip', 'splat.hip', 'mbv2.hip', 'hrfpn.hip', 'hrnet.hip', 'darknet.hip']
+           'p2p_out_bf16.hip', 'optim.hip', 'stem_bwd.hip', 'fpn_extra.hip', 'stem_deep.hip', 'conv_group.hip', 'pafpn.hip', 'bfp.hip', 'res2net.hip', 'stem3x3_bwd.hip', 'splat.hip', 'mbv2.hip', 'hrfpn.hip', 'hrnet.hip', 'darknet.hip', 'deconv.hip']
 HEADERS = ['common.h', 'conv_bf16_dma.h']
 # Kernels whose integer / mask / index outputs are held bit-exact against the reference's CPU arithmetic restate it
 # operation by operation.  hipcc's default -ffp-contract=fast fuses a*b+c into one fma EVEN ACROSS the __fmul_rn/__fadd_rn

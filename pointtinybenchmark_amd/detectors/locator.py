@@ -47,6 +47,8 @@ class BasicLocator(nn.Module):
                                       'slice convolution' % scales)
         if dt != torch.float32 and getattr(self.backbone, 'fp32_only', None):      # a RegNet backbone (backbones/regnet.py)
             raise NotImplementedError(self.backbone.fp32_only)
+        if dt != torch.float32 and getattr(self.neck, 'fp32_only', None):               # a CTResNetNeck (necks/ct_resnet_neck.py)
+            raise NotImplementedError(self.neck.fp32_only)
         self.backbone.compute_dtype = dt
         return self
 

@@ -2783,3 +2783,63 @@ def stem3x3s1_wgrad(dy, x, planar=None, out=None):
     ws = torch.empty((_lib.call('cpr_stem3x3s1_wgrad_workspace', N, H, W, positive=True),), device=x.device, dtype=torch.float32)
     _lib.call('cpr_stem3x3s1_wgrad', _ptr(dy), _ptr(x), _ptr(out), _ptr(ws), N, H, W, layout, _stream())
     return out
+
+
+# ---- CTResNetNeck (csrc/deconv.hip): the transposed convolution 4x4 / stride 2 / padding 1 without bias.  fp32 NHWC; no bf16 form.
+class DeconvPack:
+    """An nn.ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1, bias=False) weight (Cin, Cout, 4, 4) repacked for ``deconv4x4s2``: one
+    [Cout][4 * Cin] GEMM image per output-parity class (a, b), K ordered (tap row, tap column, cin) -- self.w (4, Cout, 4 * Cin) with
+    w[2a + b, co, (2t + u) * Cin + ci] = weight[ci, co, 1 - a + 2t, 1 - b + 2u]."""
+    ready = None
+
+    def __init__(self, weight):
+        Cin, Cout, KH, KW = weight.shape
+        assert (KH, KW) == (4, 4), 'the transposed-conv kernel is 4x4 / stride 2 / padding 1, got a %dx%d weight' % (KH, KW)
+        assert weight.is_cuda, 'the transposed-conv pack is built on the device'
+        self.Cin, self.Cout, self.dtype = Cin, Cout, torch.float32
+        src = weight.detach()
+        if src.dtype != torch.float32 or not src.is_contiguous():
+            src = src.float().contiguous()
+        self.w = torch.empty((4, Cout, 4 * Cin), device=weight.device, dtype=torch.float32)
+        _lib.call('cpr_pack_weights_deconv', _ptr(src), _ptr(self.w), Cin, Cout, _stream())
+        self.ready = record_ready()
+
+
+def deconv_pack_image(weight):
+    """The image ``DeconvPack`` holds, restated with torch on any device: (4, Cout, 4 * Cin) from the (Cin, Cout, 4, 4) weight (the host
+    tests and the device test of the pack kernel read it)."""
+    Cin, Cout = weight.shape[:2]
+    return torch.stack([torch.stack([weight[:, :, 1 - a + 2 * t, 1 - b + 2 * u].t() for t in range(2) for u in range(2)], 1).reshape(Cout, 4 * Cin)
+                        for a in range(2) for b in range(2)])
+
+
+def deconv4x4s2(x, pack, scale=None, bias=None, relu=False, out=None):
+    """x (N,H,W,Cin) fp32 -> (N,2H,2W,Cout) = F.conv_transpose2d(x, weight, stride=2, padding=1) in NHWC, one launch for the four
+    output-parity classes, written interleaved (no scatter pass, no atomics; bit-repeatable and independent of the batch).
+    Epilogue: * scale[c] + bias[c] (ReLU) -- eval-mode BatchNorm folded; with neither operand the raw sums."""
+    N, H, W, Cin = _check(x).shape
+    assert Cin == pack.Cin, (Cin, pack.Cin)
+    pack_ready(pack)
+    if out is None:
+        out = torch.empty((N, 2 * H, 2 * W, pack.Cout), device=x.device, dtype=torch.float32)
+    assert tuple(_check(out).shape) == (N, 2 * H, 2 * W, pack.Cout)
+    for v in (scale, bias):
+        assert v is None or _check(v).numel() == pack.Cout
+    variant = ctypes.c_int(0) if TRACE_CONV_VARIANT[0] else None
+    _lib.call('cpr_deconv4x4s2_fwd', _ptr(x), _ptr(pack.w), _ptr(out), _ptr(scale), _ptr(bias), N, H, W, Cin, pack.Cout,
+              CONV_RELU if relu else 0, ctypes.byref(variant) if variant is not None else None, _stream())
+    if variant is not None:
+        TRACE_CONV_VARIANT[1] = ('deconv', variant.value)
+    return out
+
+
+def deconv4x4s2_dgrad_pack(weight):
+    """The pack of the data gradient of ``deconv4x4s2``: dx = conv2d(dy, weight, stride 2, padding 1) with the SAME tensor read as
+    (out = Cin, in = Cout, 4, 4) -- a plain forward pack."""
+    return PackedConv(weight, 2, 1)
+
+
+def deconv4x4s2_wgrad(dy, x, weight_shape, grad=None, out=None):
+    """Weight gradient (Cin, Cout, 4, 4) of ``deconv4x4s2``: the dense conv's weight gradient with the roles of the maps swapped -- the
+    'conv' reads dy (N,2H,2W,Cout) at stride 2 / padding 1 and writes x (N,H,W,Cin)."""
+    return conv2d_wgrad(x, dy, weight_shape, 2, 1, grad=grad, out=out)

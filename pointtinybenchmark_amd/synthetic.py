@@ -301,6 +301,30 @@ def hrfpn_state_dict(in_channels, out_channels=256, num_outs=5, seed=1, prefix='
     return sd
 
 
+def ctneck_layout(in_channel, num_deconv_filters):
+    """[(ConvModule key, conv shape)] of the reference's CTResNetNeck (ct_resnet_neck.py:37-61) in its state-dict order: per stage
+    ``deconv_layers.<2s>`` -- the 3x3 conv (F, Cin, 3, 3) -- and ``deconv_layers.<2s+1>`` -- the transposed conv (F, F, 4, 4), nn.ConvTranspose2d's
+    (in, out, kh, kw) layout.  No conv biases; every module has a ``bn``."""
+    out, c = [], in_channel
+    for s, f in enumerate(num_deconv_filters):
+        out.append(('deconv_layers.%d' % (2 * s), (f, c, 3, 3)))
+        out.append(('deconv_layers.%d' % (2 * s + 1), (f, f, 4, 4)))
+        c = f
+    return out
+
+
+def ctneck_state_dict(in_channel, num_deconv_filters, seed=1, prefix='neck.'):
+    """A state dict of the reference's CTResNetNeck layout (ctneck_layout): Kaiming-scaled conv weights -- the transposed convs at the
+    fan of their 2 x 2 live taps per output pixel -- and BatchNorms with non-trivial gammas, betas and running statistics (_bn)."""
+    g = torch.Generator().manual_seed(seed + 32452843)
+    sd = {}
+    for k, (key, shape) in enumerate(ctneck_layout(in_channel, num_deconv_filters)):
+        w = _kaiming(shape, g)
+        sd[prefix + key + '.conv.weight'] = w * 2.0 if k % 2 else w
+        _bn(sd, prefix + key + '.bn', shape[0], g)
+    return sd
+
+
 def hrnet_layout(extra, in_channels=3):
     """[(conv key, conv shape, norm key)] of the reference's HRNet (hrnet.py:267-518) in its state-dict order: conv1 / bn1, conv2 / bn2,
     layer1, then per stage its transition and its modules -- per module the branches' blocks, then ``fuse_layers.<i>.<j>``: for j > i

@@ -290,6 +290,11 @@ def _is_hrfpn(neck):
     return type(neck).__name__ == 'HRFPN'
 
 
+def _is_ctneck(neck):
+    """A CTResNetNeck (necks/ct_resnet_neck.py): one chain from the last backbone map to one upsampled map, BatchNorm on batch statistics."""
+    return type(neck).__name__ == 'CTResNetNeck'
+
+
 def _as_list(x):
     """One map or a sequence of maps -> a list (the bridge's segments carry a single map bare; the engine works on lists)."""
     return list(x) if isinstance(x, (list, tuple)) else [x]
@@ -337,6 +342,9 @@ class BackwardEngine:
             raise NotImplementedError(bb.fp32_only)      # (a RegNet backbone: backbones/regnet.py, naming ``arch``)
         if (getattr(bb, 'hrnet', False) or getattr(bb, 'darknet', False)) and bb.freeze_reason() is not None:      # (any (conv, BN) pair may be frozen, as a whole)
             raise NotImplementedError(bb.freeze_reason())
+        neck = getattr(model, 'neck', None)
+        if getattr(neck, 'fp32_only', None) and getattr(bb, 'compute_dtype', torch.float32) != torch.float32:
+            raise NotImplementedError(neck.fp32_only)       # (a CTResNetNeck: necks/ct_resnet_neck.py)
         dev = next(model.parameters()).device
         self._mixed, self._wide = False, {}     # set per step (bf16 compute mode = mixed precision)
         self._sink = None                       # None: p.grad (CprTrainer); dict: id(p) -> fresh tensor (autograd bridge)
@@ -446,6 +454,12 @@ class BackwardEngine:
         if _is_hrfpn(neck):     # the reduced map is the one boundary with a true gradient: run_fuse in front of it, run_outputs behind
             out = neck.run_fuse(list(xs), tape)
             return out, tape[0]
+        if _is_ctneck(neck):    # the whole neck: its output map is the boundary (xs: the last backbone map alone)
+            x, = xs
+            out = neck.run(x, tape)
+            if tape[-1]['o2'] is out:      # (not the sliced copy of a padded last stage)
+                tape[-1]['o2'] = out.detach()      # (no autograd output reachable from its own state, autograd_bridge.py "Functions")
+            return out, tape
         lat = neck.run_laterals(list(xs), tape)
         n = min(len(lat), neck.num_outs)        # the regular output convs (fpn_convs may hold extra levels behind them)
         return (lat[0] if n == 1 else tuple(lat[:n])), {r['level']: r for r in tape}
@@ -461,6 +475,9 @@ class BackwardEngine:
             ok = pair is not None and pair[0].shape == d_out.shape and pair[0].data_ptr() == d_out.data_ptr()
             d_stage = self._backward_hrfpn_inputs(neck, recs, d_out, pair[1] if ok else None, need_dx_of=lambda stage: need[stage])
             return [d_stage.get(i) for i in range(len(need))]
+        if _is_ctneck(neck):
+            d_out, = _as_list(dlat)
+            return [self._backward_ctneck(neck, recs, d_out, need_dx=need[0])]
         d_stage = self._backward_laterals(neck, recs, _as_list(dlat), need_dx_of=lambda stage: need[stage - neck.start_level])
         return [d_stage.get(i + neck.start_level) for i in range(len(need))]
 
@@ -834,6 +851,8 @@ class BackwardEngine:
         refine = [_gn_conv(bfp.refine)] if bfp is not None and bfp.refine_type is not None else []
         if _is_hrfpn(neck):
             return refine + cls._hrfpn_units(neck)
+        if _is_ctneck(neck):
+            return refine + cls._ctneck_units(neck)
         convs = list(neck.fpn_convs)
         regular = min(len(neck.lateral_convs), neck.num_outs)
         outputs = cls._pafpn_units(neck, regular) if _is_pafpn(neck) else [_gn_conv(cm) for cm in convs[:regular]]
@@ -847,6 +866,10 @@ class BackwardEngine:
             by = {r['kind']: r for r in neck_tape}
             d_out, part = self._backward_hrfpn_outputs(neck, by['hrfpn_out'], _as_list(dz))
             return self._backward_hrfpn_inputs(neck, by['hrfpn_in'], d_out, part)
+        if _is_ctneck(neck):    # the gradient goes to the last neck input, the only one the neck reads
+            d_out, = _as_list(dz)
+            last = neck_tape[0]['n_in'] - 1
+            return {last: self._backward_ctneck(neck, neck_tape, d_out, need_dx=self._stage_trainable(last))}
         lat_recs = {r['level']: r for r in neck_tape if r['kind'] == 'lateral'}
         dlats, d_src = self._backward_outputs(neck, [r for r in neck_tape if r['kind'] != 'lateral'], _as_list(dz))
         d_stage = self._backward_laterals(neck, lat_recs, dlats)
@@ -865,6 +888,8 @@ class BackwardEngine:
             d_out, part = self._backward_hrfpn_outputs(neck, recs[0], dzs)
             self._hr_colsum = (d_out, part)
             return [d_out], None
+        if _is_ctneck(neck):    # (autograd bridge: nothing sits between the neck's output map and the head)
+            return list(dzs), None
         bfp_recs = [r for r in recs if r['kind'].startswith('bfp_')]
         if bfp_recs:
             dzs = self._backward_bfp(neck.bfp, bfp_recs, dzs)
@@ -949,6 +974,57 @@ class BackwardEngine:
             d_stage[i] = ops.conv2d_dgrad(dy, neck.level_dgrad_pack(i, pitch), tuple(sizes[i])) if need else None
         self._done_last(*self._hrfpn_units(neck))
         return d_stage
+
+    @staticmethod
+    def _ctneck_units(neck):     # per stage, last first: the transposed conv and its BatchNorm, then the 3x3 conv and its BatchNorm
+        return [u for cm, dm in reversed(neck.stages()) for u in (_conv_bn(dm.conv, dm.bn), _conv_bn(cm.conv, cm.bn))]
+
+    def _backward_ctneck(self, neck, recs, dz, need_dx=True):
+        """CTResNetNeck in reverse (necks/ct_resnet_neck.py run; T/mmdet/models/necks/ct_resnet_neck.py:37-61, :89-93), batch-statistics
+        BatchNorm throughout.  Per stage, last first: the BatchNorm backward with the ReLU mask (dgamma / dbeta on the main stream), the
+        transposed conv's weight gradient (side stream; the dense weight-gradient kernel with the maps' roles swapped) and data gradient
+        (its weight read as a (Cin, Cout, 4, 4) stride-2 conv over the gradient map), then the same for the 3x3 conv.  recs: the
+        'ct_stage' records.  dz: the fp32 gradient of the neck's output map.  -> the gradient of the neck's input (None unless need_dx)."""
+        stages = neck.stages()
+        g = dz.contiguous()
+        pad = recs[-1]['o2'].shape[-1] - g.shape[-1]
+        if pad:                 # the last stage ran at its padded pitch: zero gradient in the pad channels
+            g = torch.nn.functional.pad(g, (0, pad))
+        for rec in reversed(recs):
+            cm, dm = stages[rec['stage']]
+            x, o1 = rec['x'], rec['o1']
+            for m, st, gamma, y, mask in ((dm, rec['s2'], rec['g2'], rec['y2'], rec['o2']), (cm, rec['s1'], rec['g1'], rec['y1'], o1)):
+                bn, w = m.bn, m.conv.weight
+                f, fp = bn.num_features, y.shape[-1]       # fp > f: maps at the padded pitch, gradients at the padded shape into scratch
+                aff, direct = bn.weight.requires_grad, fp == bn.num_features
+                dy, dg, db = ops.bn_train_bwd(g, y, st.cmean, st.rstd, gamma, mask=mask, center=st.center,
+                                              out_dgamma=self._g(bn.weight) if aff and direct else None,
+                                              out_dbeta=self._g(bn.bias) if aff and direct else None)
+                if aff and not direct:
+                    self._g(bn.weight).copy_(dg[:f])
+                    self._g(bn.bias).copy_(db[:f])
+                if m is dm:
+                    if w.requires_grad:
+                        def wgrad(dy=dy, o1=o1, w=w, f=f, fp=fp):
+                            if fp == f:
+                                ops.deconv4x4s2_wgrad(dy, o1, w.shape, out=self._g(w))
+                            else:
+                                self._g(w).copy_(ops.deconv4x4s2_wgrad(dy, o1, (fp, fp, 4, 4))[:f, :f])
+                        self._param_side(wgrad, dy, o1)
+                    g = ops.conv2d(dy, neck.deconv_dgrad_pack(dm, fp))
+                else:
+                    cp = x.shape[-1]
+                    if w.requires_grad:
+                        def wgrad(dy=dy, x=x, w=w, f=f, fp=fp, cp=cp):
+                            if (fp, cp) == tuple(w.shape[:2]):
+                                ops.conv2d_wgrad(dy, x, w.shape, 1, 1, out=self._g(w))
+                            else:
+                                self._g(w).copy_(ops.conv2d_wgrad(dy, x, (fp, cp, 3, 3), 1, 1)[:f, :w.shape[1]])
+                        self._param_side(wgrad, dy, x)
+                    need = rec['stage'] > 0 or need_dx
+                    g = ops.conv2d_dgrad(dy, dgrad_packed_padded(neck._cache, cm.conv, None, fp, cp), (x.shape[1], x.shape[2]), 1) if need else None
+                self._done_last(_conv_bn(m.conv, bn))
+        return g
 
     def _backward_extras(self, neck, recs, dzs, need_src=None):
         """The extra pyramid levels, last first (T/mmdet/models/necks/fpn.py:195-217).  dzs: one gradient per output level, the extras'
@@ -1819,6 +1895,8 @@ class CprTrainer(BackwardEngine):
             n_levels = inner.num_outs
             if type(model.bbox_head).__name__ == 'CPRHead' and n_levels != 1:
                 raise NotImplementedError('CPRHead takes one pyramid level (cpr_head.py:487); this HRFPN has %d output levels' % n_levels)
+        elif _is_ctneck(inner):
+            n_levels = 1
         else:
             n_levels = min(len(inner.lateral_convs), inner.num_outs) + getattr(inner, 'extra_levels', 0)
         if _is_pafpn(inner) and type(model.bbox_head).__name__ == 'CPRHead' and n_levels != 1:
