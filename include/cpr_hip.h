@@ -536,8 +536,10 @@ int cpr_res2_conv_wgrad_workspace(int N, int OH, int OW, int width);
 int cpr_res2_conv_wgrad(const float* dy, int dy_pitch, int dy_off, const float* x, int x_pitch, int x_off, const float* add, int add_pitch,
                         int add_off, float* grad_w, float* ws, int N, int H, int W, int width, int stride, int accumulate, void* stream);
 /* Backward of a slice's ReLU, in place: g slice = (g slice (+ carry slice)) * (y slice > 0) over M pixels, and colsum[width] = the
- * per-channel sums of the result (chunk partials in ws, ceil(M / 256) * width floats, added in ascending order: no atomics).
- * carry may be NULL. */
+ * per-channel sums of the result (chunk partials in ws, cpr_res2_relu_bwd_colsum_ws(M, width) floats, added in ascending order: no
+ * atomics).  carry may be NULL.  _ws: M <= 0 or a width the slice kernels do not take is CPR_ERR_ARG, 2^31 floats or more
+ * CPR_ERR_UNSUPPORTED. */
+int cpr_res2_relu_bwd_colsum_ws(long long M, int width);
 int cpr_res2_relu_bwd_colsum(float* g, int g_pitch, int g_off, const float* carry, int c_pitch, int c_off, const float* y, int y_pitch,
                              int y_off, float* colsum, float* ws, long long M, int width, void* stream);
 /* The last slice of a stage block: stride 2: AvgPool2d(3, 2, padding 1) with the divisor always 9 (count_include_pad), (H, W) ->

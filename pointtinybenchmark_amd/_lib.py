@@ -149,6 +149,7 @@ SIGNATURES = {
     'cpr_res2_conv_wgrad_workspace': [_i] * 4,
     'cpr_res2_conv_wgrad': [_p, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p] + [_i] * 6 + [_p],
     'cpr_res2_pool_fwd': [_p, _i, _i, _p, _i, _i] + [_i] * 5 + [_p],
+    'cpr_res2_relu_bwd_colsum_ws': [_l, _i],
     'cpr_res2_relu_bwd_colsum': [_p, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _l, _i, _p],
     'cpr_res2_pool_bwd': [_p, _i, _i, _p, _i, _i] + [_i] * 5 + [_p],
     'cpr_splat_chunks': [_i] * 3,

@@ -441,6 +441,14 @@ extern "C" int cpr_res2_pool_bwd(const float* dy, int dy_pitch, int dy_off, floa
     CPR_LAUNCH_STATUS();
 }
 
+// floats of workspace cpr_res2_relu_bwd_colsum needs for M pixels of a slice: one row of `width` partials per chunk of R2_CS_PIX pixels
+extern "C" int cpr_res2_relu_bwd_colsum_ws(long long M, int width) {
+    if (M <= 0 || !r2_width_ok(width)) return CPR_ERR_ARG;
+    if (M > 0x7fffffffll) return CPR_ERR_UNSUPPORTED;
+    const long long n = cdivll(M, R2_CS_PIX) * width;
+    return n < (1ll << 31) ? (int)n : CPR_ERR_UNSUPPORTED;
+}
+
 // g slice (in place) = (g slice (+ carry slice)) * (y slice > 0); colsum[width] = its per-channel sums over the M pixels.  carry may be NULL.
 extern "C" int cpr_res2_relu_bwd_colsum(float* g, int g_pitch, int g_off, const float* carry, int c_pitch, int c_off, const float* y,
                                         int y_pitch, int y_off, float* colsum, float* ws, long long M, int width, hipStream_t stream) {

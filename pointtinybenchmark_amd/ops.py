@@ -2500,7 +2500,7 @@ def res2_relu_bwd(g, g_off, y, y_off, width, carry=None, carry_off=0):
     cp = _res2_map(carry)[3] if carry is not None else 0
     M = N * H * W
     cs = torch.empty((width,), device=g.device, dtype=torch.float32)
-    ws = torch.empty(((M + 255) // 256 * max(width, 0),), device=g.device, dtype=torch.float32)
+    ws = torch.empty((_lib.call('cpr_res2_relu_bwd_colsum_ws', M, width, positive=True),), device=g.device, dtype=torch.float32)
     _lib.call('cpr_res2_relu_bwd_colsum', _ptr(g), gp, g_off, _ptr(carry), cp, carry_off, _ptr(y), yp, y_off, _ptr(cs), _ptr(ws), M, width,
               _stream())
     return cs
